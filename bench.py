@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the batched balance-robot simulator (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536] [--env Env03-v2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536] [--env Env03-v2] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2]): Env03-v2, 65,536 env instances PER GPU, random policy
 (actions ~ U(-1,1)^2, device generator seed 1234), auto-reset on; one "step" = one env step of every instance =
 250 physics substeps each.  Inputs (state, pre-generated action batches) are resident in HBM when timing starts.
 N > 1: launched by torch.distributed.run, one rank per GPU; instances shard by global index, no collective on the
 step path (weak scaling).  Rank 0 prints ONE JSON line.
+
+A plain run measures the headline figure only.  --full adds what takes runs of its own: the two CPU baselines on the host
+cores.  --dump-outputs DIR writes what the last timed step returned (BatchedSim.step: obs, reward, terminated, truncated,
+terminal_obs) as float32 .npy files; the pre-roll has a fixed length, so the same arguments give the same inputs every run.
 """
 import argparse
 import json
@@ -103,6 +107,24 @@ def spawn_ranks(args):
     return proc.returncode if line is not None or proc.returncode else 1
 
 
+STEP_OUTPUTS = ("obs", "reward", "terminated", "truncated", "terminal_obs")  # BatchedSim.step's return value, in order
+DUMP_BYTES_MAX = 60 << 20  # the dump stays under 64 MB, .npy headers included
+
+
+def dump_outputs(sim, out_dir, n, suffix=""):
+    """--dump-outputs: the arrays the last step handed its caller, as float32 .npy.  If they exceed DUMP_BYTES_MAX, a fixed
+    seeded sample of env rows is written instead, with the rows' indices in env_index.npy"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: getattr(sim, k).float().cpu().numpy() for k in STEP_OUTPUTS}
+    per_env = sum(a.nbytes for a in arrays.values()) // n
+    if per_env * n > DUMP_BYTES_MAX:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES_MAX // (per_env + 8), replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), a)
+
+
 class SubBatches:
     """--streams S: the envs of one GPU as S handles of n/S envs (contiguous global env indices, same Philox streams as
     the single handle), each stepping on its own HIP stream.  step(k) enqueues one launch per handle and returns; there
@@ -135,6 +157,11 @@ class SubBatches:
     def terminated(self):
         return torch.cat([sim.terminated for sim in self.sims])
 
+    def __getattr__(self, name):  # the other step outputs (obs, reward, truncated, terminal_obs), in global env order
+        if name in STEP_OUTPUTS:
+            return torch.cat([getattr(sim, name) for sim in self.sims])
+        raise AttributeError(name)
+
     def step_bytes_per_env(self):
         return self.sims[0].step_bytes_per_env()
 
@@ -151,10 +178,16 @@ def main():
     ap.add_argument("--env", default="Env03-v2")
     ap.add_argument("--block-threads", type=int, default=0)
     ap.add_argument("--preroll", type=int, default=300,
-                    help="minimum untimed env steps after reset(), on top of --warmup: all episodes start in phase (2 cm "
-                         "drop, no contacts, first block in flight); the pre-roll runs until falls and auto-resets have "
-                         "de-phased them and the per-step kernel time is stationary")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="untimed env steps after reset(), on top of --warmup, in windows of 50: all episodes start in phase "
+                         "(2 cm drop, no contacts, first block in flight); the pre-roll lets falls and auto-resets de-phase "
+                         "them until the per-step kernel time is stationary.  Fixed length, so that the timed steps see the "
+                         "same inputs on every run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the two CPU baselines on the host cores")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (obs, reward, terminated, truncated, terminal_obs) as "
+                         "DIR/<name>.npy in float32 (rank r > 0: <name>_rank<r>.npy)")
     ap.add_argument("--streams", type=int, default=1,
                     help="split the envs of a GPU over this many handles, each stepping on its own HIP stream with no barrier "
                          "between them until the end (asynchronous sub-batches: a finished sub-batch's SIMDs are back-filled "
@@ -219,9 +252,10 @@ def main():
         torch.cuda.synchronize(dev)
 
     # ---- untimed pre-roll to steady state (independent of --warmup): windows of 50 steps, HIP-event time per window;
-    # stop once `--preroll` steps are done AND two consecutive windows agree within 2 %, or at the cap
+    # a fixed number of them (`--preroll` steps, rounded up), so the state entering the timed steps is the same every run;
+    # `preroll_stationary` in the result line says whether the last two windows agreed within 2 %
     kstep = 0
-    win, cap = 50, max(args.preroll, 1500)
+    win = 50
     win_ms = []
     while True:
         if S > 1:  # no single stream sees all launches: wall clock around a synchronised window
@@ -240,7 +274,7 @@ def main():
             e1.synchronize()
             win_ms.append(e0.elapsed_time(e1) / win)
         stationary = len(win_ms) >= 2 and abs(win_ms[-1] - win_ms[-2]) <= 0.02 * win_ms[-2]
-        if (kstep >= args.preroll and stationary) or kstep >= cap:
+        if kstep >= args.preroll:
             break
     preroll = kstep
     for _ in range(args.warmup):
@@ -273,6 +307,8 @@ def main():
         kms = np.array([a.elapsed_time(b) for a, b in zip(ev0, ev1)])
     kern_ms = float(kms.mean())
     n_done = int(sim.terminated.sum().item())  # touches the outputs (also proves the last step ran)
+    if args.dump_outputs:
+        dump_outputs(sim, args.dump_outputs, n, "" if world == 1 else f"_rank{rank}")
 
     if rank == 0:
         total_envs = n * world
@@ -286,7 +322,7 @@ def main():
             "config": {"workload": f"{args.env}, {n} env instances per GPU ({total_envs} total), random policy "
                                    f"U(-1,1)^2, auto-reset on, 250 substeps of 2e-5 s per env step",
                        "envs_per_gpu": n, "substeps": 250, "parallelism": f"env-sharded x{world}, no collective",
-                       "lane_grouping": not args.no_lane_grouping, "streams": S, "preroll_steps": preroll, "preroll_window_ms_per_step": [round(x, 4) for x in win_ms]},
+                       "lane_grouping": not args.no_lane_grouping, "streams": S, "preroll_steps": preroll, "preroll_stationary": stationary, "preroll_window_ms_per_step": [round(x, 4) for x in win_ms]},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                          "kernel": sim.step_kernel_name(), "kernel_ms": kern_ms,
@@ -330,7 +366,7 @@ def main():
                         out["roofline"]["binding_resource"] = "valu_issue"
             except Exception as e:
                 out["roofline"]["stale_profile"] = f"profile summary unreadable: {e}"
-        if not args.no_cpu_baseline:  # rank 0's host cores, whatever the world size
+        if args.full and not args.no_cpu_baseline:  # rank 0's host cores, whatever the world size
             out["cpu_baseline"] = cpu_baseline(args.env)
             try:
                 out["cpu_baseline_closed_form"] = cpu_baseline_closed_form(args.env)

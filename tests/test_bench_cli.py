@@ -71,3 +71,51 @@ def test_spawned_two_ranks_on_one_gpu_report_the_whole_job():
     # aggregate over both ranks: 2 x 4096 envs per step of the slower rank
     assert abs(d["value"] - 2 * 4096 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
     assert d["value"] > 1e5
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+class _FakeSim:
+    """the step outputs of a BatchedSim (obs, reward, terminated, truncated, terminal_obs), on the CPU"""
+
+    def __init__(self, n):
+        import torch
+        g = torch.Generator().manual_seed(n)
+        self.obs, self.terminal_obs = torch.randn(n, 6, generator=g), torch.randn(n, 6, generator=g)
+        self.reward = torch.randn(n, generator=g)
+        self.terminated = torch.randint(0, 2, (n,), dtype=torch.uint8, generator=g)
+        self.truncated = torch.randint(0, 2, (n,), dtype=torch.uint8, generator=g)
+
+
+def test_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """--dump-outputs DIR: one float32 .npy per step output, every env, values as the step returned them"""
+    import numpy as np
+    bench, sim = _load_bench(), _FakeSim(1000)
+    bench.dump_outputs(sim, str(tmp_path), 1000)
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{k}.npy" for k in bench.STEP_OUTPUTS)
+    for k in bench.STEP_OUTPUTS:
+        a = np.load(tmp_path / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, getattr(sim, k).float().numpy())
+
+
+def test_dump_outputs_of_a_large_batch_is_a_fixed_sample_under_64_mb(tmp_path):
+    import numpy as np
+    bench, n = _load_bench(), 1_200_000
+    sim = _FakeSim(n)
+    for d in ("a", "b"):
+        bench.dump_outputs(sim, str(tmp_path / d), n)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "env_index.npy")) and len(np.unique(idx)) == len(idx) < n
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "obs.npy"), sim.obs.numpy()[idx.astype(np.int64)])
+
+
+def test_help_lists_full_and_dump_outputs():
+    p = subprocess.run([sys.executable, BENCH, "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout

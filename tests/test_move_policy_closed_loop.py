@@ -118,29 +118,20 @@ def test_mujoco_trained_policy_balances_the_hip_path():
         sim.close(); pol.close()
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/balance_robot/envs/RobotMovePolicy.tflite"),
-                    reason="the reference checkout is only present in the build container")
 def test_fixture_regenerates_from_the_reference_file():
-    """tools/gen_policy_fixture.py run again on the reference's .tflite gives the committed arrays (nothing hand-edited)"""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    from tflite_reader import read_tflite
-    m = read_tflite("/root/reference/src/balance_robot/envs/RobotMovePolicy.tflite")
+    """the committed arrays are the reference's .tflite tensors (nothing hand-edited): checked against the digests
+    tools/gen_policy_fixture.py took from the file itself (tests/golden/robot_move_policy_tflite.json: the walk of output[1],
+    the actions the reference reads, back to the input; sha256 of each quantised tensor, scales, zero points)"""
+    import hashlib, json
+    d = json.load(open(os.path.join(ROOT, "tests", "golden", "robot_move_policy_tflite.json")))
     z = np.load(os.path.join(ROOT, "tests", "golden", "robot_move_policy.npz"))
-    T = m["tensors"]
-    ops = {o["outputs"][0]: o for o in m["operators"]}
-    # walk output[1] (the actions the reference reads) back to the input
-    t, fcs = m["outputs"][1], []
-    while t != m["inputs"][0]:
-        o = ops[t]
-        if o["op"] == "FULLY_CONNECTED":
-            fcs.append(o)
-        t = o["inputs"][0]
-    fcs.reverse()
-    assert len(fcs) == 3
-    for k, o in enumerate(fcs):
-        np.testing.assert_array_equal(z[f"fc{k}_weight_q"], T[o["inputs"][1]]["data"])
-        np.testing.assert_array_equal(z[f"fc{k}_bias_q"], T[o["inputs"][2]]["data"])
-        np.testing.assert_allclose(z[f"fc{k}_weight_scale"], np.asarray(T[o["inputs"][1]]["scale"], np.float64))
-        np.testing.assert_allclose(z[f"fc{k}_out_scale"], np.asarray(T[o["outputs"][0]]["scale"], np.float64))
-    np.testing.assert_allclose(z["input_scale"], np.asarray(T[m["inputs"][0]]["scale"], np.float64))
-    assert int(z["input_zero_point"][0]) == T[m["inputs"][0]]["zero_point"][0]
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    assert d["ops"].count("FULLY_CONNECTED") == 3 and len(d["fc"]) == 3
+    for k, f in enumerate(d["fc"]):
+        assert z[f"fc{k}_weight_q"].dtype == np.int8 and list(z[f"fc{k}_weight_q"].shape) == f["weight_q_shape"]
+        assert z[f"fc{k}_bias_q"].dtype == np.int32
+        assert sha(z[f"fc{k}_weight_q"]) == f["weight_q_sha256"] and sha(z[f"fc{k}_bias_q"]) == f["bias_q_sha256"]
+        np.testing.assert_allclose(z[f"fc{k}_weight_scale"], np.asarray(f["weight_scale"], np.float64))
+        np.testing.assert_allclose(z[f"fc{k}_out_scale"], np.asarray(f["out_scale"], np.float64))
+    np.testing.assert_allclose(z["input_scale"], np.asarray(d["input_scale"], np.float64))
+    assert int(z["input_zero_point"][0]) == d["input_zero_point"][0]

@@ -2,7 +2,7 @@
 """Turns the policy the reference ships (ref: src/balance_robot/envs/RobotMovePolicy.tflite -- an int8-quantised export of an SB3
 PPO MlpPolicy, loaded by ref:envs/RobotMoveBaseEnv.py:81-98 and driven at :178-208) into a plain weights fixture:
 
-    python tools/gen_policy_fixture.py  ->  tests/golden/robot_move_policy.npz
+    python tools/gen_policy_fixture.py  ->  tests/golden/robot_move_policy.npz, tests/golden/robot_move_policy_tflite.json
 
 The file is DATA of the reference (quantised weights, biases, scales, zero points of the actor path input -> output[1],
 the tensor RobotMoveBaseEnv reads), parsed by tools/tflite_reader.py -- nothing from the file is executed, no TFLite runtime
@@ -71,3 +71,18 @@ assert k == 3
 dst = os.path.join(ROOT, "tests", "golden", "robot_move_policy.npz")
 np.savez_compressed(dst, **out)
 print("wrote", dst, os.path.getsize(dst), "bytes;", {k: v.shape for k, v in out.items() if k.endswith("_q")})
+# digests of the same tensors, taken from the file itself: tests/test_move_policy_closed_loop.py checks the npz against them
+# without the .tflite (walk of output[1] back to the input; sha256 of the raw little-endian tensor bytes)
+import hashlib, json
+sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+digest = dict(source="RobotMovePolicy.tflite", source_sha256=hashlib.sha256(open(SRC, "rb").read()).hexdigest(),
+              ops=[o["op"] for o in chain], input_scale=[float(x) for x in T[m["inputs"][0]]["scale"]],
+              input_zero_point=[int(x) for x in T[m["inputs"][0]]["zero_point"]], fc=[])
+for o in chain:
+    if o["op"] == "FULLY_CONNECTED":
+        a, w, b = o["inputs"]
+        digest["fc"].append(dict(weight_q_sha256=sha(T[w]["data"]), weight_q_shape=list(T[w]["data"].shape), bias_q_sha256=sha(T[b]["data"]),
+                                 weight_scale=[float(x) for x in T[w]["scale"]], out_scale=[float(x) for x in T[o["outputs"][0]]["scale"]]))
+dst = os.path.join(ROOT, "tests", "golden", "robot_move_policy_tflite.json")
+json.dump(digest, open(dst, "w"), indent=1)
+print("wrote", dst)

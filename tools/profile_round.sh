@@ -9,7 +9,7 @@ ENVARG=${2:-Env03-v2}
 mkdir -p $OUT
 export TMPDIR=/tmp
 ROOT=$(pwd)
-python3 bench.py --env $ENVARG --steps 300 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --env $ENVARG --steps 300 --warmup 20 --full > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/trace -o trace -- python3 $ROOT/bench.py --env $ENVARG --steps 300 --warmup 20 --no-cpu-baseline > $ROOT/$OUT/bench_traced.json 2> $ROOT/$OUT/trace.err
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_SALU SQ_INSTS_LDS" \
