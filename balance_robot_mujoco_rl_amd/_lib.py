@@ -8,8 +8,12 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libbrs_hip.so")
 SRC = os.path.join(_PKG, "csrc", "brs_kernels.hip")
 SRC_POLICY = os.path.join(_PKG, "csrc", "brs_policy.hip")
+SRC_RENDER = os.path.join(_PKG, "csrc", "brs_render.hip")
 HEADERS = [os.path.join(_PKG, "csrc", h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp")] + \
           [os.path.join(os.path.dirname(_PKG), "include", h) for h in ("brs.h", "brs_policy.h")]
+# the renderer (include/brs_render.h) is built into the same library but stays out of the build id, which identifies the
+# step and policy kernels that committed profiles were measured on
+HEADERS_RENDER = [os.path.join(_PKG, "csrc", "brs_render.hpp"), os.path.join(os.path.dirname(_PKG), "include", "brs_render.h")]
 
 # every symbol include/brs.h declares
 SYMBOLS = ["brs_create", "brs_destroy", "brs_last_error", "brs_sizes", "brs_reset", "brs_step", "brs_physics",
@@ -18,6 +22,8 @@ SYMBOLS = ["brs_create", "brs_destroy", "brs_last_error", "brs_sizes", "brs_rese
            # include/brs_policy.h
            "brs_policy_create", "brs_policy_destroy", "brs_policy_last_error", "brs_policy_set_weights",
            "brs_policy_use_device_weights", "brs_policy_act", "brs_policy_value", "brs_rollout_bootstrap", "brs_gae"]
+# every symbol include/brs_render.h declares
+RENDER_SYMBOLS = ["brs_render_default_camera", "brs_render", "brs_render_last_error"]
 POLICY_NPARAM = (64 * 6 + 64 + 64 * 64 + 64 + 2 * 64 + 2) + (64 * 6 + 64 + 64 * 64 + 64 + 64 + 1) + 2
 
 
@@ -25,6 +31,11 @@ class BrsConfig(C.Structure):
     _fields_ = [("variant", C.c_int32), ("num_envs", C.c_int32), ("device", C.c_int32), ("flags", C.c_uint32),
                 ("seed", C.c_uint64), ("env_index_base", C.c_int64), ("max_episode_steps", C.c_int32),
                 ("substeps", C.c_int32), ("timestep", C.c_double), ("block_threads", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BrsCamera(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fovy_deg", C.c_float), ("distance", C.c_float),
+                ("azimuth_deg", C.c_float), ("elevation_deg", C.c_float)]
 
 
 FLAG_AUTO_RESET, FLAG_NOISE_ON, FLAG_NOISE_OFF, FLAG_NO_LANE_GROUPING = 1, 2, 4, 8
@@ -40,7 +51,7 @@ def hipcc_path():
 def build(force=False, verbose=False, out=None, extra_flags=()):
     """compile the HIP kernels + C ABI for gfx950 in-tree (hipcc cross-compiles without a GPU).  `out` / `extra_flags`: an A/B
     build next to the product library (tools/ab_build.py; loaded only when BRS_HIP_LIB points at it)"""
-    srcs = [SRC, SRC_POLICY] + HEADERS
+    srcs = [SRC, SRC_POLICY, SRC_RENDER] + HEADERS + HEADERS_RENDER
     if out is not None:
         return _compile(out, verbose, list(extra_flags), tag="_" + os.path.splitext(os.path.basename(out))[0])
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -77,7 +88,10 @@ def _compile(lib_path, verbose, extra_flags, tag):
     subprocess.check_call(base + sim_flags + ["-c", "-o", obj_sim, SRC])
     # policy / GAE kernels: IEEE math (tanh, exp, log at libm accuracy): the parity test is rtol 1e-5 against fp32 torch
     subprocess.check_call(base + ["-c", "-o", obj_pol, SRC_POLICY])
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path, obj_sim, obj_pol])
+    # renderer: IEEE math, like its host build in tests/renderhost that the CPU tests compare with the numpy reference
+    obj_ren = os.path.join(_PKG, "csrc", f"brs_render{tag}.o")
+    subprocess.check_call(base + (["-Rpass-analysis=kernel-resource-usage"] if verbose else []) + ["-c", "-o", obj_ren, SRC_RENDER])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path, obj_sim, obj_pol, obj_ren])
     return lib_path
 
 
@@ -126,6 +140,11 @@ def lib():
     L.brs_policy_value.argtypes = [vp, i32, vp, vp, vp]
     L.brs_rollout_bootstrap.argtypes = [vp, i32, vp, vp, vp, f32, vp, vp]
     L.brs_gae.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp]
+    L.brs_render_default_camera.argtypes = [C.POINTER(BrsCamera)]
+    L.brs_render_default_camera.restype = None
+    L.brs_render.argtypes = [i32, i32, i32, vp, C.POINTER(BrsCamera), vp, vp, vp, vp]
+    L.brs_render_last_error.argtypes = []
+    L.brs_render_last_error.restype = C.c_char_p
     _lib = L
     return L
 

@@ -185,3 +185,64 @@ class BatchedSim:
 
     def step_kernel_name(self):
         return self.L.brs_step_kernel_name(self.h).decode()
+
+    # ------------------------------------------------------------------ rendering (include/brs_render.h)
+    def render(self, env_ids=None, camera=None, depth=False, segmentation=False):
+        """rgb_array images of the envs `env_ids` (indices into this handle; default all), through the reference's
+        follow camera.  `camera`: dict overriding any of width, height, fovy, distance, azimuth, elevation.
+
+        -> rgb [K,H,W,3] uint8 device tensor; with depth / segmentation: (rgb, depth [K,H,W] f32, seg [K,H,W] uint8), only
+        the requested ones, in that order.  Poses come from brs_get_state (host, synchronous); the kernel is enqueued on
+        the current stream of the handle's device."""
+        ids = _env_ids(env_ids, self.n)
+        cam = make_camera(camera)
+        qpos = np.ascontiguousarray(self.get_state()[0][ids])
+        k, H, W = len(ids), cam.height, cam.width
+        q = torch.from_numpy(qpos).to(self.device, non_blocking=False)
+        rgb = torch.empty((k, H, W, 3), dtype=torch.uint8, device=self.device)
+        dep = torch.empty((k, H, W), dtype=torch.float32, device=self.device) if depth else None
+        seg = torch.empty((k, H, W), dtype=torch.uint8, device=self.device) if segmentation else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        rc = self.L.brs_render(self.device.index, self.spec.variant, k, ptr(q), C.byref(cam), ptr(rgb), ptr(dep), ptr(seg),
+                               self._stream())
+        if rc != 0:
+            raise BrsError(f"brs_render failed ({rc}): {self.L.brs_render_last_error().decode()}")
+        out = [rgb] + ([dep] if depth else []) + ([seg] if segmentation else [])
+        return out[0] if len(out) == 1 else tuple(out)
+
+
+_CAMERA_KEYS = {"width": "width", "height": "height", "fovy": "fovy_deg", "distance": "distance", "azimuth": "azimuth_deg",
+                "elevation": "elevation_deg"}
+
+
+def make_camera(camera=None):
+    """brs_camera of the reference's default camera, with the entries of the dict `camera` overridden (validated here,
+    before anything crosses the C ABI)"""
+    cam = _lib.BrsCamera(800, 800, 45.0, 1.25, 45.0, -25.0)
+    for key, val in (camera or {}).items():
+        if key not in _CAMERA_KEYS:
+            raise ValueError(f"unknown camera entry {key!r}; expected some of {sorted(_CAMERA_KEYS)}")
+        if key in ("width", "height"):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or not 1 <= val <= 4096:
+                raise ValueError(f"camera {key} must be an integer in [1, 4096], got {val!r}")
+        elif isinstance(val, bool) or not isinstance(val, (int, float, np.integer, np.floating)) or not np.isfinite(val):
+            raise ValueError(f"camera {key} must be a finite number, got {val!r}")
+        setattr(cam, _CAMERA_KEYS[key], val)
+    if not 0 < cam.fovy_deg < 180:
+        raise ValueError(f"camera fovy must be in (0, 180), got {cam.fovy_deg}")
+    if not cam.distance > 0:
+        raise ValueError(f"camera distance must be > 0, got {cam.distance}")
+    return cam
+
+
+def _env_ids(env_ids, n):
+    """validated env indices (int64 numpy, 1-D, non-empty, each in [0, n))"""
+    if env_ids is None:
+        return np.arange(n)
+    ids = env_ids.cpu().numpy() if isinstance(env_ids, torch.Tensor) else np.asarray(env_ids)
+    ids = ids.reshape(-1) if ids.ndim == 0 else ids
+    if ids.ndim != 1 or ids.size == 0 or ids.dtype == np.bool_ or not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError(f"env_ids must be a non-empty 1-D sequence of integers, got {env_ids!r}")
+    if ids.min() < 0 or ids.max() >= n:
+        raise IndexError(f"env_ids must lie in [0, {n}), got range [{ids.min()}, {ids.max()}]")
+    return ids.astype(np.int64)

@@ -122,6 +122,18 @@ def make_spaces():
     return _Box(-hi, hi, dtype=np.float32), _Box(-np.ones(2, np.float32), np.ones(2, np.float32), dtype=np.float32)
 
 
+def tile_images(images):
+    """[n, H, W, C] -> one [rows*H, cols*W, C] image: rows = ceil(sqrt(n)), cols = ceil(n / rows), filled row by row,
+    empty cells black (the layout of SB3's VecEnv.render / tile_images)"""
+    imgs = np.asarray(images)
+    n, h, w, c = imgs.shape
+    rows = int(np.ceil(np.sqrt(n)))
+    cols = int(np.ceil(n / rows))
+    grid = np.zeros((rows * cols, h, w, c), dtype=imgs.dtype)
+    grid[:n] = imgs
+    return grid.reshape(rows, cols, h, w, c).transpose(0, 2, 1, 3, 4).reshape(rows * h, cols * w, c)
+
+
 def shard_ranges(num_envs, num_shards):
     """contiguous, near-equal env-index ranges [(start, count), ...]"""
     base, rem = divmod(num_envs, num_shards)
@@ -134,13 +146,21 @@ def shard_ranges(num_envs, num_shards):
 
 
 class BalanceVecEnv(_VecEnvBase):
-    metadata = {"render_modes": [], "render_fps": 200}
+    metadata = {"render_modes": ["rgb_array"], "render_fps": 200}
 
     def __init__(self, env_id, num_envs, devices=None, seed=0, obs_noise=None, max_episode_steps=0, env_index_base=0,
-                 sparse_infos=True, _sims=None):
+                 sparse_infos=True, render_mode=None, render_envs=(0,), _sims=None):
         self.spec_ = spec(env_id)
         self.env_id = env_id
-        self.render_mode = None
+        if render_mode not in (None, "rgb_array"):
+            raise ValueError(f"render_mode must be None or 'rgb_array', got {render_mode!r}")
+        self.render_mode = render_mode
+        ids = np.asarray(render_envs)
+        if ids.ndim != 1 or ids.size == 0 or ids.dtype == np.bool_ or not np.issubdtype(ids.dtype, np.integer) \
+                or ids.min() < 0 or ids.max() >= num_envs:
+            raise ValueError(f"render_envs must be a non-empty sequence of env indices in [0, {num_envs}), got {render_envs!r}")
+        self.render_envs = [int(i) for i in ids]
+        self._in_flight = False
         self._sparse = sparse_infos
         if _sims is None:  # product path: HIP only
             import torch
@@ -176,6 +196,7 @@ class BalanceVecEnv(_VecEnvBase):
         self._actions = None
         self._empty = {}
         super().__init__(num_envs, obs_space, act_space)
+        self.render_mode = render_mode  # the fallback base class resets it
 
     # ------------------------------------------------------------------ helpers
     def _to_numpy(self, t):
@@ -206,10 +227,12 @@ class BalanceVecEnv(_VecEnvBase):
         self._ep_ret[:] = 0
         self._ep_len[:] = 0
         self.reset_infos = [{} for _ in range(self.num_envs)]
+        self._in_flight = False
         return obs.astype(np.float32, copy=False)
 
     def step_async(self, actions):
         a = np.asarray(actions, dtype=np.float32).reshape(self.num_envs, 2)
+        self._in_flight = True
         self._pending = []
         for s, st, (start, cnt) in zip(self._sims, self._streams, self._ranges):  # enqueue on every device before waiting on any
             if self._torch is None:
@@ -236,6 +259,7 @@ class BalanceVecEnv(_VecEnvBase):
 
     def step_wait(self):
         obs, rew, term, trunc, tob = self._collect()
+        self._in_flight = False
         dones = term | trunc
         self._ep_ret += rew
         self._ep_len += 1
@@ -267,7 +291,7 @@ class BalanceVecEnv(_VecEnvBase):
         return indices
 
     def get_attr(self, attr_name, indices=None):
-        val = {"render_mode": None, "spec": self.spec_, "env_id": self.env_id,
+        val = {"render_mode": self.render_mode, "spec": self.spec_, "env_id": self.env_id,
                "max_episode_steps": self.spec_.max_episode_steps}.get(attr_name, getattr(self, attr_name, None))
         return [val for _ in self._indices(indices)]
 
@@ -280,11 +304,40 @@ class BalanceVecEnv(_VecEnvBase):
     def env_is_wrapped(self, wrapper_class, indices=None):
         return [False for _ in self._indices(indices)]
 
+    def _render_frames(self):
+        """rgb frames [len(render_envs), H, W, 3] u8 of the global indices in render_envs, each rendered by the shard (and
+        on the device and stream) that owns it"""
+        if self._in_flight:
+            raise RuntimeError("render() between step_async() and step_wait(): the step is still in flight")
+        ids = np.asarray(self.render_envs)
+        frames = [None] * len(ids)
+        for s, st, (start, cnt) in zip(self._sims, self._streams, self._ranges):
+            sel = np.flatnonzero((ids >= start) & (ids < start + cnt))
+            if sel.size == 0:
+                continue
+            if self._torch is None:
+                imgs = self._to_numpy(s.render(env_ids=ids[sel] - start))
+            else:
+                with self._on(st):
+                    imgs = s.render(env_ids=ids[sel] - start).cpu().numpy()
+            for k, j in enumerate(sel):
+                frames[j] = imgs[k]
+        return np.stack(frames)
+
     def get_images(self):
-        return [None for _ in range(self.num_envs)]
+        if self.render_mode != "rgb_array":
+            return [None for _ in range(self.num_envs)]
+        out = [None] * self.num_envs
+        for i, f in zip(self.render_envs, self._render_frames()):
+            out[i] = f
+        return out
 
     def render(self, mode=None):
-        return None  # no GL on the GPU box; the reference's viewer overlays are out of scope
+        """render_mode "rgb_array": one H x W x 3 u8 frame, the images of render_envs tiled (default: env 0's image, what
+        the reference's single-env RecordVideo records); render_mode None: None.  Human mode / viewer overlays: not provided"""
+        if self.render_mode != "rgb_array" or mode not in (None, "rgb_array"):
+            return None
+        return tile_images(self._render_frames())
 
 
 class BalanceVectorEnv:
@@ -306,6 +359,7 @@ class BalanceVectorEnv:
         v = self._v
         v.step_async(a)
         obs, rew, term, trunc, tob = v._collect()
+        v._in_flight = False
         tob = np.array(tob, copy=True)
         done = term | trunc
         infos = {}
@@ -315,6 +369,10 @@ class BalanceVectorEnv:
                 final[i] = tob[i]
             infos = {"final_observation": final, "_final_observation": done.copy()}
         return obs, rew, term, trunc, infos
+
+    def render(self):
+        """render_mode "rgb_array": tuple of the H x W x 3 u8 frames of render_envs; otherwise None"""
+        return tuple(self._v._render_frames()) if self._v.render_mode == "rgb_array" else None
 
     def close(self):
         self._v.close()
