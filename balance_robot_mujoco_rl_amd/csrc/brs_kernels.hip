@@ -23,7 +23,9 @@
 #include "../../include/brs.h"
 #if defined(BRS_TIMING)
 __device__ unsigned long long brs_dbg[16];
-__device__ unsigned long long brs_dbg_wave[4096];
+// per-wave record of the last launch, 16 words per wave (waves 0-1023): phase slots 0-11 (brs_core.hpp: BRS_TIC ids), HW_ID,
+// XCC_ID, lanes per cost-class key (8 x u8) and lanes per bucket (8 x u8) of the keys the lane map was built from
+__device__ unsigned long long brs_dbg_wave[16 * 1024];
 #define BRS_TIMING_LANE_WORDS 153
 #endif
 #include "brs_state.hpp"
@@ -56,24 +58,17 @@ template <int VARIANT> __device__ __forceinline__ Params<float> fold_params(cons
 }
 
 // Lane grouping (Env03): after every step the envs are regrouped along the lanes by the cost class of their NEXT step
-// (brs_state.hpp: cost_class).  Bucket order along the lanes:
-//     floor | far A | near (plain) | far B | wheel | floor + wheel
-// "far" lanes (no block<->robot work at all; split by env parity into A and B) are put between the classes: a boundary wave
-// then pays one expensive path, not two.  The step kernel counts its lanes per bucket as it retires (wave-aggregated atomics
-// into 6 counters behind the lane map), brs_group_kernel turns the counts into bucket bases and hands out the slots with
-// wave-aggregated cursors: a few microseconds over 256 workgroups.  (Round 2a: a stable counting sort in ONE workgroup,
-// 95 us = 2 % of the step.)  The order inside a bucket depends on the order the atomics arrive in -- an env's arithmetic does
-// not depend on its lane, so results stay bit-identical (test_determinism_and_shard_invariance).
-constexpr int NBUCKET = 6;
-__device__ __forceinline__ int bucket_of(int key, int e) {
-  const int k = key & 3;
-  if (k == 1) return 0;
-  if (k == 2) return 4;
-  if (k == 3) return 5;
-  return (key & 4) ? ((e & 1) ? 3 : 1) : 2;
-}
+// (brs_state.hpp: cost_class).  The bucket of an env is its cost-class key; brs_state.hpp: lane_slot lays the buckets out
+// along the lanes, every expensive bucket from a wave boundary with far lanes filling its last wave.  The step kernel
+// counts its lanes per bucket as it retires (wave-aggregated atomics into 8 counters behind the lane map), brs_group_kernel
+// ranks the envs inside their buckets with wave-aggregated cursors and turns (bucket, rank, counts) into a slot: a few
+// microseconds over 256 workgroups.  (Round 2a: a stable counting sort in ONE workgroup, 95 us = 2 % of the step.)  The order
+// inside a bucket depends on the order the atomics arrive in -- an env's arithmetic does not depend on its lane, so results
+// stay bit-identical (tests/test_lane_map_gpu.py).
+constexpr int NBUCKET = LM_NBUCKET;
 // counters behind the lane map and the keys: cnt[NBUCKET] (lanes per bucket, filled by the step kernel), cursor[NBUCKET], ticket
-constexpr int GROUP_WORDS = 16;
+constexpr int GROUP_WORDS = 32;
+static_assert(2 * NBUCKET + 1 <= GROUP_WORDS, "bucket counters do not fit");
 template <bool BLK> __device__ __forceinline__ unsigned* group_counters(int* ii, int N) {
   return (unsigned*)(ii + ((size_t)Layout<BLK>::NI + 2) * N);
 }
@@ -102,6 +97,12 @@ __device__ __forceinline__ void step_body(const Params<float>& Prt, const int N,
   Store<float> st = lane_store<BLK>(lds);
 #if defined(BRS_TIMING) && defined(__HIP_DEVICE_COMPILE__)
   if ((threadIdx.x & 63) == 0) for (int k = 0; k < 16; k++) brs_tim_slots()[k] = 0;
+  if constexpr (BLK) {  // the wave's composition at launch: the keys are read before this step overwrites them
+    const int key = ((const uint8_t*)(ii + ((size_t)Layout<BLK>::NI + 1) * N))[idx.get()];
+    unsigned long long ck = 0ull;
+    for (int k = 0; k < 8; k++) ck |= (unsigned long long)__popcll(__ballot(key == k)) << (8 * k);
+    if ((threadIdx.x & 63) == 0) { brs_tim_slots()[14] = ck; brs_tim_slots()[15] = ck; }  // (the buckets are the keys)
+  }
 #endif
   Stream<float> rng;
   float a0, a1;
@@ -116,7 +117,7 @@ __device__ __forceinline__ void step_body(const Params<float>& Prt, const int N,
   const size_t i = idx.get();
   if constexpr (BLK) {
     ((uint8_t*)(ii + ((size_t)Layout<BLK>::NI + 1) * N))[i] = (uint8_t)cls;
-    const int b = bucket_of(cls, (int)i);
+    const int b = cls;
     unsigned* cnt = group_counters<BLK>(ii, N);
 #pragma unroll
     for (int k = 0; k < NBUCKET; k++) {
@@ -129,14 +130,15 @@ __device__ __forceinline__ void step_body(const Params<float>& Prt, const int N,
     for (int k = 0; k < 12; k++) atomicAdd(&brs_dbg[k], brs_tim_slots()[k]);
     atomicMax(&brs_dbg[12], brs_tim_slots()[8]);  // slowest wave of the launch: cycles, trips (load imbalance, 1 wave per SIMD)
     atomicMax(&brs_dbg[13], brs_tim_slots()[9]);
-    // per-wave record of the LAST launch: cycles, trips, HW_ID, XCC_ID (where did the slow waves run?)
+    // per-wave record of the LAST launch: phase cycles, where the wave ran, what it carried (which lanes made it slow?)
     unsigned hw, xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     const unsigned w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (w < 1024) {
-      brs_dbg_wave[4 * w + 0] = brs_tim_slots()[8]; brs_dbg_wave[4 * w + 1] = brs_tim_slots()[9];
-      brs_dbg_wave[4 * w + 2] = hw; brs_dbg_wave[4 * w + 3] = xcc;
+      for (int k = 0; k < 12; k++) brs_dbg_wave[16 * w + k] = brs_tim_slots()[k];
+      brs_dbg_wave[16 * w + 12] = hw; brs_dbg_wave[16 * w + 13] = xcc;
+      brs_dbg_wave[16 * w + 14] = BLK ? brs_tim_slots()[14] : 0ull; brs_dbg_wave[16 * w + 15] = BLK ? brs_tim_slots()[15] : 0ull;
     }
   }
 #endif
@@ -201,18 +203,19 @@ __global__ void __launch_bounds__(256) brs_physics_kernel(const Params<float> P,
 constexpr int GROUP_THREADS = 256, GROUP_ENVS = 1024;  // small workgroups (they have to find room between step-kernel waves
                                                        // when several handles share a GPU), 4 envs per thread
 __global__ void __launch_bounds__(GROUP_THREADS) brs_group_kernel(const int N, const uint8_t* __restrict__ keys, int* __restrict__ perm,
-                                                                  unsigned* __restrict__ ctr) {
+                                                                  unsigned* __restrict__ ctr, const unsigned cap) {
   // ONE slot request per workgroup and bucket: same-address device atomics are the cost of this kernel (one request per
   // wave: 61 us for 65,536 envs; per 1,024 envs: 7 us).  Wave counts -> LDS -> exclusive offsets inside the workgroup
   constexpr int NV = GROUP_ENVS / 64;  // 64-env groups of the workgroup ("virtual waves": 4 passes x 4 waves)
-  __shared__ unsigned wcnt[NV][NBUCKET], woff[NBUCKET];
+  __shared__ unsigned wcnt[NV][NBUCKET], woff[NBUCKET], cnt[NBUCKET];
+  __shared__ LanePlan plan;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int b[GROUP_ENVS / GROUP_THREADS];
   unsigned long long mine[GROUP_ENVS / GROUP_THREADS];
 #pragma unroll
   for (int j = 0; j < GROUP_ENVS / GROUP_THREADS; j++) {
     const int e = blockIdx.x * GROUP_ENVS + j * GROUP_THREADS + threadIdx.x;
-    b[j] = e < N ? bucket_of(keys[e], e) : -1;
+    b[j] = e < N ? (int)keys[e] : -1;
     mine[j] = 0ull;
 #pragma unroll
     for (int k = 0; k < NBUCKET; k++) {
@@ -222,18 +225,23 @@ __global__ void __launch_bounds__(GROUP_THREADS) brs_group_kernel(const int N, c
     }
   }
   __syncthreads();
-  if (threadIdx.x < NBUCKET) {  // thread k: bucket base from the step kernel's counts, this workgroup's share of the cursor
+  if (threadIdx.x < NBUCKET) {  // thread k: the step kernel's count of bucket k, this workgroup's share of the bucket's cursor
     const int k = threadIdx.x;
-    unsigned base = 0, tot = 0;
-    for (int j = 0; j < k; j++) base += ctr[j];
+    unsigned tot = 0;
+    cnt[k] = ctr[k];
     for (int v = 0; v < NV; v++) { const unsigned c = wcnt[v][k]; wcnt[v][k] = tot; tot += c; }  // exclusive over the 64-env groups
-    woff[k] = base + (tot ? atomicAdd(&ctr[NBUCKET + k], tot) : 0u);
+    woff[k] = tot ? atomicAdd(&ctr[NBUCKET + k], tot) : 0u;
   }
+  __syncthreads();
+  if (threadIdx.x == 0) plan = lane_plan(cnt, cap);  // where the buckets go: once per workgroup
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < GROUP_ENVS / GROUP_THREADS; j++) {
     const int e = blockIdx.x * GROUP_ENVS + j * GROUP_THREADS + threadIdx.x;
-    if (b[j] >= 0) perm[woff[b[j]] + wcnt[j * (GROUP_THREADS / 64) + w][b[j]] + (unsigned)__popcll(mine[j] & ((1ull << lane) - 1ull))] = e;
+    if (b[j] >= 0) {
+      const unsigned r = woff[b[j]] + wcnt[j * (GROUP_THREADS / 64) + w][b[j]] + (unsigned)__popcll(mine[j] & ((1ull << lane) - 1ull));
+      perm[lane_slot(plan, cnt, b[j], r)] = e;
+    }
   }
   // the last workgroup to finish clears the counters for the next step (every other one has read them by then)
   __syncthreads();
@@ -261,6 +269,7 @@ struct brs_handle {
   bool folded = false;       // model constants folded at compile time (default timestep): variant-specific step kernel
   bool occ2 = false;         // Env01 family: body capped at 256 registers, two waves per SIMD (default; BRS_ENV01_OCC1=1: off)
   bool grouping = false;     // Env03: regroup lanes by cost class after every step (perm / keys live behind the int state)
+  unsigned wheel_cap = LM_WAVE;  // wheel lanes per wave in the lane map: diluted only if the launch fits one wave per SIMD
   int* perm() const { return ii + ni; }                            // [N] lane slot -> env
   uint8_t* keys() const { return (uint8_t*)(ii + ni + (size_t)N); }  // [N] cost class of every env for its next step
   unsigned* counters() const { return (unsigned*)(ii + ni + 2 * (size_t)N); }  // [GROUP_WORDS] bucket counts, cursors, ticket
@@ -369,6 +378,9 @@ int brs_create(const brs_config* cfg, brs_handle** out) {
     if (hipMemcpy(h->perm(), id.data(), 2 * N * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return bail("brs_create: lane map init failed");
     if (hipMemset(h->counters(), 0, GROUP_WORDS * sizeof(int)) != hipSuccess) return bail("brs_create: counter init failed");
     h->grouping = h->blk && !(cfg->flags & BRS_FLAG_NO_LANE_GROUPING);
+    int cus = 0;  // CDNA: 4 SIMDs per CU.  More waves than SIMDs are back-filled: diluting would only add work
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) return bail("brs_create: CU count query failed");
+    h->wheel_cap = (N + LM_WAVE - 1) / LM_WAVE <= 4 * (size_t)cus ? (unsigned)LM_RARE_CAP : (unsigned)LM_WAVE;
     h->folded = !(cfg->timestep > 0 && cfg->timestep != 2e-5) && !std::getenv("BRS_NO_FOLD");
     h->occ2 = !h->blk && std::getenv("BRS_ENV01_OCC1") == nullptr;
   }
@@ -458,7 +470,7 @@ int brs_step(brs_handle* h, const float* actions_dev, float* obs_dev, float* rew
   BRS_HIP_TRY(h, hipGetLastError());
   if (h->blk) {  // lanes of the NEXT step; without grouping the counts the step kernel left are just cleared
     if (h->grouping) {
-      hipLaunchKernelGGL(brs_group_kernel, dim3((h->N + GROUP_ENVS - 1) / GROUP_ENVS), dim3(GROUP_THREADS), 0, s, h->N, h->keys(), h->perm(), h->counters());
+      hipLaunchKernelGGL(brs_group_kernel, dim3((h->N + GROUP_ENVS - 1) / GROUP_ENVS), dim3(GROUP_THREADS), 0, s, h->N, h->keys(), h->perm(), h->counters(), h->wheel_cap);
       BRS_HIP_TRY(h, hipGetLastError());
     } else
       BRS_HIP_TRY(h, hipMemsetAsync(h->counters(), 0, GROUP_WORDS * sizeof(int), s));
@@ -524,8 +536,8 @@ int64_t brs_step_bytes_per_env(const brs_handle* h) {
 }
 #if defined(BRS_TIMING)
 // diagnostic builds only: read and clear the per-phase cycle sums
-int brs_debug_waves(unsigned long long* out4096) {
-  return hipMemcpyFromSymbol(out4096, HIP_SYMBOL(brs_dbg_wave), 4096 * sizeof(unsigned long long)) == hipSuccess ? BRS_OK : BRS_ERR_HIP;
+int brs_debug_waves(unsigned long long* out16384) {
+  return hipMemcpyFromSymbol(out16384, HIP_SYMBOL(brs_dbg_wave), 16 * 1024 * sizeof(unsigned long long)) == hipSuccess ? BRS_OK : BRS_ERR_HIP;
 }
 int brs_debug_counters(unsigned long long* out16) {
   if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(brs_dbg), 16 * sizeof(unsigned long long)) != hipSuccess) return BRS_ERR_HIP;

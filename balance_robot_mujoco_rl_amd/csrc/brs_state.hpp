@@ -171,6 +171,83 @@ template <typename R, bool BLK> BRS_HD int cost_class(const Params<R>& P, const 
   }
 }
 
+// Lane map (Env03): after every step the envs are regrouped along the lanes by their cost class (brs_kernels.hip:
+// brs_group_kernel).  The bucket of an env is its cost-class key (0-7).  Slot order along the lanes:
+//     expensive buckets, most expensive first (lm_bucket_at), each starting on a wave (64-lane) boundary  |  far lanes left over
+// A bucket's last partial wave is filled with far lanes (key 4: no block<->robot work, they only ride along), so that no wave
+// pays two expensive paths.  With too few far lanes for every gap, the most expensive buckets are filled first and a bucket
+// left unfilled shares its last wave with the next one.  A wheel bucket (key bit 1: the slowest waves) is moreover DILUTED:
+// at most BRS_RARE_CAP of its lanes per wave, the rest of each wave far lanes -- a wave of fewer expensive lanes runs fewer
+// cycles per trip and fewer trips; with too few far lanes for the cap the bucket is spread over as many
+// waves as the far lanes left allow (64 = no dilution).  Pure scheduling: an env's arithmetic does not depend on its lane.
+#ifndef BRS_RARE_CAP
+#define BRS_RARE_CAP 16
+#endif
+enum { LM_NBUCKET = 8, LM_PLAIN = 0, LM_FAR = 4, LM_WAVE = 64, LM_RARE_CAP = BRS_RARE_CAP };
+static_assert(LM_RARE_CAP >= 1 && LM_RARE_CAP <= LM_WAVE, "BRS_RARE_CAP: 1..64 lanes per wave");
+// the expensive buckets in slot order (o = 0 .. LM_NBUCKET - 2), by measured cycles per trip of their waves (profiles/
+// r04_phase_timing*.log): floor+wheel, wheel, floor+wheel far, wheel far, plain, floor, floor far.  Far (4) is the filler.
+BRS_HD constexpr int lm_bucket_at(int o) {
+  return o == 0 ? 3 : o == 1 ? 2 : o == 2 ? 7 : o == 3 ? 6 : o == 4 ? LM_PLAIN : o == 5 ? 1 : 5;
+}
+// Where every bucket goes, from the number of envs per bucket cnt[LM_NBUCKET] (their sum is N).  cap: wheel lanes per wave,
+// LM_RARE_CAP or LM_WAVE (brs_step dilutes only launches of at most one wave per SIMD: with back-filling, the extra work of
+// the diluted waves costs time instead of filling idle SIMDs).  Computed once per workgroup (brs_group_kernel).
+struct LanePlan {
+  unsigned pos[LM_NBUCKET];   // first slot of the bucket's waves
+  unsigned per[LM_NBUCKET];   // lanes of the bucket per wave (LM_WAVE: packed)
+  unsigned nfar[LM_NBUCKET];  // far lanes placed in its waves ...
+  unsigned far0[LM_NBUCKET];  // ... from this far rank on
+  unsigned rest_pos, rest_far0;  // the far lanes left over: first slot, first far rank
+};
+BRS_HD LanePlan lane_plan(const unsigned* cnt, unsigned cap = LM_RARE_CAP) {
+  LanePlan L;
+  unsigned pos = 0, far_left = cnt[LM_FAR], far_used = 0;
+#pragma unroll
+  for (int o = 0; o < LM_NBUCKET - 1; o++) {
+    const int k = lm_bucket_at(o);
+    const unsigned c = cnt[k];
+    unsigned per = (k & 2) ? cap : (unsigned)LM_WAVE;
+    unsigned need = 0;
+    if (c > 0) {
+      if (per < LM_WAVE) {  // capped: whole waves from a wave boundary, as many as the cap asks and the far lanes left allow
+        const unsigned nw = min_((c + per - 1) / per, (c + far_left) / LM_WAVE);
+        if (pos % LM_WAVE != 0 || nw <= (c - 1) / LM_WAVE) per = LM_WAVE;  // (no more waves than without the cap)
+        else per = (c + nw - 1) / nw;
+        need = (c + per - 1) / per * LM_WAVE - c;
+      }
+      if (per == LM_WAVE) {  // fill the last partial wave up to the next boundary, or not at all
+        need = (LM_WAVE - (pos + c) % LM_WAVE) % LM_WAVE;
+        if (need > far_left) need = 0;
+      }
+    }
+    L.pos[k] = pos; L.per[k] = per; L.nfar[k] = need; L.far0[k] = far_used;
+    pos += c + need; far_used += need; far_left -= need;
+  }
+  L.pos[LM_FAR] = 0; L.per[LM_FAR] = LM_WAVE; L.nfar[LM_FAR] = 0; L.far0[LM_FAR] = 0;
+  L.rest_pos = pos; L.rest_far0 = far_used;
+  return L;
+}
+// lane slot of the r-th env (0-based) of bucket b: a permutation of [0, N) for any counts (tests/test_lane_map_cpu.py)
+BRS_HD unsigned lane_slot(const LanePlan& L, const unsigned* cnt, int b, unsigned r) {
+  if (b != LM_FAR) {
+    const unsigned per = L.per[b];
+    return per == LM_WAVE ? L.pos[b] + r : L.pos[b] + LM_WAVE * (r / per) + r % per;
+  }
+#pragma unroll
+  for (int k = 0; k < LM_NBUCKET; k++) {
+    if (k == LM_FAR || r - L.far0[k] >= L.nfar[k]) continue;  // (unsigned: also r < far0)
+    const unsigned j = r - L.far0[k], per = L.per[k], c = cnt[k];
+    if (per == LM_WAVE) return L.pos[k] + c + j;
+    const unsigned f = LM_WAVE - per, nw = (c + per - 1) / per, full = (nw - 1) * f;  // far lanes of the full waves
+    return j < full ? L.pos[k] + LM_WAVE * (j / f) + per + j % f : L.pos[k] + LM_WAVE * (nw - 1) + (c - (nw - 1) * per) + (j - full);
+  }
+  return L.rest_pos + (r - L.rest_far0);  // far lanes left over
+}
+BRS_HD unsigned lane_slot(int b, unsigned r, const unsigned* cnt, unsigned cap = LM_RARE_CAP) {
+  return lane_slot(lane_plan(cnt, cap), cnt, b, r);
+}
+
 // One full env step working from / to the SoA state in memory (the HIP step kernel's body; the host test build runs
 // the same function).  Register diet for the 250-substep loop: the accessor pose of the LAST forward pass is written
 // straight to its HBM slot when the last substep starts and read back afterwards, and the env-level scalars are only
