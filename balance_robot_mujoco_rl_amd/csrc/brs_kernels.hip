@@ -384,7 +384,7 @@ int brs_create(const brs_config* cfg, brs_handle** out) {
     h->folded = !(cfg->timestep > 0 && cfg->timestep != 2e-5) && !std::getenv("BRS_NO_FOLD");
     h->occ2 = !h->blk && std::getenv("BRS_ENV01_OCC1") == nullptr;
   }
-  // dynamic LDS above the 64 KiB default needs the attribute (Env03, 256-thread blocks: 144 KiB)
+  // dynamic LDS above the 64 KiB default needs the attribute (Env03, 256-thread blocks: 256 x 160 words = 160 KiB, all of a CU's LDS)
   size_t lb = lds_bytes(h);
   hipError_t ea = hipSuccess;
   auto want = [&](const void* fn) { if (ea == hipSuccess) ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb); };

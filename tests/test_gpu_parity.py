@@ -178,11 +178,12 @@ def test_config3_under_the_reference_balancing_policy():
     assert g.n["up"] > 0.95 * 1024 * 150, "under the policy the robots stay upright"
 
 
-def _constructed(env_id, qpos, qvel, ctrl, nsub):
-    """constructed states on the HIP path: set_state -> brs_physics(nsub) against the oracle; relative velocity error per env"""
+def _constructed(env_id, qpos, qvel, ctrl, nsub, **kw):
+    """constructed states on the HIP path: set_state -> brs_physics(nsub) against the oracle; relative velocity error per env.
+    kw: more BatchedSim arguments (e.g. block_threads)"""
     from tests import constructed_states as cs
     n = len(qpos)
-    torch, sim, orc = _mk(env_id, n, seed=0, auto_reset=False, obs_noise=False)
+    torch, sim, orc = _mk(env_id, n, seed=0, auto_reset=False, obs_noise=False, **kw)
     orc.set_state(qpos, qvel); sim.set_state(qpos, qvel)
     orc.physics(ctrl, nsub); sim.physics(ctrl.astype(np.float32), nsub)
     (qo, vo, _, _), (qg, vg, _, _) = orc.get_state(), sim.get_state()
@@ -197,8 +198,11 @@ def test_constructed_block_robot_contact_states_on_the_hip_path():
     states of tests/test_hostsim_parity.py::test_constructed_block_robot_contact_states, 5 substeps via brs_physics"""
     from tests import constructed_states as cs
     qpos, qvel = cs.block_robot_states()
-    err, vo = _constructed("Env03-v2", qpos, qvel, np.zeros((len(qpos), 2)), 5)
-    assert (np.abs(vo[:, :6]).max(axis=1) > 1e-6).sum() > len(qpos) // 3, "a coupled contact acted on the robot"
+    _block_robot_caps(*_constructed("Env03-v2", qpos, qvel, np.zeros((len(qpos), 2)), 5))
+
+
+def _block_robot_caps(err, vo):
+    assert (np.abs(vo[:, :6]).max(axis=1) > 1e-6).sum() > len(vo) // 3, "a coupled contact acted on the robot"
     print(f"block<->robot constructed states on HIP: rel. velocity error q98 {np.quantile(err, 0.98):.3g}, max {err.max():.3g}")
     # measured 2.8e-7 / 3.1e-7 (deterministic arithmetic).  The cap on the maximum sits BELOW the 7.0e-7 the first version of the
     # patch-frame algebra reached (relative twist taken at the torso origin: the block's point acceleration as a difference of two
@@ -210,7 +214,10 @@ def test_constructed_edge_edge_states_on_the_hip_path():
     """one-point edge-edge patches between 0.5 mm outside and 1.5 mm inside the margin: existence decided from the fp64 poses"""
     from tests import constructed_states as cs
     qpos, qvel = cs.edge_edge_states()
-    err, vo = _constructed("Env03-v2", qpos, qvel, np.zeros((len(qpos), 2)), 5)
+    _edge_edge_caps(*_constructed("Env03-v2", qpos, qvel, np.zeros((len(qpos), 2)), 5))
+
+
+def _edge_edge_caps(err, vo):
     print(f"edge-edge constructed states on HIP: rel. velocity error q95 {np.quantile(err, 0.95):.3g}, max {err.max():.3g}")
     assert np.quantile(err, 0.95) < 2e-6 and err.max() < 5e-6, (np.quantile(err, 0.95), err.max())   # measured 1.1e-7 / 1.5e-7: a point
     # existing on one side only would show as ~1e-2
@@ -220,8 +227,14 @@ def test_constructed_floor_contact_states_on_the_hip_path():
     """robot pressed into the floor in every orientation (wheel rim / side / triangle points, torso corners, up to 8 slots)"""
     from tests import constructed_states as cs
     qpos, qvel = cs.floor_states()
-    ctrl = np.random.default_rng(5).uniform(-30, 30, size=(len(qpos), 2)).astype(np.float32).astype(np.float64)
-    err, vo = _constructed("Env01-v2", qpos, qvel, ctrl, 5)
+    _floor_caps(*_constructed("Env01-v2", qpos, qvel, _floor_ctrl(len(qpos)), 5))
+
+
+def _floor_ctrl(n):
+    return np.random.default_rng(5).uniform(-30, 30, size=(n, 2)).astype(np.float32).astype(np.float64)
+
+
+def _floor_caps(err, vo):
     print(f"floor constructed states on HIP: rel. velocity error q98 {np.quantile(err, 0.98):.3g}, max {err.max():.3g}")
     assert np.quantile(err, 0.98) < 5e-7 and err.max() < 1e-6, (np.quantile(err, 0.98), err.max())   # measured 2.8e-8 / 3.8e-8
 
@@ -278,8 +291,15 @@ def test_config4_per_node_total_on_one_gpu():
 def test_env_step_parity_with_shared_rng(env_id):
     """full env step (reward, obs with noise, termination, block state machine, time limit, auto-reset) against the
     oracle, teacher-forced, with the SAME Philox streams on both sides"""
-    n, steps = 256, 40
-    torch, sim, orc = _mk(env_id, n, seed=11, auto_reset=True, max_episode_steps=25)
+    _shared_rng_parity(env_id, 256, 40)
+
+
+def _shared_rng_parity(env_id, n, steps, **kw):
+    """the assertions of test_env_step_parity_with_shared_rng; kw: more BatchedSim arguments (e.g. block_threads).
+    -> (Gates of the qpos of the env-steps whose discrete outcomes agree and did not end an episode, step kernel name)"""
+    torch, sim, orc = _mk(env_id, n, seed=11, auto_reset=True, max_episode_steps=25, **kw)
+    kernel = sim.step_kernel_name()
+    g = Gates()
     og = sim.reset().cpu().numpy().copy()
     oo = orc.reset()
     np.testing.assert_allclose(og, oo, atol=2e-5, rtol=1e-5)
@@ -314,11 +334,14 @@ def test_env_step_parity_with_shared_rng(env_id):
         tim_g, tim_o = ag[ok2][:, 1], ao[ok2][:, 1]
         assert np.array_equal(tim_g[~np.isnan(tim_g)], tim_o[~np.isnan(tim_o)])
         n_done += int((te_o | tr_o).sum())
+        g.add(qpos, sim.get_state()[0], orc.get_state()[0], skip=~ok2 | te_g.astype(bool) | tr_g.astype(bool) | te_o | tr_o)
+    sim.close(); orc.close()
     assert n_done > 0, "the test must exercise auto-reset"
     # discrete outcomes decided within rounding of a threshold (|pitch| vs 50 degrees; block speed vs 0.1 m/s) may differ in
     # fp32: at most 2 of the n * steps = 10,240 env-steps each (measured: see profiles/r02_gpu_tests.log)
     print(f"{env_id}: termination disagreements {n_term_disagree}, block-timer disagreements {n_timer_disagree} of {n * steps}")
     assert n_term_disagree <= 2 and n_timer_disagree <= 2
+    return g, kernel
 
 
 def test_determinism_and_shard_invariance():
@@ -566,9 +589,14 @@ def test_runtime_parameter_kernel_with_non_default_timestep(env_id):
     """brs_config.timestep / .substeps other than the reference's 2e-5 s x 250: the handle runs the kernel whose model
     constants are kernel ARGUMENTS (the per-id kernels fold the default ones at compile time).  Same gates vs the oracle
     created with the same settings (100 substeps of 5e-5 s = the same 5 ms env step)"""
-    n, steps = 256, 60
-    torch, sim, orc = _mk(env_id, n, seed=2, auto_reset=True, obs_noise=False, substeps=100, timestep=5e-5)
-    assert "-1>" in sim.step_kernel_name(), sim.step_kernel_name()
+    _runtime_parameter_parity(env_id, 256, 60)
+
+
+def _runtime_parameter_parity(env_id, n, steps, **kw):
+    """the assertions of test_runtime_parameter_kernel_with_non_default_timestep; kw: more BatchedSim arguments -> step kernel name"""
+    torch, sim, orc = _mk(env_id, n, seed=2, auto_reset=True, obs_noise=False, substeps=100, timestep=5e-5, **kw)
+    kernel = sim.step_kernel_name()
+    assert "-1>" in kernel, kernel
     sim.reset(); orc.reset()
     rng = np.random.default_rng(7)
     g = Gates()
@@ -582,8 +610,9 @@ def test_runtime_parameter_kernel_with_non_default_timestep(env_id):
         skip |= np.isnan(sim.get_aux()[:, 1]) != np.isnan(orc.get_aux()[:, 1])
         g.add(qpos, sim.get_state()[0], orc.get_state()[0], skip)
         assert np.array_equal(sim.get_state()[3][~skip], orc.get_state()[3][~skip]), "time = 100 fp64 additions of 5e-5"
-    g.check(env_id + " (5e-5 s x 100)")
+    g.check(f"{env_id} (5e-5 s x 100, {kernel})")
     sim.close(); orc.close()
+    return kernel
 
 
 def test_folded_and_runtime_constant_kernels_agree(monkeypatch):

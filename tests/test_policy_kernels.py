@@ -8,18 +8,20 @@ import numpy as np
 import pytest
 
 
-def _ref_gae(rew, val, start, last_val, last_done, gamma, lam):
-    """SB3 RolloutBuffer.compute_returns_and_advantage, float32 like SB3's buffers"""
+def _ref_gae(rew, val, start, last_val, last_done, gamma, lam, dtype=np.float32):
+    """SB3 RolloutBuffer.compute_returns_and_advantage, float32 like SB3's buffers (dtype=np.float64: the same recursion on
+    the same inputs in fp64)"""
     T, N = rew.shape
-    adv = np.zeros((T, N), np.float32)
-    last = np.zeros(N, np.float32)
+    rew, val, last_val = rew.astype(dtype), val.astype(dtype), last_val.astype(dtype)
+    adv = np.zeros((T, N), dtype)
+    last = np.zeros(N, dtype)
     for t in reversed(range(T)):
         if t == T - 1:
-            nnt, nv = 1.0 - last_done.astype(np.float32), last_val
+            nnt, nv = 1.0 - last_done.astype(dtype), last_val
         else:
-            nnt, nv = 1.0 - start[t + 1].astype(np.float32), val[t + 1]
-        delta = rew[t] + np.float32(gamma) * nv * nnt - val[t]
-        last = delta + np.float32(gamma) * np.float32(lam) * nnt * last
+            nnt, nv = 1.0 - start[t + 1].astype(dtype), val[t + 1]
+        delta = rew[t] + dtype(gamma) * nv * nnt - val[t]
+        last = delta + dtype(gamma) * dtype(lam) * nnt * last
         adv[t] = last
     return adv, adv + val
 
