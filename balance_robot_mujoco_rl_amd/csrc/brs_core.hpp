@@ -158,6 +158,12 @@ BRS_HD void sincos_(float x, float* s, float* c) { *s = sinf(x); *c = cosf(x); }
 BRS_HD void sincos_(double x, double* s, double* c) { *s = sin(x); *c = cos(x); }
 BRS_HD bool isbad_(float x) { union { float f; uint32_t u; } c; c.f = x; return (c.u & 0x7fffffffu) >= 0x7f800000u; }  // NaN or Inf
 BRS_HD bool isbad_(double x) { union { double f; uint64_t u; } c; c.f = x; return (c.u & 0x7fffffffffffffffull) >= 0x7ff0000000000000ull; }
+BRS_HD bool isnan_(float x) { union { float f; uint32_t u; } c; c.f = x; return (c.u & 0x7fffffffu) > 0x7f800000u; }
+// MuJoCo's mju_isBad: NaN or |x| > 1e10 (mjMAXVAL).  Positive IEEE numbers order like their bit patterns, with Inf and every
+// NaN above all finite ones: ONE unsigned compare against the bits of 1e10 (exact in fp32 and fp64) covers NaN, Inf and the
+// range, and -ffinite-math-only (which folds x != x and may assume that a float compare never meets a NaN) cannot touch it.
+BRS_HD bool isbadnum_(float x) { union { float f; uint32_t u; } c; c.f = x; return (c.u & 0x7fffffffu) > 0x501502f9u; }
+BRS_HD bool isbadnum_(double x) { union { double f; uint64_t u; } c; c.f = x; return (c.u & 0x7fffffffffffffffull) > 0x4202a05f20000000ull; }
 template <typename R> BRS_HD R max_(R a, R b) { return a > b ? a : b; }
 template <typename R> BRS_HD R min_(R a, R b) { return a < b ? a : b; }
 
@@ -290,6 +296,7 @@ BRS_HD int sel_robot(uint32_t sels, int c) { return (int)((sels >> (2 * c)) & 3u
 BRS_HD int sel_wheel_contact(uint32_t sels) { return (int)((sels >> 16) & 3u); }  // 0: no block<->wheel contact, 1 L, 2 R
 
 // ------------------------------------------------------------------------------------ env state (registers)
+constexpr int BAD_START_BIT = INT32_MIN;  // stored bad count, sign bit: EnvState::bad_start on its way to env_post
 template <typename R, bool BLK> struct EnvState {
   static constexpr int NV = BLK ? 14 : 8;
   double p[3], q[4], th[2];  // torso position, unit quaternion (w,x,y,z), wheel angles  (fp64 accumulators)
@@ -326,8 +333,10 @@ template <typename R, bool BLK> struct EnvState {
   uint32_t rng_ctr;
   int side_front;
   R ep_return;
-  int bad;
-  R muw;            // Env02: wheel/floor friction of this episode (envs/env02_v1.py:57-65)
+  int bad;          // guard resets so far (aux column 7)
+  bool bad_start;   // this step starts from a bad state or a NaN action (consumed by env_post); stored as the sign bit of the bad
+                    // count (BAD_START_BIT) by whoever planted the state, and across the substep loop: not in a register
+  R muw;           // Env02: wheel/floor friction of this episode (envs/env02_v1.py:57-65)
   R dts, poff, tws; // Env01-v3: delay_target_speed, pitch_offset, target_wheel_speed (envs/env01_v3.py:16-53)
   int pnfr, pnfb, pnc;  // previous substep: contact-list lengths, body selectors and final active-row masks -- the first
   uint32_t psels, pmR, pmB, pmC;  // guess of this substep's active set (not persisted across launches)
@@ -2413,7 +2422,7 @@ template <typename R, bool BLK> struct Sim {
     S.ww[0] = S.ww[1] = 0;
 #pragma unroll
     for (int i = 0; i < NV; i++) S.a[i] = 0;
-    S.time = 0; S.elapsed = 0; S.ep_return = 0;
+    S.time = 0; S.elapsed = 0; S.ep_return = 0; S.bad_start = false;
     R xr = (rng.next() - (R)0.5) * TWO_PI, yr = (rng.next() - (R)0.5) * P.Sy, zr = (rng.next() - (R)0.5) * P.Sz;
     euler_slot_quat(xr, yr, zr, S.q);
     if (P.per_env_mu) S.muw = rng.next() / (R)2 + (R)0.5;  // envs/env02_v1.py:61-65, after the pose draws
@@ -2432,8 +2441,45 @@ template <typename R, bool BLK> struct Sim {
     get_obs(P, S, rng, true, obs);
   }
 
+  // ---- the bad-state guard: mj_checkPos / mj_checkVel over EVERY stored coordinate (NaN, Inf, |x| > 1e10); the velocities as they are stored
+  static BRS_HD bool state_bad(const ES& S) {
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < 3; k++) bad |= isbadnum_(S.p[k]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) bad |= isbadnum_(S.q[k]);
+    bad |= isbadnum_(S.th[0]) | isbadnum_(S.th[1]);
+#if BRS_VEL64
+#pragma unroll
+    for (int k = 0; k < 3; k++) bad |= isbadnum_(S.vd[k]) | isbadnum_(S.wd[k]);
+    bad |= isbadnum_(S.wwd[0]) | isbadnum_(S.wwd[1]);
+#else
+#pragma unroll
+    for (int k = 0; k < 3; k++) bad |= isbadnum_(S.v[k]) | isbadnum_(S.w[k]);
+    bad |= isbadnum_(S.ww[0]) | isbadnum_(S.ww[1]);
+#endif
+    if constexpr (BLK) {
+#pragma unroll
+      for (int k = 0; k < 3; k++) bad |= isbadnum_(S.bp[k]);
+#pragma unroll
+      for (int k = 0; k < 4; k++) bad |= isbadnum_(S.bq[k]);
+#if BRS_VEL64
+#pragma unroll
+      for (int k = 0; k < 3; k++) bad |= isbadnum_(S.bvd[k]) | isbadnum_(S.bwd[k]);
+#else
+#pragma unroll
+      for (int k = 0; k < 3; k++) bad |= isbadnum_(S.bv[k]) | isbadnum_(S.bw[k]);
+#endif
+    }
+    return bad;
+  }
+  // a lane that STARTS bad, or is handed a NaN action (Inf and huge ones are clamped by the servo), is reset by env_post
+  // (EnvState::bad_start); its substeps run on garbage in between
+  static BRS_HD bool start_bad(const ES& S, float a0, float a1) { return state_bad(S) | isnan_(a0) | isnan_(a1); }
   // ---- one full env step = env_pre (reward + control law on the PRE-step state) -> nsub substeps -> env_post
   static BRS_HD R env_pre(const Params<R>& P, ES& S, Stream<R>& rng, float a0, float a1, CT& ctrlL, CT& ctrlR) {
+    // a bad friction coefficient (Env02; only set_aux can plant one) is no bad STATE: the model's own value takes its place
+    if (P.per_env_mu && isbadnum_(S.muw)) S.muw = P.cc[CC_WHEEL_FLOOR].mu;
     if (P.v3) {  // envs/env01_v3.py:28-36: schedule keyed on data.time at the start of step
       const double t = S.time;  // fp64 like the reference: the accumulated time sits within rounding of the thresholds
       if (t > 5.5) S.tws = (R)3 * S.dts;
@@ -2453,15 +2499,16 @@ template <typename R, bool BLK> struct Sim {
   }
   static BRS_HD void env_post(const Params<R>& P, ES& S, Stream<R>& rng, R rew, float* obs, float* terminal_obs, float& reward,
                               int& terminated, int& truncated) {
-    // mj_check*: NaN / runaway -> reset the simulation (counted)
-    bool bad = isbad_(S.p[0]) || isbad_(S.p[2]) || isbad_(S.q[0]) || isbad_(S.v[0]) || isbad_(S.v[2]) || isbad_(S.w[0]) ||
-               isbad_(S.ww[0]) || isbad_(S.ww[1]) || abs_(S.v[0]) > (R)1e10 || abs_(S.v[2]) > (R)1e10;
-    if constexpr (BLK) bad = bad || isbad_(S.bp[0]) || isbad_(S.bp[2]) || isbad_(S.bq[0]) || isbad_(S.bv[0]) || isbad_(S.bw[0]);
+    // mj_check*: NaN / runaway at the start of the step (bad_start) or at its end -> reset the simulation (counted).  A reward
+    // that the bad pre-step state made non-finite is dropped: the learner never sees a NaN
+    const bool bad = S.bad_start | state_bad(S);
+    S.bad_start = false;
     if (bad) {
       float tmp[6];
       S.bad++;
       env_reset(P, S, rng, tmp);
     }
+    rew = (bad & isbad_(rew)) ? (R)0 : rew;
     if constexpr (BLK) {  // envs/env03_v1.py:39-49
       R bv2 = S.bv[0] * S.bv[0] + S.bv[1] * S.bv[1] + S.bv[2] * S.bv[2];
       if (bv2 < (R)0.01 && S.block_timer < 0) {
@@ -2475,6 +2522,7 @@ template <typename R, bool BLK> struct Sim {
     }
     terminated = abs_(get_pitch(P, S, rng)) > (R)(50.0 * 3.14159265358979323846 / 180.0) ? 1 : 0;
     get_obs(P, S, rng, false, obs);
+    if (bad) obs[1] = 0;  // after a guard reset this is the new episode's first observation: no pitch rate across the reset
     S.elapsed++;
     S.ep_return += rew;
     truncated = S.elapsed >= P.max_episode_steps ? 1 : 0;
@@ -2486,6 +2534,7 @@ template <typename R, bool BLK> struct Sim {
   static BRS_HD void env_step(const Params<R>& P, Store<R>& st, ES& S, Stream<R>& rng, float a0, float a1, float* obs,
                               float* terminal_obs, float& reward, int& terminated, int& truncated) {
     CT ctrlL, ctrlR;
+    S.bad_start = start_bad(S, a0, a1);
     R rew = env_pre(P, S, rng, a0, a1, ctrlL, ctrlR);
     for (int k = 0; k < P.nsub; k++) {
       if (k == P.nsub - 1) {  // accessor pose = kinematics of the LAST forward pass (lags qpos by one substep)

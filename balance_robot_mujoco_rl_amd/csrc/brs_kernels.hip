@@ -110,6 +110,7 @@ __device__ __forceinline__ void step_body(const Params<float>& Prt, const int N,
     const size_t i = idx.get();
     rng.open(P.seed, P.gid_base + (int64_t)i, 0u);
     a0 = actions[2 * i]; a1 = actions[2 * i + 1];
+    if (isnan_(a0) | isnan_(a1)) ii[(size_t)Layout<BLK>::I_BAD * N + i] |= BAD_START_BIT;
   }
   float o[6], to[6], rew;
   int te, tr, cls = 0;
@@ -508,8 +509,10 @@ int brs_get_state(brs_handle* h, double* qpos, double* qvel, double* warm, doubl
                       hostconv::get_state<false>(d.data(), f.data(), N, qpos, qvel, warm, time), false);
 }
 int brs_set_state(brs_handle* h, const double* qpos, const double* qvel, const double* warm, const double* time) {
-  BRS_STATE_ROUNDTRIP(h, hostconv::set_state<true>(d.data(), f.data(), N, qpos, qvel, warm, time),
-                      hostconv::set_state<false>(d.data(), f.data(), N, qpos, qvel, warm, time), true);
+  BRS_STATE_ROUNDTRIP(h, (hostconv::set_state<true>(d.data(), f.data(), N, qpos, qvel, warm, time),
+                          hostconv::mark_bad_start<true>(d.data(), f.data(), ii.data(), N)),
+                      (hostconv::set_state<false>(d.data(), f.data(), N, qpos, qvel, warm, time),
+                       hostconv::mark_bad_start<false>(d.data(), f.data(), ii.data(), N)), true);
 }
 int brs_get_aux(brs_handle* h, double* aux) {
   if (!aux) return BRS_ERR_ARG;

@@ -79,7 +79,7 @@ BRS_HD void load_state_env(EnvState<R, BLK>& S, const double* d, const FT* f, co
   S.ep_return = (R)f[L::F_EPRET * N + i];
   if constexpr (BLK) S.block_timer = d[L::D_TIMER * N + i]; else S.block_timer = -1.0;
   S.elapsed = ii[L::I_ELAPSED * N + i];
-  S.bad = ii[L::I_BAD * N + i];
+  { const int b = ii[L::I_BAD * N + i]; S.bad = b & ~BAD_START_BIT; S.bad_start = b < 0; }
   S.dts = (R)f[L::F_DTS * N + i]; S.poff = (R)f[L::F_POFF * N + i]; S.tws = (R)f[L::F_TWS * N + i];
 }
 template <typename R, bool BLK, typename FT>
@@ -128,7 +128,31 @@ BRS_HD void store_state(const EnvState<R, BLK>& S, double* d, FT* f, int* ii, si
   ii[L::I_ELAPSED * N + i] = S.elapsed;
   ii[L::I_RNG * N + i] = (int)S.rng_ctr;
   ii[L::I_SIDE * N + i] = S.side_front;
-  ii[L::I_BAD * N + i] = S.bad;
+  ii[L::I_BAD * N + i] = S.bad | (S.bad_start ? BAD_START_BIT : 0);  // (set only between env_pre and env_post)
+}
+
+// Sim::state_bad on the state in memory: NaN, Inf or |x| > 1e10 in any stored coordinate of qpos or qvel
+template <bool BLK, typename FT> BRS_HD bool stored_state_bad(const double* d, const FT* f, size_t N, size_t i) {
+  using L = Layout<BLK>;
+  bool bad = false;
+#pragma unroll
+  for (int k = L::D_P; k < L::D_TH + 2; k++) bad |= isbadnum_(d[k * N + i]);  // p, q, th
+  if constexpr (BLK) {
+#pragma unroll
+    for (int k = L::D_BP; k < L::D_BQ + 4; k++) bad |= isbadnum_(d[k * N + i]);  // bp, bq
+  }
+#if BRS_VEL64
+#pragma unroll
+  for (int k = 0; k < L::NV; k++) bad |= isbadnum_(d[(L::D_V + k) * N + i]);
+#else
+#pragma unroll
+  for (int k = L::F_V; k < L::F_WW + 2; k++) bad |= isbadnum_(f[k * N + i]);
+  if constexpr (BLK) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) bad |= isbadnum_(f[(L::F_BV + k) * N + i]) | isbadnum_(f[(L::F_BW + k) * N + i]);
+  }
+#endif
+  return bad;
 }
 
 // Cost class of an env for its NEXT step (Env03): which of the rare, expensive collision paths it is likely to walk.
@@ -283,6 +307,11 @@ BRS_HD void env_step_idx(const Params<R>& P, Store<R>& st, Stream<R>& rng, doubl
   R rew;
   {
     const size_t i = idx.get();
+    // The verdict on what the step starts from reaches env_post through memory like the env scalars (BAD_START_BIT in the stored
+    // bad count; load_state_env reads it back after the loop): a flag held across the loop would cost a register.  The STATE a
+    // step starts from was either left by a step (env_post checked it) or planted by brs_set_state / brs_physics, which set the
+    // bit themselves (mark_bad_start, physics_mem); a NaN ACTION is added to it by whoever reads the actions (the step kernel,
+    // the host build's step)
     load_state_phys<R, BLK, FT>(S, d, f, ii, N, i);
     load_state_env<R, BLK, FT>(S, d, f, ii, N, i);  // re-loaded after the loop: not live across it
     rng.ctr = S.rng_ctr;
@@ -373,6 +402,7 @@ BRS_HD void physics_mem(const Params<R>& P, Store<R>& st, double* d, FT* f, int*
     }
   }
   S.derive_vel32();
+  S.bad_start = SimT::state_bad(S);  // no env_post here: the next env step resets such a lane
   store_state<R, BLK, FT>(S, d, f, ii, N, i);
 }
 
@@ -457,6 +487,13 @@ inline void set_state(double* d, FT* f, size_t N, const double* qpos, const doub
     if (time) d[L::D_TIME * N + i] = time[i];
   }
 }
+// The bad-state guard's verdict on the state as it is now stored: whoever plants a state (brs_set_state) calls
+// this after set_state, and the next env step resets the lanes marked here.
+template <bool BLK, typename FT> inline void mark_bad_start(const double* d, const FT* f, int* ii, size_t N) {
+  using L = Layout<BLK>;
+  for (size_t i = 0; i < N; i++)
+    ii[L::I_BAD * N + i] = (ii[L::I_BAD * N + i] & ~BAD_START_BIT) | (stored_state_bad<BLK, FT>(d, f, N, i) ? BAD_START_BIT : 0);
+}
 
 template <bool BLK, typename FT>
 inline void get_state(const double* d, const FT* f, size_t N, double* qpos, double* qvel, double* warm, double* time) {
@@ -516,7 +553,7 @@ template <bool BLK, typename FT> inline void get_aux(const double* d, const FT* 
     for (int k = 0; k < 4; k++) xq[k] = d[(L::D_XQ + k) * N + i];
     double p, y;
     Sim<double, BLK>::pitch_yaw(xq, p, y);
-    a[5] = p; a[6] = f[L::F_EPRET * N + i]; a[7] = ii[L::I_BAD * N + i]; a[8] = a[9] = 0;
+    a[5] = p; a[6] = f[L::F_EPRET * N + i]; a[7] = ii[L::I_BAD * N + i] & ~BAD_START_BIT; a[8] = a[9] = 0;
     a[10] = f[L::F_MUW * N + i]; a[11] = f[L::F_DTS * N + i]; a[12] = f[L::F_POFF * N + i]; a[13] = f[L::F_TWS * N + i];
   }
 }

@@ -749,7 +749,7 @@ static void box_cyl(const model_t* m, const double* wpos, const double* tmat, in
 static int collide(const model_t* m, const kin_t* k, bo_contact* con, double muw) {
   int n = 0;
   cparam cpw = m->cp_wheel_floor;
-  if (muw > 0) cpw.mu = muw; /* max(floor, wheel) friction, both set to the episode's value */
+  if (muw > 0 && muw <= 1e10) cpw.mu = muw; /* max(floor, wheel) friction, both set to the episode's value (a bad one: the model's) */
   double gpos[3], t[3], gmat[9];
   /* floor <-> wheels (Env01: explicit <pair>, envs/env01_v1.xml:30-33; Env03: geom defaults) */
   for (int w = 0; w < 2; w++) {
@@ -1051,6 +1051,11 @@ static int bad_number(double x) { return !(x == x) || x > 1e10 || x < -1e10; }
 /* one mj_step: forward at (qpos,qvel) then semi-implicit advance; returns 0, or 1 if the state went bad */
 static int substep(const model_t* m, env_t* e, const double* ctrl, fwd_t* f) {
   int nv = m->nv;
+  /* mj_checkPos / mj_checkVel at the head of mj_step */
+  for (int j = 0; j < m->nq; j++)
+    if (bad_number(e->qpos[j])) return 1;
+  for (int j = 0; j < nv; j++)
+    if (bad_number(e->qvel[j])) return 1;
   forward(m, e->qpos, e->qvel, ctrl, e->warm, f, m->variant == BO_ENV02_V1 ? e->muw : 0.0);
   memcpy(e->warm, f->qacc, nv * sizeof(double));
   /* accessor pose = kinematics of THIS forward pass (lags the advanced qpos by one substep) */
@@ -1340,6 +1345,7 @@ static void env_step(bo_handle* h, int idx, const float* action, float* obs, flo
     else if (e->time > 1.0) e->tws = e->dts;
   }
   double rew = get_reward(m, e, &s); /* on the PRE-step state (env01_v2.py:29) */
+  int guard = 0; /* the bad-state guard fired in this step */
   double ctrl[2] = {e->qvel[6] + (double)action[0] * 4.0, e->qvel[7] + (double)action[1] * 4.0}; /* :31-36 */
   e->last_ctrl[0] = ctrl[0]; e->last_ctrl[1] = ctrl[1];
   if (e->stub) {
@@ -1356,6 +1362,8 @@ static void env_step(bo_handle* h, int idx, const float* action, float* obs, flo
         float tmp[6];
         e->bad_count++;
         env_reset(h, idx, tmp);
+        if (!isfinite(rew)) rew = 0; /* deliberate deviation: a reward the bad pre-step state made non-finite is dropped */
+        guard = 1;
         break;
       }
   }
@@ -1371,7 +1379,7 @@ static void env_step(bo_handle* h, int idx, const float* action, float* obs, flo
     }
   }
   int term = fabs(get_pitch(m, e, &s)) > (50 * PI / 180); /* env01_v2.py:44 */
-  get_obs(m, e, &s, 0, obs);
+  get_obs(m, e, &s, guard, obs); /* after a guard reset: the new episode's first observation, no pitch rate across the reset */
   e->elapsed++;
   e->ep_return += rew;
   int trunc = e->elapsed >= m->max_episode_steps; /* gymnasium TimeLimit, __init__.py:15,50 */

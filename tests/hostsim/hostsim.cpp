@@ -50,6 +50,7 @@ template <typename R, bool BLK> struct HostSim : IHost {
   int nv() const override { return L::NV; }
   void set_state(const double* qp, const double* qv, const double* wm, const double* tm) override {
     hostconv::set_state<BLK>(d.data(), f.data(), N, qp, qv, wm, tm);
+    hostconv::mark_bad_start<BLK>(d.data(), f.data(), ii.data(), N);
   }
   void get_state(double* qp, double* qv, double* wm, double* tm) const override {
     hostconv::get_state<BLK>(d.data(), f.data(), N, qp, qv, wm, tm);
@@ -93,6 +94,7 @@ template <typename R, bool BLK> struct HostSim : IHost {
       Store<R> st{buf, 1};
       int te, tr;
       float tob[6];
+      if (isnan_(act[2 * i]) | isnan_(act[2 * i + 1])) ii[L::I_BAD * N + i] |= BAD_START_BIT;  // as the step kernel does (brs_kernels.hip: step_body)
       env_step_mem<R, BLK, R>(P, st, rng, d.data(), f.data(), ii.data(), N, i, act[2 * i], act[2 * i + 1], obs + 6 * i, tob, rew[i], te, tr);
       spos[i] = rng.script_pos;
       term[i] = (uint8_t)te; trunc[i] = (uint8_t)tr;

@@ -6,16 +6,25 @@ import subprocess
 import numpy as np
 
 _DIR = os.path.dirname(os.path.abspath(__file__))
-_LIB = os.path.join(_DIR, "libbrs_hostsim.so")
+_TARGET = "libbrs_hostsim.so"
 VARIANTS = {"Env01-v1": 0, "Env01-v2": 1, "Env03-v1": 2, "Env03-v2": 3, "Env01-v3": 4, "Env02-v1": 5}
 _lib = None
+
+
+def use_library(target):
+    """load another build of the host library: a target of the Makefile in this directory (libbrs_hostsim_ubsan.so).
+    Process-wide, before the first use."""
+    global _TARGET
+    if _lib is not None:
+        raise RuntimeError("the host library is already loaded")
+    _TARGET = target
 
 
 def lib():
     global _lib
     if _lib is None:
-        subprocess.check_call(["make", "-C", _DIR, "-s"])
-        L = C.CDLL(_LIB)
+        subprocess.check_call(["make", "-C", _DIR, "-s", _TARGET])
+        L = C.CDLL(os.path.join(_DIR, _TARGET))
         vp, dp, fp, u8p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_uint8)
         L.hs_create.restype = vp
         L.hs_set_threads.argtypes = [C.c_int]
