@@ -74,7 +74,7 @@ def _compile(lib_path, verbose, extra_flags, tag):
                  # for register pressure and leaves serial chains (a dependent VALU instruction issues ~1.7x slower than
                  # an independent one for a lone wave).  The ILP strategy: +4.3 % Env03, +2.7 % Env01 (same-box A/B)
                  "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
-    sim_flags += os.environ.get("BRS_EXTRA_HIPCC_FLAGS", "").split()  # ablation builds (e.g. -DBRS_NO_COUPLED); not for production
+    sim_flags += os.environ.get("BRS_EXTRA_HIPCC_FLAGS", "").split()  # builds with a compile-time switch (e.g. -DBRS_NO_COUPLED); not for production
     sim_flags += extra_flags
     if verbose:
         sim_flags.append("-Rpass-analysis=kernel-resource-usage")

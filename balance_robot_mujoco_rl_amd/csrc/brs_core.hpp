@@ -56,32 +56,8 @@ __device__ __forceinline__ unsigned long long* brs_tim_slots() {  // 16 x u64 pe
 #define BRS_TOC(id) do { } while (0)
 #define BRS_PIN(x) do { } while (0)
 #endif
-#ifndef BRS_MASK_HINT
-#define BRS_MASK_HINT 1
-#endif
 #ifndef BRS_FLIP_TOL
 #define BRS_FLIP_TOL 1e-6
-#endif
-#ifndef BRS_UNDAMPED_ITERS
-#define BRS_UNDAMPED_ITERS 3
-#endif
-// velocities carried as fp64 ACCUMULATORS (like qpos and time): the state enters a step with the caller's fp64 qvel, h * acc is
-// added in fp64 and the fp32 copy the force path reads is re-derived from it every substep
-#ifndef BRS_VEL64
-#define BRS_VEL64 1
-#endif
-// the block<->torso patch in PATCH-FRAME algebra (Sim::Patch below): per point ~60 instructions in a 6-dof twist space shared by
-// all points of the patch, one 6x6 congruence per pass into H -- instead of a rank-3 update of the 12x12 dof block per point
-#ifndef BRS_PATCH_FRAME
-#define BRS_PATCH_FRAME 1
-#endif
-// clip candidates of the box-box patch parked at fixed LDS words and walked by bit scan (1) or rank-scattered (0)
-#ifndef BRS_FIXED_SCATTER
-#define BRS_FIXED_SCATTER 1
-#endif
-// fp32 velocity mirrors re-derived from the fp64 accumulators at the start of each substep (1) or carried across the solver (0)
-#ifndef BRS_LAZY_VEL32
-#define BRS_LAZY_VEL32 BRS_VEL64
 #endif
 // (Tried and not kept, round 3: the robot<->floor contacts in the same frame algebra as the patch -- they all share the world-aligned
 // frame, so they can accumulate one 8x8 matrix in (frame-coordinate twist, two wheel rates) and enter H by one congruence: 840
@@ -260,10 +236,7 @@ template <typename R> struct Stream {
 // at base[k*stride] (GPU: stride 64 = one LDS row per word, consecutive lanes on consecutive banks).  7 coupled slots =
 // PATCH_MAX = 6 patch points + the wheel point: nothing the generator emits is dropped.  160 words/lane = 40 KiB per wave:
 // exactly 4 waves per 160-KiB CU (measured: no loss against 153 words).
-#ifndef BRS_PATCH_MAX
-#define BRS_PATCH_MAX 6  // (A/B builds may set 4: round-2a behaviour)
-#endif
-enum { PATCH_MAX = BRS_PATCH_MAX };
+constexpr int PATCH_MAX = 6;
 #if defined(BRS_TIMING)  // diagnostic build: one robot<->floor slot less makes room for the per-wave timing slots (the bench workload
 enum { BRS_NRS = 7 };    // never has more than 4 robot<->floor contacts)
 #else
@@ -303,24 +276,18 @@ template <typename R, bool BLK> struct EnvState {
   R v[3], w[3], ww[2];       // world-frame linear velocity, BODY-frame angular velocity, wheel rates
   double bp[3], bq[4];       // block pose
   R bv[3], bw[3];            // block: world linear, body angular
-#if BRS_VEL64
   double vd[3], wd[3], wwd[2], bvd[3], bwd[3];  // the fp64 accumulators behind v, w, ww, bv, bw (those are their roundings)
-#endif
   // the fp32 velocities the force path reads ARE the roundings of the fp64 accumulators: re-derived when a substep starts (and once
   // after the loop) instead of being carried across the solver -- 14 registers less at the kernel's register peak, same numbers
   BRS_HD void derive_vel32() {
-#if BRS_VEL64
     for (int i = 0; i < 3; i++) { v[i] = (R)vd[i]; w[i] = (R)wd[i]; }
     ww[0] = (R)wwd[0]; ww[1] = (R)wwd[1];
     if constexpr (BLK) { for (int i = 0; i < 3; i++) { bv[i] = (R)bvd[i]; bw[i] = (R)bwd[i]; } }
-#endif
   }
   BRS_HD void sync_vel64() {  // after code that wrote the fp32 velocities directly (reset, block throw)
-#if BRS_VEL64
     for (int i = 0; i < 3; i++) { vd[i] = (double)v[i]; wd[i] = (double)w[i]; }
     wwd[0] = (double)ww[0]; wwd[1] = (double)ww[1];
     if constexpr (BLK) { for (int i = 0; i < 3; i++) { bvd[i] = (double)bv[i]; bwd[i] = (double)bw[i]; } }
-#endif
   }
   R a[NV];                   // solver variable / warm start, BODY-frame linear coordinates (robot and block)
   double time;
@@ -342,12 +309,9 @@ template <typename R, bool BLK> struct EnvState {
   uint32_t psels, pmR, pmB, pmC;  // guess of this substep's active set (not persisted across launches)
 };
 
-// type of the two servo targets (data.ctrl) held across the substeps of a step: the reference forms ctrl = qvel + 4 a in fp64
-#if BRS_VEL64
+// type of the two servo targets (data.ctrl) held across the substeps of a step: always fp64 (the reference forms ctrl = qvel + 4 a in
+// fp64); the name stays for host harnesses written against it (tests/hostsim)
 template <typename R> using CtrlT = double;
-#else
-template <typename R> using CtrlT = R;
-#endif
 
 template <typename R> BRS_HD R impedance_(const ContactClass<R>& c, R dist) {
   if (c.inv_width == (R)0) return c.d0;
@@ -589,19 +553,12 @@ template <typename R, bool BLK> struct Sim {
     else { vy = 0; vz = -P.wheel_r; }
     R sg = nx > 0 ? (R)-1 : (R)1;  // cylinder axis (body x) flipped to point towards the plane
     R axh = sg * P.wheel_hl;
-#if defined(BRS_FLOOR_DIST32)  // A/B: round-2a behaviour
-    R prjaxis = -abs_(nx) * P.wheel_hl, prjvec = vy * ny + vz * nz;
-    R dist0 = zT + nx * px + nz * pz;
-    const R d1 = dist0 + prjaxis + prjvec, d2 = dist0 - prjaxis + prjvec, dT = dist0 + prjaxis - (R)0.5 * prjvec;
-    const bool in1 = d1 < c.margin, in2 = d2 < c.margin, inT = dT < c.margin;
-#else
     const double prjaxis = -abs_(G.nx) * P.wheel_hl_d, prjvec = -P.wheel_r_d * G.len;  // vy ny + vz nz = -r len
     const double dist0 = G.zT + G.nx * (sel == 1 ? -P.wheel_px_d : P.wheel_px_d) + G.nz * P.wheel_pz_d;
     const double d1d = dist0 + prjaxis + prjvec, d2d = dist0 - prjaxis + prjvec, dTd = dist0 + prjaxis - 0.5 * prjvec;
     const double mg = P.margin_d[CC_WHEEL_FLOOR];
     const bool in1 = d1d < mg, in2 = d2d < mg, inT = dTd < mg;
     const R d1 = (R)d1d, d2 = (R)d2d, dT = (R)dTd;
-#endif
     if (!in1) return;
     if (!triangles) {
       R p1[3] = {px + axh, vy, pz + vz};
@@ -713,12 +670,10 @@ template <typename R, bool BLK> struct Sim {
     fw[3] *= il; fw[4] *= il; fw[5] *= il;
     cross_(fw, fw + 3, fw + 6);
   }
-  // coupled record (10 words): rT(3) torso frame, rB(3) block frame, An, Bt1, Bt2, D; the world normal robot->block of its
-  // patch goes to contact-frame slot `sel` (written by the patch's first point, share = false).
-  // fw = world contact frame (normal + MuJoCo's mju_makeFrame tangents), built once per patch by the caller.
-  static BRS_HD void add_coupled(const Params<R>& P, Store<R>& st, Frame& F, const ES& S, const R* rT, const R* fw, R dist,
-                                 int sel, bool share) {
-    if (sel == 0 && F.nc >= PATCH_MAX) return;
+  // the block<->wheel contact on wheel sel (1 L, 2 R).  Record (10 words, coupled slot PATCH_MAX: the patch loops never meet it):
+  // rT(3) torso frame, rB(3) block frame, An, Bt1, Bt2, D; its world normal robot->block goes to contact-frame slot 1.
+  // fw = world contact frame (normal + MuJoCo's mju_makeFrame tangents), built by the caller.
+  static BRS_HD void add_wheel_contact(const Params<R>& P, Store<R>& st, Frame& F, const ES& S, const R* rT, const R* fw, R dist, int sel) {
     const ContactClass<R>& c = P.cc[CC_BLOCK_ROBOT];
     R pw[3], rB[3], wc[3], t[3];
     mul_(F.RT, rT, pw);
@@ -736,23 +691,22 @@ template <typename R, bool BLK> struct Sim {
     R rel[3] = {S.bv[0] + pBw[0] - S.v[0] - pTw[0], S.bv[1] + pBw[1] - S.v[1] - pTw[1], S.bv[2] + pBw[2] - S.v[2] - pTw[2]};
     R vn = dot_(fw, rel), vt1 = dot_(fw + 3, rel), vt2 = dot_(fw + 6, rel);
     R imp = impedance_(c, dist);
-    R cD = sel == 0 ? c.cD : P.cD_block_wheel;
-    const int k = sel == 0 ? F.nc : PATCH_MAX;  // the wheel contact has its own slot: the patch loops never meet it
+    const R cD = P.cD_block_wheel;
+    const int k = PATCH_MAX;
     st.setc(k, 0, rT[0]); st.setc(k, 1, rT[1]); st.setc(k, 2, rT[2]);
     st.setc(k, 3, rB[0]); st.setc(k, 4, rB[1]); st.setc(k, 5, rB[2]);
     st.setc(k, 6, -c.B * vn - c.K * imp * (dist - c.margin));
     st.setc(k, 7, -c.B * c.mu * vt1);
     st.setc(k, 8, -c.B * c.mu * vt2);
     st.setc(k, 9, imp * rcp_((1 - imp) * cD));
-    if (!share) { const int fs = sel ? 1 : 0; st.setf(fs, 0, fw[0]); st.setf(fs, 1, fw[1]); st.setf(fs, 2, fw[2]); }
+    st.setf(1, 0, fw[0]); st.setf(1, 1, fw[1]); st.setf(1, 2, fw[2]);
     F.sels |= (uint32_t)sel << 16;
-    F.nc += sel == 0 ? 1 : 0;
   }
   static BRS_HD void world_frame(const Frame& F, const R* nTf, R* fw) {  // unit normal in the torso frame -> world contact frame
     mul_(F.RT, nTf, fw);
     make_frame(fw);
   }
-  // ---- patch-frame algebra for the block<->torso patch (BRS_PATCH_FRAME).  All points of a patch share ONE contact frame
+  // ---- patch-frame algebra for the block<->torso patch.  All points of a patch share ONE contact frame
   // (n, t1, t2).  In FRAME coordinates, with c' = the block centre seen from the torso origin and rho = r' - c' the position of a
   // point seen from the BLOCK CENTRE,
   //     acceleration of the block's material point:    aB' + wB' x rho                (aB' = Ph x[8:11], wB' = Ph x[11:14])
@@ -770,7 +724,7 @@ template <typename R, bool BLK> struct Sim {
   // 6 D; words 7-9 of slots 0-2 hold the frame axes in the TORSO frame (Fm rows), of slots 3-5 in the BLOCK frame (Ph rows);
   // contact-frame slot 0 holds c'.
   struct Patch { R Fm[9], Ph[9], c[3], cT[3]; };  // cT: the block centre in the torso frame (patch_begin -> add_patch_point only)
-  static_assert(!BRS_PATCH_FRAME || PATCH_MAX == 6, "the patch frame is parked in words 7-9 of patch slots 0-5");
+  static_assert(PATCH_MAX == 6, "the patch frame is parked in words 7-9 of patch slots 0-5");
   static BRS_HD void patch_load(const Store<R>& st, Patch& Q) {
 #pragma unroll
     for (int k = 0; k < 3; k++)
@@ -977,13 +931,9 @@ template <typename R, bool BLK> struct Sim {
       double bestE64 = 0;
       int axF = 0, axE = -1;
       bool sep = false;
-#if defined(BRS_PATCH_DIST32)
-      const R sat_margin = c.margin;
-#else
       // within a micrometre of the margin the fp32 axis test does not get to say "separated": the candidates' distances,
       // taken from the fp64 poses below, decide (face axes: the deepest vertex distance IS the axis separation)
       const R sat_margin = c.margin + (sizeof(R) == 4 ? (R)1e-6 : (R)0);
-#endif
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         R sp = abs_(cg[k]) - sT[k] - s * (Q[3 * k] + Q[3 * k + 1] + Q[3 * k + 2]);
@@ -1022,7 +972,6 @@ template <typename R, bool BLK> struct Sim {
         }
       }
       bool use_edge = (axE >= 0) & (bestE > bestF + (R)0.05 * abs_(bestF) + (R)1e-5);
-#if !defined(BRS_PATCH_DIST32)
       if (sizeof(R) == 4 && !sep) {
         // a DISCRETE outcome within rounding of a tie (fp32 separations carry ~1e-8 m; band 2e-6 m): two face axes level, the edge
         // axis at its threshold against the face axis, or -- where the edge axis may win -- two edge axes level.  Then all
@@ -1035,15 +984,11 @@ template <typename R, bool BLK> struct Sim {
           use_edge = (d.axE >= 0) & (d.bestE > d.bestF + 0.05 * abs_(d.bestF) + 1e-5);
         }
       }
-#endif
       if (!sep) {
         BRS_MARK("cc_branch");
         if (use_edge) {
           const int i = axE / 3, j = axE - 3 * i;
           const int i1 = i == 2 ? 0 : i + 1, i2 = i == 0 ? 2 : i - 1;
-#if defined(BRS_PATCH_DIST32)
-          const bool edge_in = bestE < c.margin;
-#else
           // the separation along the chosen edge axis L = e_i x b_j once more from the fp64 poses: it is the distance of the
           // patch's only point, and `< margin` decides whether that point exists in this substep (like the face case below;
           // the axis itself is the fp32 choice).  ~90 fp64 operations, only for lanes in the edge case.
@@ -1065,7 +1010,6 @@ template <typename R, bool BLK> struct Sim {
           }
           const bool edge_in = bestE64 < P.margin_d[CC_BLOCK_ROBOT];
           bestE = (R)bestE64;
-#endif
           if (edge_in) {
             R bj[3] = {pick3(j, RTB[0], RTB[1], RTB[2]), pick3(j, RTB[3], RTB[4], RTB[5]), pick3(j, RTB[6], RTB[7], RTB[8])};
             const R bji = pick3(i, bj), bji1 = pick3(i1, bj), bji2 = pick3(i2, bj);
@@ -1098,16 +1042,10 @@ template <typename R, bool BLK> struct Sim {
 #pragma unroll
             for (int m = 0; m < 3; m++) pos[m] = (R)0.5 * (pA[m] + (m == i ? al : (R)0) + pB[m] + be * bj[m]);
             pos[2] += P.torso_cz;
-#if BRS_PATCH_FRAME
             Patch Q;
             R V0[3], W0[3];
             patch_begin(st, F, S, L, Q, V0, W0);
             add_patch_point(P, st, F, Q, V0, W0, pos, bestE);
-#else
-            R fw[9];
-            world_frame(F, L, fw);
-            add_coupled(P, st, F, S, pos, fw, bestE, 0, false);
-#endif
           }
         } else {
           // face case.  Reference frame coordinates (u, v, g): u, v span the reference rectangle |u| <= ra, |v| <= rb, g is
@@ -1115,7 +1053,6 @@ template <typename R, bool BLK> struct Sim {
           // candidate (u, v, g) maps back to the torso geom frame as  pos = u A1 + v A2 + (half + g/2) A3 + A0.
           BRS_MARK("cc_face_setup");
           R Cc[3], H1[3], H2[3], A0[3], A1[3], A2[3], A3[3], nrm[3], ra, rb, half;
-#if !defined(BRS_PATCH_DIST32)
           // The NORMAL components of the incident face (centre and half edges along the reference normal) once more, from
           // the fp64 poses: every candidate's signed distance g is affine in these three numbers, and g < margin decides
           // whether a patch point exists in this substep -- in fp32 its rounding (~1e-8 m) put points of the patch one
@@ -1166,20 +1103,10 @@ template <typename R, bool BLK> struct Sim {
               H12 = -sgB * pick3(a1, sTd) * pick3(a1, bj64); H22 = -sgB * pick3(a2, sTd) * pick3(a2, bj64);
             }
           }
-#endif
           if (axF < 3) {
             const int k = axF, j1 = k == 2 ? 0 : k + 1, j2 = k == 0 ? 2 : k - 1;
-#if defined(BRS_PATCH_DIST32)
-            const R sg = pick3(k, cg) >= 0 ? (R)1 : (R)-1;
-            R rk[3] = {pick3(k, RTB[0], RTB[3], RTB[6]), pick3(k, RTB[1], RTB[4], RTB[7]), pick3(k, RTB[2], RTB[5], RTB[8])};  // row k
-            int js = 0;
-            if (abs_(rk[1]) > abs_(rk[0])) js = 1;
-            if (abs_(rk[2]) > abs_(pick3(js, rk))) js = 2;
-            const R sj = -sg * (pick3(js, rk) >= 0 ? (R)1 : (R)-1);
-#else
             const R sg = (R)fsg, sj = (R)fsj;  // side, incident face and its sign: decided above on the fp64 values
             const int js = fsel;
-#endif
             const int a1 = js == 2 ? 0 : js + 1, a2 = js == 0 ? 2 : js - 1;
             // block axes (torso frame) js, a1, a2 = columns of RTB
             R bs[3] = {pick3(js, RTB[0], RTB[1], RTB[2]), pick3(js, RTB[3], RTB[4], RTB[5]), pick3(js, RTB[6], RTB[7], RTB[8])};
@@ -1201,16 +1128,8 @@ template <typename R, bool BLK> struct Sim {
             R bj[3] = {pick3(j, RTB[0], RTB[1], RTB[2]), pick3(j, RTB[3], RTB[4], RTB[5]), pick3(j, RTB[6], RTB[7], RTB[8])};
             R bi1[3] = {pick3(i1, RTB[0], RTB[1], RTB[2]), pick3(i1, RTB[3], RTB[4], RTB[5]), pick3(i1, RTB[6], RTB[7], RTB[8])};
             R bi2[3] = {pick3(i2, RTB[0], RTB[1], RTB[2]), pick3(i2, RTB[3], RTB[4], RTB[5]), pick3(i2, RTB[6], RTB[7], RTB[8])};
-#if defined(BRS_PATCH_DIST32)
-            const R sgB = dot_(cg, bj) >= 0 ? (R)1 : (R)-1;
-            int ks = 0;
-            if (abs_(bj[1]) > abs_(bj[0])) ks = 1;
-            if (abs_(bj[2]) > abs_(pick3(ks, bj))) ks = 2;
-            const R sk = sgB * (pick3(ks, bj) >= 0 ? (R)1 : (R)-1);
-#else
             const R sgB = (R)fsg, sk = (R)fsj;
             const int ks = fsel;
-#endif
             const int a1 = ks == 2 ? 0 : ks + 1, a2 = ks == 0 ? 2 : ks - 1;
             const R sTs = pick3(ks, sT), sT1 = pick3(a1, sT), sT2 = pick3(a2, sT);
             // incident torso face: centre sk sT[ks] e_ks, half edges sT[a1] e_a1, sT[a2] e_a2; into the block frame: R^T (x - cg)
@@ -1236,18 +1155,9 @@ template <typename R, bool BLK> struct Sim {
           R cu_[16], cv_[16], gq[16];
           uint32_t vmask = 0;
           bool ins[4];
-#if defined(BRS_PATCH_DIST32)
-          typedef R GT;
-          const GT Vg[4] = {V[0][2], V[1][2], V[2][2], V[3][2]}, H12x2 = 2 * H1[2], H22x2 = 2 * H2[2];
-#else
           typedef double GT;
           const GT Vg[4] = {Cc2 - H12 - H22, Cc2 + H12 - H22, Cc2 + H12 + H22, Cc2 - H12 + H22}, H12x2 = 2 * H12, H22x2 = 2 * H22;
-#endif
-#if defined(BRS_PATCH_DIST32)
-          const GT gmargin = (GT)c.margin;
-#else
           const GT gmargin = P.margin_d[CC_BLOCK_ROBOT];
-#endif
 #pragma unroll
           for (int v = 0; v < 4; v++) {
             ins[v] = (abs_(V[v][0]) <= ra) & (abs_(V[v][1]) <= rb);
@@ -1301,11 +1211,7 @@ template <typename R, bool BLK> struct Sim {
           // (sorted groups of 4, bitonic merges to two sorted octets, low half of their merge) -- branch-free inside: a
           // per-lane selection loop would cost every lane its worst case
           uint32_t keep = vmask;
-#if defined(BRS_ALWAYS_REDUCE)  // A/B only
-          {
-#else
           if (__builtin_popcount(vmask) > PATCH_MAX) {  // rare with 6 slots: a wave usually skips the network
-#endif
             R k_[16];
 #pragma unroll
             for (int q = 0; q < 16; q++) k_[q] = ((vmask >> q) & 1u) ? gq[q] : (R)1e30;
@@ -1352,7 +1258,6 @@ template <typename R, bool BLK> struct Sim {
           BRS_MARK("cc_scatter");
           const int nkeep = (int)__builtin_popcount(keep);
           R* scr = st.base + (SLOT_ROBOT * SLOT_WORDS) * st.stride;
-#if BRS_FIXED_SCATTER
           // all 16 candidates parked at FIXED words of the (not yet written) robot<->floor slot region -- 48 stores at immediate
           // offsets, no address arithmetic; the insertion loop walks `keep` by bit scan (ascending candidate index = rank order)
           static_assert(16 * 3 <= N_ROBOT_SLOTS * SLOT_WORDS, "the candidate scratch must fit the robot<->floor slot region");
@@ -1360,46 +1265,20 @@ template <typename R, bool BLK> struct Sim {
           for (int q = 0; q < 16; q++) {
             scr[(3 * q) * st.stride] = cu_[q]; scr[(3 * q + 1) * st.stride] = cv_[q]; scr[(3 * q + 2) * st.stride] = gq[q];
           }
-#else
-          // compaction through the lane's LDS column: kept candidate with rank r -> scratch words 3r .. 3r+2 of the (not yet
-          // written) robot<->floor slot region, everything else -> a dump slot; the insertion loop then reads by rank
-#pragma unroll
-          for (int q = 0; q < 16; q++) {
-            const bool kq = ((keep >> q) & 1u) != 0;
-            const int rank = (int)__builtin_popcount(keep & ((1u << q) - 1u));
-            R* dst = scr + (3 * (kq ? rank : PATCH_MAX)) * st.stride;
-            dst[0] = cu_[q]; dst[st.stride] = cv_[q]; dst[2 * st.stride] = gq[q];
-          }
-#endif
           BRS_MARK("cc_insert");
           if (nkeep > 0) {
-#if BRS_PATCH_FRAME
             Patch Q;
             R V0[3], W0[3];
             patch_begin(st, F, S, nrm, Q, V0, W0);  // one contact frame for the whole patch
-#else
-            R fw[9];
-            world_frame(F, nrm, fw);  // one contact frame for the whole patch
-#endif
-#if BRS_FIXED_SCATTER
             uint32_t walk = keep;
-#endif
             for (int r = 0; r < nkeep; r++) {
-#if BRS_FIXED_SCATTER
               const int qi = __builtin_ctz(walk);
               walk &= walk - 1u;
               const R u = scr[(3 * qi) * st.stride], v = scr[(3 * qi + 1) * st.stride], g = scr[(3 * qi + 2) * st.stride];
-#else
-              const R u = scr[(3 * r) * st.stride], v = scr[(3 * r + 1) * st.stride], g = scr[(3 * r + 2) * st.stride];
-#endif
               const R wv = half + (R)0.5 * g;
               R pos[3] = {A0[0] + u * A1[0] + v * A2[0] + wv * A3[0], A0[1] + u * A1[1] + v * A2[1] + wv * A3[1],
                           A0[2] + u * A1[2] + v * A2[2] + wv * A3[2] + P.torso_cz};
-#if BRS_PATCH_FRAME
               add_patch_point(P, st, F, Q, V0, W0, pos, g);
-#else
-              add_coupled(P, st, F, S, pos, fw, g, 0, r > 0);
-#endif
             }
           }
         }
@@ -1419,17 +1298,10 @@ template <typename R, bool BLK> struct Sim {
       R wp[3] = {wsel == 1 ? -P.wheel_px : P.wheel_px, (R)0, P.wheel_pz};
       R d[3] = {cB[0] - wp[0], cB[1] - wp[1], cB[2] - wp[2]};
       R rr = P.wheel_brad + P.block_brad + c.margin;
-#ifdef BRS_NO_WHEELS
-      if (true) { BRS_TOC(11); return; }  // ablation only
-#endif
       if (dot_(d, d) > rr * rr) { BRS_TOC(11); return; }
-#if defined(BRS_PATCH_DIST32)
-      const R wband = (R)0;
-#else
       // candidates within 2 um BEYOND the margin are still tracked: whether the contact exists is then decided below on the
       // distance taken from the fp64 poses (wheel_block_dist_f64), like every other contact-existence test
       const R wband = sizeof(R) == 4 ? (R)2e-6 : (R)0;
-#endif
       R best = c.margin + wband, bpos[3] = {0, 0, 0}, bn[3] = {0, 0, 1}, wq[3] = {0, 0, 0};
       bool found = false;
       // (a) + (b): block points against the cylinder -- only the winning POINT is tracked in the loops (4 selects per
@@ -1511,46 +1383,39 @@ template <typename R, bool BLK> struct Sim {
           }
         }
       }
-#if !defined(BRS_PATCH_DIST32)
       if (sizeof(R) == 4 && found && best > c.margin - wband) {  // rare: a wave skips this block
         const double d64 = wheel_block_dist_f64(P, S, wsel);
         found = d64 < P.margin_d[CC_BLOCK_ROBOT];
         best = (R)d64;
       }
-#endif
       if (found) {
         R fw[9];
         world_frame(F, bn, fw);
-        add_coupled(P, st, F, S, bpos, fw, best, wsel, false);
+        add_wheel_contact(P, st, F, S, bpos, fw, best, wsel);
       }
     }
     BRS_TOC(11);
   }
 
-  // per-pass data of one coupled contact: frame axes (n,t1,t2) rotated into both body frames
+  // per-pass data of the block<->wheel contact: frame axes (n,t1,t2) rotated into both body frames.  The passes take it from their
+  // caller, next to the patch call: declared inside them the step kernels get another register allocation
   struct Coupled {
     R rT[3], rB[3], dT[3][3], dB[3][3], wc[3];
     R An, Bt1, Bt2, D, mu;
     int sel;
   };
-  // C persists across the points of the patch: the frame rows rotated into both body frames are computed at its first point.
-  // WHEEL = false: point c of the torso patch (no wheel dof involved); WHEEL = true: the wheel contact (slot PATCH_MAX).
-  template <bool WHEEL> static BRS_HD void coupled_load(const Params<R>& P, const Store<R>& st, const Frame& F, int c, Coupled& C) {
-    const int slot = WHEEL ? (int)PATCH_MAX : c;
+  static BRS_HD void coupled_load(const Params<R>& P, const Store<R>& st, const Frame& F, Coupled& C) {
+    const int slot = PATCH_MAX;
 #pragma unroll
     for (int j = 0; j < 3; j++) { C.rT[j] = st.getc(slot, j); C.rB[j] = st.getc(slot, 3 + j); }
     C.An = st.getc(slot, 6); C.Bt1 = st.getc(slot, 7); C.Bt2 = st.getc(slot, 8); C.D = st.getc(slot, 9);
-    C.sel = WHEEL ? sel_wheel_contact(F.sels) : 0;
+    C.sel = sel_wheel_contact(F.sels);
     C.mu = P.cc[CC_BLOCK_ROBOT].mu;
-    if (WHEEL || c == 0) {
-      const int fs = WHEEL ? 1 : 0;
-      R fw[9] = {st.getf(fs, 0), st.getf(fs, 1), st.getf(fs, 2), 0, 0, 0, 0, 0, 0};
-      make_frame(fw);
+    R fw[9] = {st.getf(1, 0), st.getf(1, 1), st.getf(1, 2), 0, 0, 0, 0, 0, 0};
+    make_frame(fw);
 #pragma unroll
-      for (int k = 0; k < 3; k++) { mulT_(F.RT, fw + 3 * k, C.dT[k]); mulT_(F.RB, fw + 3 * k, C.dB[k]); }
-    }
-    if constexpr (WHEEL) wheel_col(P, C.sel, C.rT, C.wc);
-    else { C.wc[0] = 0; C.wc[1] = 0; C.wc[2] = 0; }
+    for (int k = 0; k < 3; k++) { mulT_(F.RT, fw + 3 * k, C.dT[k]); mulT_(F.RB, fw + 3 * k, C.dB[k]); }
+    wheel_col(P, C.sel, C.rT, C.wc);
   }
 
   // ---- Newton solver of the convex acceleration problem  min 1/2 (x-a0)^T M (x-a0) + sum 1/2 D min(0, J x - aref)^2
@@ -1593,19 +1458,18 @@ template <typename R, bool BLK> struct Sim {
       return mk;
     }
 
-    // rows of one block<->robot contact at x (and its force when FORCES): a point of the torso patch or the wheel contact
-    template <bool FORCES, bool WHEEL>
-    static BRS_HD void passA_coupled(const Params<R>& P, Store<R>& st, const Frame& F, Masks& M, const R* x, int c, Coupled& C, R& cst,
-                                     R* l, R* fcon, bool& sm) {
-      coupled_load<WHEEL>(P, st, F, c, C);
+    // rows of the block<->wheel contact at x (and its force when FORCES)
+    template <bool FORCES>
+    static BRS_HD void passA_coupled(const Params<R>& P, Store<R>& st, const Frame& F, Masks& M, const R* x, Coupled& C, R& cst, R* l, R* fcon,
+                                     bool& sm) {
+      constexpr int c = PATCH_MAX;
+      coupled_load(P, st, F, C);
       R t[3];
       cross_(x + 3, C.rT, t);
       R paT[3] = {x[0] + t[0], x[1] + t[1], x[2] + t[2]};
-      if constexpr (WHEEL) {
-        const R x6 = x[6], x7 = x[7];
-        const R xs = by_wheel<R>(C.sel, x6, x7);
-        paT[0] += xs * C.wc[0]; paT[1] += xs * C.wc[1]; paT[2] += xs * C.wc[2];
-      }
+      const R x6 = x[6], x7 = x[7];
+      const R xs = by_wheel<R>(C.sel, x6, x7);
+      paT[0] += xs * C.wc[0]; paT[1] += xs * C.wc[1]; paT[2] += xs * C.wc[2];
       cross_(x + 11, C.rB, t);
       R paB[3] = {x[8] + t[0], x[9] + t[1], x[10] + t[2]};
       int mk = rows_(dot_(C.dB[0], paB) - dot_(C.dT[0], paT) - C.An, C.mu * (dot_(C.dB[1], paB) - dot_(C.dT[1], paT)) - C.Bt1,
@@ -1622,11 +1486,9 @@ template <typename R, bool BLK> struct Sim {
         cross_(C.rT, fT, t);
         fcon[0] += fT[0]; fcon[1] += fT[1]; fcon[2] += fT[2];
         fcon[3] += t[0]; fcon[4] += t[1]; fcon[5] += t[2];
-        if constexpr (WHEEL) {
-          R fw = dot_(C.wc, fT);
-          fcon[6] += C.sel == 1 ? fw : (R)0;
-          fcon[7] += C.sel == 2 ? fw : (R)0;
-        }
+        R fw = dot_(C.wc, fT);
+        fcon[6] += C.sel == 1 ? fw : (R)0;
+        fcon[7] += C.sel == 2 ? fw : (R)0;
         cross_(C.rB, fB, t);
         fcon[8] += fB[0]; fcon[9] += fB[1]; fcon[10] += fB[2];
         fcon[11] += t[0]; fcon[12] += t[1]; fcon[13] += t[2];
@@ -1752,12 +1614,8 @@ template <typename R, bool BLK> struct Sim {
           }
         }
         Coupled C;
-#if BRS_PATCH_FRAME
         if (F.nc > 0) passA_patch<FORCES>(P, st, F, M, x, cst, l, fcon, sm);
-#else
-        for (int c = 0; c < F.nc; c++) passA_coupled<FORCES, false>(P, st, F, M, x, c, C, cst, l, fcon, sm);
-#endif
-        if (sel_wheel_contact(F.sels)) passA_coupled<FORCES, true>(P, st, F, M, x, PATCH_MAX, C, cst, l, fcon, sm);
+        if (sel_wheel_contact(F.sels)) passA_coupled<FORCES>(P, st, F, M, x, C, cst, l, fcon, sm);
       }
       cost = cst;
       same = sm;
@@ -1768,8 +1626,7 @@ template <typename R, bool BLK> struct Sim {
     // One contact into H and rhs through its 3x3 weight matrix in the contact frame:
     //   rows j_k = G_n +- mu G_t ;  sum_k act_k D j_k j_k^T = G^T W G ,  W = D [[sum a, mu(a0-a1), mu(a2-a3)], [., mu^2(a0+a1), 0], [., 0, mu^2(a2+a3)]]
     // G rows arrive as pairs over the dof range [2*P0, 2*(P0+NPA)); `eval`: decide the active rows at x (else from mnew).
-    // SKIP: a pair of the range whose G entries are zero (the wheel dofs for a point of the torso patch): left out everywhere
-    template <int P0, int NPA, int SKIP = -1>
+    template <int P0, int NPA>
     static BRS_HD int contact_into(V2<R>* H, V2<R>* rhs2, const V2<R>* gn, const V2<R>* g1, const V2<R>* g2, R mu, R D, R An,
                                    R Bt1, R Bt2, bool eval, int mnew, const V2<R>* x2) {
       int mk = mnew;
@@ -1777,7 +1634,6 @@ template <typename R, bool BLK> struct Sim {
         V2<R> an = v2_splat<R>((R)0), a1 = an, a2 = an;
 #pragma unroll
         for (int k = 0; k < NPA; k++) {
-          if (k == SKIP) continue;
           an = v2_fma(gn[k], x2[P0 + k], an); a1 = v2_fma(g1[k], x2[P0 + k], a1); a2 = v2_fma(g2[k], x2[P0 + k], a2);
         }
         R cn = (an.x + an.y) - An, c1 = mu * (a1.x + a1.y) - Bt1, c2 = mu * (a2.x + a2.y) - Bt2;
@@ -1794,7 +1650,6 @@ template <typename R, bool BLK> struct Sim {
       const V2<R> srn = v2_splat(rn), sr1 = v2_splat(r1), sr2 = v2_splat(r2);
 #pragma unroll
       for (int k = 0; k < NPA; k++) {
-        if (k == SKIP) continue;
         tn[k] = v2_fma(sWnn, gn[k], v2_fma(sWn1, g1[k], v2_mul(sWn2, g2[k])));
         t1[k] = v2_fma(sWn1, gn[k], v2_mul(sW11, g1[k]));
         t2[k] = v2_fma(sWn2, gn[k], v2_mul(sW22, g2[k]));
@@ -1809,11 +1664,9 @@ template <typename R, bool BLK> struct Sim {
         const V2<R>* tt = axis == 0 ? t2 : (axis == 1 ? t1 : tn);
 #pragma unroll
         for (int a = 0; a < 2 * NPA; a++) {
-          if (a / 2 == SKIP) continue;
           const V2<R> sg = v2_splat((a & 1) ? gg[a / 2].y : gg[a / 2].x);
 #pragma unroll
           for (int k = 0; k <= a / 2; k++) {
-            if (k == SKIP) continue;
             H[hp(2 * P0 + a, P0 + k)] = v2_fma(sg, tt[k], H[hp(2 * P0 + a, P0 + k)]);
           }
         }
@@ -1821,13 +1674,11 @@ template <typename R, bool BLK> struct Sim {
       return mk;
     }
 
-    // one block<->robot contact into H / rhs.  A point of the torso patch does not see the wheel dofs: pair 3 of its G rows is
-    // zero and 14 of the 56 pair updates fall away; the wheel contact (its own slot, met once, outside the patch loop) takes
-    // the full form -- no per-iteration divergence between the two
-    template <bool WHEEL>
-    static BRS_HD void assemble_coupled(const Params<R>& P, Store<R>& st, const Frame& F, Masks& M, bool first, uint32_t srcC, int c,
-                                        Coupled& C, V2<R>* H, V2<R>* rhs2, const V2<R>* x2) {
-      coupled_load<WHEEL>(P, st, F, c, C);
+    // the block<->wheel contact (its own slot, met once, outside the patch) into H / rhs: all 14 dofs
+    static BRS_HD void assemble_coupled(const Params<R>& P, Store<R>& st, const Frame& F, Masks& M, bool first, uint32_t srcC, Coupled& C,
+                                        V2<R>* H, V2<R>* rhs2, const V2<R>* x2) {
+      constexpr int c = PATCH_MAX;
+      coupled_load(P, st, F, C);
       V2<R> g[3][7];
 #pragma unroll
       for (int k = 0; k < 3; k++) {
@@ -1835,21 +1686,12 @@ template <typename R, bool BLK> struct Sim {
         cross_(C.rT, C.dT[k], ct);
         cross_(C.rB, C.dB[k], cb);
         g[k][0] = v2_make(-C.dT[k][0], -C.dT[k][1]); g[k][1] = v2_make(-C.dT[k][2], -ct[0]); g[k][2] = v2_make(-ct[1], -ct[2]);
-        if constexpr (WHEEL) {
-          const R wk = dot_(C.wc, C.dT[k]);
-          g[k][3] = v2_make(C.sel == 1 ? -wk : (R)0, C.sel == 2 ? -wk : (R)0);
-        } else
-          g[k][3] = v2_splat<R>((R)0);
+        const R wk = dot_(C.wc, C.dT[k]);
+        g[k][3] = v2_make(C.sel == 1 ? -wk : (R)0, C.sel == 2 ? -wk : (R)0);
         g[k][4] = v2_make(C.dB[k][0], C.dB[k][1]); g[k][5] = v2_make(C.dB[k][2], cb[0]); g[k][6] = v2_make(cb[1], cb[2]);
       }
-      int mk;
-      if constexpr (WHEEL) {
-        const bool ev = first && !(BRS_MASK_HINT && sel_wheel_contact(F.psels) == C.sel);
-        mk = contact_into<0, 7>(H, rhs2, g[0], g[1], g[2], C.mu, C.D, C.An, C.Bt1, C.Bt2, ev, get4(srcC, c), x2);
-      } else {
-        const bool ev = first && !(BRS_MASK_HINT && c < F.pnc);
-        mk = contact_into<0, 7, 3>(H, rhs2, g[0], g[1], g[2], C.mu, C.D, C.An, C.Bt1, C.Bt2, ev, get4(srcC, c), x2);
-      }
+      const bool ev = first && !(sel_wheel_contact(F.psels) == C.sel);
+      const int mk = contact_into<0, 7>(H, rhs2, g[0], g[1], g[2], C.mu, C.D, C.An, C.Bt1, C.Bt2, ev, get4(srcC, c), x2);
       M.hC |= put4(mk, c);
     }
 
@@ -1870,7 +1712,7 @@ template <typename R, bool BLK> struct Sim {
         const R rx = st.getc(c, 0), ry = st.getc(c, 1), rz = st.getc(c, 2);
         const R An = st.getc(c, 3), Bt1 = st.getc(c, 4), Bt2 = st.getc(c, 5), D = st.getc(c, 6);
         int mk = get4(srcC, c);
-        if (first && !(BRS_MASK_HINT && c < F.pnc)) {
+        if (first && !(c < F.pnc)) {
           const R cn = Vp[0] + (Wp[1] * rz - Wp[2] * ry) - An, c1 = mu * (Vp[1] + (Wp[2] * rx - Wp[0] * rz)) - Bt1,
                   c2 = mu * (Vp[2] + (Wp[0] * ry - Wp[1] * rx)) - Bt2;
           mk = (cn + c1 < 0 ? 1 : 0) | (cn - c1 < 0 ? 2 : 0) | (cn + c2 < 0 ? 4 : 0) | (cn - c2 < 0 ? 8 : 0);
@@ -1998,7 +1840,7 @@ template <typename R, bool BLK> struct Sim {
         R r[3] = {st.get(s, 0), st.get(s, 1), st.get(s, 2)};
         R An = st.get(s, 3), Bt1 = st.get(s, 4), Bt2 = st.get(s, 5), D = st.get(s, 6);
         int sel = sel_robot(F.sels, c);
-        const bool ev = first && !(BRS_MASK_HINT && c < F.pnfr && sel_robot(F.psels, c) == sel);
+        const bool ev = first && !(c < F.pnfr && sel_robot(F.psels, c) == sel);
         R mu = sel == 0 ? P.cc[CC_TORSO_FLOOR].mu : F.muW;
         R wc[3], rn[3], r1[3], r2[3];
         wheel_col(P, sel, r, wc);
@@ -2017,7 +1859,7 @@ template <typename R, bool BLK> struct Sim {
           int s = SLOT_BLOCK + c;
           R r[3] = {st.get(s, 0), st.get(s, 1), st.get(s, 2)};
           R An = st.get(s, 3), Bt1 = st.get(s, 4), Bt2 = st.get(s, 5), D = st.get(s, 6);
-          const bool ev = first && !(BRS_MASK_HINT && c < F.pnfb);
+          const bool ev = first && !(c < F.pnfb);
           R rn[3], r1[3], r2[3];
           cross_(r, F.nB(), rn); cross_(r, F.t1B(), r1); cross_(F.xB(), r, r2);
           V2<R> gn[3] = {v2_make(F.nB()[0], F.nB()[1]), v2_make(F.nB()[2], rn[0]), v2_make(rn[1], rn[2])};
@@ -2028,13 +1870,9 @@ template <typename R, bool BLK> struct Sim {
         }
         Coupled C;
         BRS_MARK("asm_patch_loop");
-#if BRS_PATCH_FRAME
         if (F.nc > 0) assemble_patch(P, st, F, M, first, srcC, H, rhs2, x);
-#else
-        for (int c = 0; c < F.nc; c++) assemble_coupled<false>(P, st, F, M, first, srcC, c, C, H, rhs2, x2);
-#endif
         BRS_MARK("asm_wheel_contact");
-        if (sel_wheel_contact(F.sels)) assemble_coupled<true>(P, st, F, M, first, srcC, PATCH_MAX, C, H, rhs2, x2);
+        if (sel_wheel_contact(F.sels)) assemble_coupled(P, st, F, M, first, srcC, C, H, rhs2, x2);
         BRS_MARK("asm_done");
       }
     }
@@ -2042,6 +1880,7 @@ template <typename R, bool BLK> struct Sim {
     // ONE Newton iteration at x (in/out); fcon out = J^T f at the new x.  Returns true when the new point is the
     // minimiser (a full step that reproduced its own active set) or the iteration cap is reached.
     // State carried by the caller across iterations of one substep: first (true on entry), it (0), cost.
+    static constexpr int UNDAMPED_ITERS = 3;  // full Newton steps before the backtracking fallback may engage
     static BRS_HD bool iterate(const Params<R>& P, Store<R>& st, const Frame& F, Masks& M, R* x, const R* a0, R* fcon, bool& first,
                                int& it, R& cost) {
       V2<R> H[NH2], rhs2[NP];
@@ -2066,7 +1905,7 @@ template <typename R, bool BLK> struct Sim {
       BRS_TOC(5);
       BRS_TIC(6);
       BRS_MARK("iter_passA");
-      const bool lite = it + 1 < BRS_UNDAMPED_ITERS;  // the damped fallback needs costs and forces at every point
+      const bool lite = it + 1 < UNDAMPED_ITERS;  // the damped fallback needs costs and forces at every point
       if (lite) {
         passA<false>(P, st, F, M, xn, a0, ct, ft, same);
         gauss(P, xn, a0, ft, ct);  // ft = M (xn - a0): the constraint force if xn reproduces its active set
@@ -2079,7 +1918,7 @@ template <typename R, bool BLK> struct Sim {
       bool full = true;
       // pure active-set iteration for the first sweeps (it terminates at once in ~97% of the substeps); if it has not
       // settled by then, fall back to cost-monotone damping, which cannot cycle
-      for (int bt = 0; it >= BRS_UNDAMPED_ITERS && bt < 6 && ct > cost + (R)1e-5 * abs_(cost) + (R)1e-12; bt++) {
+      for (int bt = 0; it >= UNDAMPED_ITERS && bt < 6 && ct > cost + (R)1e-5 * abs_(cost) + (R)1e-12; bt++) {
         full = false;
         BRS_STAT(stats().backtracks[0]++);
 #pragma unroll
@@ -2105,15 +1944,13 @@ template <typename R, bool BLK> struct Sim {
     int it;
     Masks M;
   };
-  using CT = CtrlT<R>;
-  static BRS_HD void sub_begin(const Params<R>& P, Store<R>& st, ES& S, CT ctrlL, CT ctrlR, SubCtx& C) {
+  // the two servo targets (data.ctrl) are held in fp64 across the substeps of a step: the reference forms ctrl = qvel + 4 a in fp64
+  static BRS_HD void sub_begin(const Params<R>& P, Store<R>& st, ES& S, double ctrlL, double ctrlR, SubCtx& C) {
     Frame& F = C.F;
     R* f = C.f;
     BRS_MARK("begin_kin");
     BRS_TIC(0);
-#if BRS_LAZY_VEL32
     S.derive_vel32();
-#endif
     // kinematics
     R qf[4] = {(R)S.q[0], (R)S.q[1], (R)S.q[2], (R)S.q[3]};
     quat2mat_(qf, F.RT);
@@ -2131,7 +1968,6 @@ template <typename R, bool BLK> struct Sim {
     f[4] = -(wz * Lx - wx * Lz) + P.mcz * gb[0];
     f[5] = -(wx * Ly - wy * Lx);
     // velocity servos (envs/robot-02.xml:22-25): ctrl clamp, force clamp; derivative dropped when clamped
-#if BRS_VEL64
     // target minus wheel rate in fp64: the two are close (ctrl = rate + 4 a), their fp32 difference would carry ~1e-5 of the force,
     // and whether the force clamp binds -- which decides if the servo's derivative enters implicitfast -- is a discrete
     // outcome: a wheel gains 0.26 rad/s per substep clamped and 0.10 unclamped
@@ -2140,14 +1976,6 @@ template <typename R, bool BLK> struct Sim {
     C.clL = fLd >= P.forcerange_d || fLd <= -P.forcerange_d;
     C.clR = fRd >= P.forcerange_d || fRd <= -P.forcerange_d;
     R fL = (R)min_(max_(fLd, -P.forcerange_d), P.forcerange_d), fR = (R)min_(max_(fRd, -P.forcerange_d), P.forcerange_d);
-#else
-    R uL = min_(max_(ctrlL, -P.ctrlrange), P.ctrlrange), uR = min_(max_(ctrlR, -P.ctrlrange), P.ctrlrange);
-    R fL = P.kv * (uL - S.ww[0]), fR = P.kv * (uR - S.ww[1]);
-    C.clL = fL >= P.forcerange || fL <= -P.forcerange;
-    C.clR = fR >= P.forcerange || fR <= -P.forcerange;
-    fL = min_(max_(fL, -P.forcerange), P.forcerange);
-    fR = min_(max_(fR, -P.forcerange), P.forcerange);
-#endif
     f[6] = fL - P.damping * S.ww[0];
     f[7] = fR - P.damping * S.ww[1];
     msolve0_(P, f, F.a0);
@@ -2227,56 +2055,27 @@ template <typename R, bool BLK> struct Sim {
     // advance: velocities first, then positions with the NEW velocities
     R aw[3];
     mul_(F.RT, acc, aw);
-#if BRS_VEL64
 #pragma unroll
     for (int i = 0; i < 3; i++) {
       S.vd[i] += P.h_d * (double)aw[i]; S.wd[i] += P.h_d * (double)acc[3 + i];
-#if !BRS_LAZY_VEL32
-      S.v[i] = (R)S.vd[i]; S.w[i] = (R)S.wd[i];
-#endif
     }
     S.wwd[0] += P.h_d * (double)acc[6]; S.wwd[1] += P.h_d * (double)acc[7];
-#if !BRS_LAZY_VEL32
-    S.ww[0] = (R)S.wwd[0]; S.ww[1] = (R)S.wwd[1];
-#endif
 #pragma unroll
     for (int i = 0; i < 3; i++) S.p[i] += P.h_d * S.vd[i];
     quat_advance(S.q, S.wd[0], S.wd[1], S.wd[2], P.h_d);
     S.th[0] += P.h_d * S.wwd[0];
     S.th[1] += P.h_d * S.wwd[1];
-#else
-#pragma unroll
-    for (int i = 0; i < 3; i++) { S.v[i] += P.h * aw[i]; S.w[i] += P.h * acc[3 + i]; }
-    S.ww[0] += P.h * acc[6];
-    S.ww[1] += P.h * acc[7];
-#pragma unroll
-    for (int i = 0; i < 3; i++) S.p[i] += P.h_d * (double)S.v[i];
-    quat_advance(S.q, (double)S.w[0], (double)S.w[1], (double)S.w[2], P.h_d);
-    S.th[0] += P.h_d * (double)S.ww[0];
-    S.th[1] += P.h_d * (double)S.ww[1];
-#endif
     if constexpr (BLK) {
       // block smooth force: gravity only (isotropic inertia: no gyroscopic torque)
       R ab[3], al[3] = {fcon[8] * P.inv_mB - P.g * F.nB()[0], fcon[9] * P.inv_mB - P.g * F.nB()[1], fcon[10] * P.inv_mB - P.g * F.nB()[2]};
       mul_(F.RB, al, ab);
-#if BRS_VEL64
 #pragma unroll
       for (int i = 0; i < 3; i++) {
         S.bvd[i] += P.h_d * (double)ab[i]; S.bwd[i] += P.h_d * (double)(fcon[11 + i] * P.inv_IB);
-#if !BRS_LAZY_VEL32
-        S.bv[i] = (R)S.bvd[i]; S.bw[i] = (R)S.bwd[i];
-#endif
       }
 #pragma unroll
       for (int i = 0; i < 3; i++) S.bp[i] += P.h_d * S.bvd[i];
       quat_advance(S.bq, S.bwd[0], S.bwd[1], S.bwd[2], P.h_d);
-#else
-#pragma unroll
-      for (int i = 0; i < 3; i++) { S.bv[i] += P.h * ab[i]; S.bw[i] += P.h * fcon[11 + i] * P.inv_IB; }
-#pragma unroll
-      for (int i = 0; i < 3; i++) S.bp[i] += P.h_d * (double)S.bv[i];
-      quat_advance(S.bq, (double)S.bw[0], (double)S.bw[1], (double)S.bw[2], P.h_d);
-#endif
     }
     S.time += P.h_d;
     // first guess of the next substep's active set
@@ -2290,7 +2089,7 @@ template <typename R, bool BLK> struct Sim {
     BRS_MARK("end_done");
   }
   // un-flattened form (one lane at a time: host tests, single substeps)
-  static BRS_HD void substep(const Params<R>& P, Store<R>& st, ES& S, CT ctrlL, CT ctrlR) {
+  static BRS_HD void substep(const Params<R>& P, Store<R>& st, ES& S, double ctrlL, double ctrlR) {
     SubCtx C;
     sub_begin(P, st, S, ctrlL, ctrlR, C);
     while (!C.conv) sub_iter(P, st, S, C);
@@ -2399,9 +2198,7 @@ template <typename R, bool BLK> struct Sim {
     (void)xp0; (void)xp1;
     euler_slot_quat(xr, yr, zr, S.bq);
     S.bv[0] = vx * k; S.bv[1] = vy * k; S.bv[2] = vz * k;
-#if BRS_VEL64
     if constexpr (BLK) { S.bvd[0] = (double)S.bv[0]; S.bvd[1] = (double)S.bv[1]; S.bvd[2] = (double)S.bv[2]; }
-#endif
   }
   static BRS_HD void env_reset(const Params<R>& P, ES& S, Stream<R>& rng, float* obs) {
     const R TWO_PI = (R)6.283185307179586476925;
@@ -2449,27 +2246,16 @@ template <typename R, bool BLK> struct Sim {
 #pragma unroll
     for (int k = 0; k < 4; k++) bad |= isbadnum_(S.q[k]);
     bad |= isbadnum_(S.th[0]) | isbadnum_(S.th[1]);
-#if BRS_VEL64
 #pragma unroll
     for (int k = 0; k < 3; k++) bad |= isbadnum_(S.vd[k]) | isbadnum_(S.wd[k]);
     bad |= isbadnum_(S.wwd[0]) | isbadnum_(S.wwd[1]);
-#else
-#pragma unroll
-    for (int k = 0; k < 3; k++) bad |= isbadnum_(S.v[k]) | isbadnum_(S.w[k]);
-    bad |= isbadnum_(S.ww[0]) | isbadnum_(S.ww[1]);
-#endif
     if constexpr (BLK) {
 #pragma unroll
       for (int k = 0; k < 3; k++) bad |= isbadnum_(S.bp[k]);
 #pragma unroll
       for (int k = 0; k < 4; k++) bad |= isbadnum_(S.bq[k]);
-#if BRS_VEL64
 #pragma unroll
       for (int k = 0; k < 3; k++) bad |= isbadnum_(S.bvd[k]) | isbadnum_(S.bwd[k]);
-#else
-#pragma unroll
-      for (int k = 0; k < 3; k++) bad |= isbadnum_(S.bv[k]) | isbadnum_(S.bw[k]);
-#endif
     }
     return bad;
   }
@@ -2477,7 +2263,7 @@ template <typename R, bool BLK> struct Sim {
   // (EnvState::bad_start); its substeps run on garbage in between
   static BRS_HD bool start_bad(const ES& S, float a0, float a1) { return state_bad(S) | isnan_(a0) | isnan_(a1); }
   // ---- one full env step = env_pre (reward + control law on the PRE-step state) -> nsub substeps -> env_post
-  static BRS_HD R env_pre(const Params<R>& P, ES& S, Stream<R>& rng, float a0, float a1, CT& ctrlL, CT& ctrlR) {
+  static BRS_HD R env_pre(const Params<R>& P, ES& S, Stream<R>& rng, float a0, float a1, double& ctrlL, double& ctrlR) {
     // a bad friction coefficient (Env02; only set_aux can plant one) is no bad STATE: the model's own value takes its place
     if (P.per_env_mu && isbadnum_(S.muw)) S.muw = P.cc[CC_WHEEL_FLOOR].mu;
     if (P.v3) {  // envs/env01_v3.py:28-36: schedule keyed on data.time at the start of step
@@ -2488,13 +2274,8 @@ template <typename R, bool BLK> struct Sim {
       else if (t > 1.0) S.tws = S.dts;
     }
     R rew = get_reward(P, S, rng);
-#if BRS_VEL64
     ctrlL = S.wwd[0] + (double)a0 * 4.0;  // envs/env01_v2.py:31-36 ; the env does not clip the action
     ctrlR = S.wwd[1] + (double)a1 * 4.0;
-#else
-    ctrlL = S.ww[0] + (R)a0 * (R)4;  // envs/env01_v2.py:31-36 ; the env does not clip the action
-    ctrlR = S.ww[1] + (R)a1 * (R)4;
-#endif
     return rew;
   }
   static BRS_HD void env_post(const Params<R>& P, ES& S, Stream<R>& rng, R rew, float* obs, float* terminal_obs, float& reward,
@@ -2533,7 +2314,7 @@ template <typename R, bool BLK> struct Sim {
   }
   static BRS_HD void env_step(const Params<R>& P, Store<R>& st, ES& S, Stream<R>& rng, float a0, float a1, float* obs,
                               float* terminal_obs, float& reward, int& terminated, int& truncated) {
-    CT ctrlL, ctrlR;
+    double ctrlL, ctrlR;
     S.bad_start = start_bad(S, a0, a1);
     R rew = env_pre(P, S, rng, a0, a1, ctrlL, ctrlR);
     for (int k = 0; k < P.nsub; k++) {

@@ -89,11 +89,7 @@ __device__ __forceinline__ void step_body(const Params<float>& Prt, const int N,
   // The map and the cost classes live behind the int state in the SAME allocation (ii + NI * N: perm[N], then keys[N] bytes):
   // no extra kernel arguments -- the kernel is SGPR-bound too (its Params live in SGPRs), and two more pointers held across
   // the loop cost ~10 % in spill traffic (measured).  Env01 has no rare collision paths: identity, decided at compile time.
-#if defined(BRS_NO_PERM)  // A/B builds only
-  const LaneIndex idx{nullptr, lane_slot};
-#else
   const LaneIndex idx{BLK ? ii + (size_t)Layout<BLK>::NI * N : nullptr, lane_slot};
-#endif
   Store<float> st = lane_store<BLK>(lds);
 #if defined(BRS_TIMING) && defined(__HIP_DEVICE_COMPILE__)
   if ((threadIdx.x & 63) == 0) for (int k = 0; k < 16; k++) brs_tim_slots()[k] = 0;
@@ -308,6 +304,33 @@ size_t lds_bytes(const brs_handle* h) { return (size_t)h->bt * (h->blk ? LDS_WOR
 #endif
 int grid_of(const brs_handle* h) { return (h->N + h->bt - 1) / h->bt; }
 
+// every step-kernel instantiation there is: brs_create prepares a handle's rows, brs_step launches the one step_kernel_of selects
+struct StepKernel { bool blk, occ2; int variant; const void* fn; };
+const StepKernel STEP_KERNELS[] = {
+    {true, false, -1, (const void*)brs_step_kernel<true, -1>},
+    {true, false, ENV03_V1, (const void*)brs_step_kernel<true, ENV03_V1>},
+    {true, false, ENV03_V2, (const void*)brs_step_kernel<true, ENV03_V2>},
+    {false, false, -1, (const void*)brs_step_kernel<false, -1>},
+    {false, false, ENV01_V1, (const void*)brs_step_kernel<false, ENV01_V1>},
+    {false, false, ENV01_V2, (const void*)brs_step_kernel<false, ENV01_V2>},
+    {false, false, ENV01_V3, (const void*)brs_step_kernel<false, ENV01_V3>},
+    {false, false, ENV02_V1, (const void*)brs_step_kernel<false, ENV02_V1>},
+    {false, true, -1, (const void*)brs_step_kernel_occ2<-1>},
+    {false, true, ENV01_V1, (const void*)brs_step_kernel_occ2<ENV01_V1>},
+    {false, true, ENV01_V2, (const void*)brs_step_kernel_occ2<ENV01_V2>},
+    {false, true, ENV01_V3, (const void*)brs_step_kernel_occ2<ENV01_V3>},
+    {false, true, ENV02_V1, (const void*)brs_step_kernel_occ2<ENV02_V1>},
+};
+// the kernel brs_step launches for this handle: the capped build only for the Env01 family at one wave per workgroup, model
+// constants folded only at the default timestep (every handle brs_create returns has one: it checks)
+const StepKernel* step_kernel_of(const brs_handle* h) {
+  const bool occ2 = !h->blk && h->occ2 && h->bt == 64;
+  const int variant = h->folded ? h->P.variant : -1;
+  for (const StepKernel& k : STEP_KERNELS)
+    if (k.blk == h->blk && k.occ2 == occ2 && k.variant == variant) return &k;
+  return nullptr;
+}
+
 template <bool BLK> int upload_state(brs_handle* h, const std::vector<double>& d, const std::vector<float>& f, const std::vector<int>& ii) {
   BRS_HIP_TRY(h, hipMemcpy(h->d, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice));
   BRS_HIP_TRY(h, hipMemcpy(h->f, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -389,17 +412,10 @@ int brs_create(const brs_config* cfg, brs_handle** out) {
   size_t lb = lds_bytes(h);
   hipError_t ea = hipSuccess;
   auto want = [&](const void* fn) { if (ea == hipSuccess) ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb); };
-  if (h->blk) {
-    want((const void*)brs_step_kernel<true, -1>); want((const void*)brs_step_kernel<true, ENV03_V1>);
-    want((const void*)brs_step_kernel<true, ENV03_V2>); want((const void*)brs_physics_kernel<true>);
-  } else {
-    want((const void*)brs_step_kernel<false, -1>); want((const void*)brs_step_kernel<false, ENV01_V1>);
-    want((const void*)brs_step_kernel<false, ENV01_V2>); want((const void*)brs_step_kernel<false, ENV01_V3>);
-    want((const void*)brs_step_kernel<false, ENV02_V1>); want((const void*)brs_physics_kernel<false>);
-    want((const void*)brs_step_kernel_occ2<-1>); want((const void*)brs_step_kernel_occ2<ENV01_V1>);
-    want((const void*)brs_step_kernel_occ2<ENV01_V2>); want((const void*)brs_step_kernel_occ2<ENV01_V3>);
-    want((const void*)brs_step_kernel_occ2<ENV02_V1>);
-  }
+  if (!step_kernel_of(h)) return bail("brs_create: no step kernel for this variant");
+  for (const StepKernel& k : STEP_KERNELS)
+    if (k.blk == h->blk) want(k.fn);
+  want(h->blk ? (const void*)brs_physics_kernel<true> : (const void*)brs_physics_kernel<false>);
   if (ea != hipSuccess) return bail(std::string("brs_create: hipFuncSetAttribute: ") + hipGetErrorString(ea));
   *out = h;
   return BRS_OK;
@@ -439,33 +455,8 @@ int brs_step(brs_handle* h, const float* actions_dev, float* obs_dev, float* rew
   hipStream_t s = (hipStream_t)stream;
   size_t lb = lds_bytes(h);
   const dim3 grid(grid_of(h)), block(h->bt);
-#define BRS_LAUNCH_STEP(BLK_, VAR_)                                                                                          \
-  hipLaunchKernelGGL((brs_step_kernel<BLK_, VAR_>), grid, block, lb, s, h->P, h->N, h->d, h->f, h->ii, actions_dev, obs_dev, \
-                     reward_dev, terminated_dev, truncated_dev, terminal_obs_dev)
-#define BRS_LAUNCH_OCC2(VAR_)                                                                                              \
-  hipLaunchKernelGGL((brs_step_kernel_occ2<VAR_>), grid, block, lb, s, h->P, h->N, h->d, h->f, h->ii, actions_dev, obs_dev, \
-                     reward_dev, terminated_dev, truncated_dev, terminal_obs_dev)
-  if (!h->blk && h->occ2 && h->bt == 64) {
-    switch (h->folded ? h->P.variant : -1) {
-      case ENV01_V1: BRS_LAUNCH_OCC2(ENV01_V1); break;
-      case ENV01_V2: BRS_LAUNCH_OCC2(ENV01_V2); break;
-      case ENV01_V3: BRS_LAUNCH_OCC2(ENV01_V3); break;
-      case ENV02_V1: BRS_LAUNCH_OCC2(ENV02_V1); break;
-      default: BRS_LAUNCH_OCC2(-1);
-    }
-  } else
-  switch (h->folded ? h->P.variant : -1) {
-    case ENV01_V1: BRS_LAUNCH_STEP(false, ENV01_V1); break;
-    case ENV01_V2: BRS_LAUNCH_STEP(false, ENV01_V2); break;
-    case ENV01_V3: BRS_LAUNCH_STEP(false, ENV01_V3); break;
-    case ENV02_V1: BRS_LAUNCH_STEP(false, ENV02_V1); break;
-    case ENV03_V1: BRS_LAUNCH_STEP(true, ENV03_V1); break;
-    case ENV03_V2: BRS_LAUNCH_STEP(true, ENV03_V2); break;
-    default:
-      if (h->blk) BRS_LAUNCH_STEP(true, -1); else BRS_LAUNCH_STEP(false, -1);
-  }
-#undef BRS_LAUNCH_STEP
-#undef BRS_LAUNCH_OCC2
+  void* args[] = {&h->P, &h->N, &h->d, &h->f, &h->ii, &actions_dev, &obs_dev, &reward_dev, &terminated_dev, &truncated_dev, &terminal_obs_dev};
+  (void)hipLaunchKernel(step_kernel_of(h)->fn, grid, block, args, lb, s);  // its status is what hipGetLastError returns below
   // a step launch that failed left no bucket counts: the grouping kernel must not run on them (its output would not be a
   // permutation, and later steps would skip or double envs)
   BRS_HIP_TRY(h, hipGetLastError());
@@ -557,9 +548,9 @@ const char* brs_step_kernel_name(const brs_handle* h) {
   if (!h) return "";
   // the instantiation brs_step launches, spelled as rocprofv3 prints it
   static thread_local char name[64];
-  const int var = h->folded ? h->P.variant : -1;
-  if (!h->blk && h->occ2 && h->bt == 64) std::snprintf(name, sizeof name, "brs_step_kernel_occ2<%d>", var);
-  else std::snprintf(name, sizeof name, "brs_step_kernel<%s, %d>", h->blk ? "true" : "false", var);
+  const StepKernel* k = step_kernel_of(h);
+  if (k->occ2) std::snprintf(name, sizeof name, "brs_step_kernel_occ2<%d>", k->variant);
+  else std::snprintf(name, sizeof name, "brs_step_kernel<%s, %d>", k->blk ? "true" : "false", k->variant);
   return name;
 }
 

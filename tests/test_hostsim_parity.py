@@ -128,7 +128,8 @@ def test_constructed_floor_contact_states(double, tol):
 def test_float_build_stays_on_the_double_build_over_full_env_steps(env_id, n, steps):
     """kernel source in float vs in double, teacher-forced over full env steps with auto-reset (the bench workload's dynamics):
     the distances that decide whether a contact point exists are taken from the fp64 poses.  The same A/B on
-    the CPU (this library built with -DBRS_FLOOR_DIST32 -DBRS_PATCH_DIST32, 2,048 envs x 150 steps, ~300 k env-steps):
+    the CPU (a round-3 build of this library with fp32 distances, whose compile-time switches are gone; 2,048 envs x 150 steps,
+    ~300 k env-steps):
     env-steps above 1e-5: Env03-v2 9 -> 2, Env01-v2 69 -> 13; above 1e-6: 27 -> 6 and 602 -> 76; maximum 9.9e-5 -> 2.1e-5 and
     5.2e-5 -> 3.3e-5."""
     rng = np.random.default_rng(3)

@@ -27,7 +27,7 @@ IDS = ("Env01-v1", "Env01-v2", "Env03-v1", "Env03-v2", "Env01-v3", "Env02-v1")
 RUNTIME = dict(substeps=100, timestep=5e-5)   # a non-default timestep: the kernel whose model constants are arguments
 OUTPUTS = ("obs", "reward", "terminated", "truncated", "terminal_obs")
 
-# ---- A: every step kernel instantiation brs_step can launch (brs_kernels.hip: brs_step, brs_step_kernel_name) -> the tests
+# ---- A: every step kernel instantiation brs_step can launch (brs_kernels.hip: STEP_KERNELS, step_kernel_of) -> the tests
 # that run it.  Names in this module are checked to exist; "gp." names live in tests/test_gpu_parity.py.
 _SHARED_RNG = "gp.test_env_step_parity_with_shared_rng"
 KERNELS = {

@@ -3,7 +3,7 @@
 runs on one box compare): extra -D flags, output under ab/ (git-ignored *.so, travels with gpurun); select it with
 BRS_HIP_LIB=ab/libbrs_hip_<name>.so python bench.py ...
 
-    python tools/ab_build.py novel64 -DBRS_VEL64=0
+    python tools/ab_build.py nocoupled -DBRS_NO_COUPLED
 """
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
