@@ -9,11 +9,15 @@ include/brs.h (libbrs_hip.so).  This package is the host-side mirror of the refe
     BatchedSim                             zero-copy torch-tensor interface to the kernels
     policy.DevicePolicy / DeviceRollout    SB3 MlpPolicy forward + sampling, time-limit bootstrap and GAE as HIP kernels
                                            (include/brs_policy.h): the rollout side of sb_rl.py:63-71, 552-556 on the GPU
+    quant.quantize_policy / QuantPolicy    int8 post-training quantisation of the actor and the int8 network as a HIP kernel
+                                           (include/brs_qpolicy.h): quantize_tflite.py and sb_rl.py:285-364 on the GPU
 
 There is no CPU fallback: creating a sim without a HIP device raises.
 """
 from .registry import ENV_SPECS, make_vec, spec  # noqa: F401
+from .quant import REFERENCE_CALIBRATION, QuantModel, QuantPolicy, quantize_policy  # noqa: F401
 from .sim import BatchedSim, BrsError  # noqa: F401
 from .vec_env import BalanceVecEnv  # noqa: F401
 
-__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "ENV_SPECS", "make_vec", "spec"]
+__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "ENV_SPECS", "QuantModel", "QuantPolicy", "REFERENCE_CALIBRATION", "make_vec",
+           "quantize_policy", "spec"]

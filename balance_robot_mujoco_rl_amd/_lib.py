@@ -14,6 +14,9 @@ HEADERS = [os.path.join(_PKG, "csrc", h) for h in ("brs_core.hpp", "brs_model.hp
 # the renderer (include/brs_render.h) is built into the same library but stays out of the build id, which identifies the
 # step and policy kernels that committed profiles were measured on
 HEADERS_RENDER = [os.path.join(_PKG, "csrc", "brs_render.hpp"), os.path.join(os.path.dirname(_PKG), "include", "brs_render.h")]
+# the int8 actor (include/brs_qpolicy.h): same library, out of the build id for the same reason
+SRC_QPOLICY = os.path.join(_PKG, "csrc", "brs_qpolicy.hip")
+HEADERS_QPOLICY = [os.path.join(_PKG, "csrc", "brs_qpolicy.hpp"), os.path.join(os.path.dirname(_PKG), "include", "brs_qpolicy.h")]
 
 # every symbol include/brs.h declares
 SYMBOLS = ["brs_create", "brs_destroy", "brs_last_error", "brs_sizes", "brs_reset", "brs_step", "brs_physics",
@@ -24,6 +27,9 @@ SYMBOLS = ["brs_create", "brs_destroy", "brs_last_error", "brs_sizes", "brs_rese
            "brs_policy_use_device_weights", "brs_policy_act", "brs_policy_value", "brs_rollout_bootstrap", "brs_gae"]
 # every symbol include/brs_render.h declares
 RENDER_SYMBOLS = ["brs_render_default_camera", "brs_render", "brs_render_last_error"]
+# every symbol include/brs_qpolicy.h declares
+QPOLICY_SYMBOLS = ["brs_qpolicy_create", "brs_qpolicy_destroy", "brs_qpolicy_last_error", "brs_qpolicy_quantize_multiplier",
+                   "brs_qpolicy_set_model", "brs_qpolicy_act"]
 POLICY_NPARAM = (64 * 6 + 64 + 64 * 64 + 64 + 2 * 64 + 2) + (64 * 6 + 64 + 64 * 64 + 64 + 64 + 1) + 2
 
 
@@ -36,6 +42,15 @@ class BrsConfig(C.Structure):
 class BrsCamera(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fovy_deg", C.c_float), ("distance", C.c_float),
                 ("azimuth_deg", C.c_float), ("elevation_deg", C.c_float)]
+
+
+class BrsQLayer(C.Structure):
+    _fields_ = [("n_in", C.c_int32), ("n_out", C.c_int32), ("weight", C.c_void_p), ("bias", C.c_void_p), ("bias_scale", C.c_void_p),
+                ("out_scale", C.c_double), ("out_zero", C.c_int32), ("tanh_zero", C.c_int32), ("tanh_table", C.c_void_p)]
+
+
+class BrsQModel(C.Structure):
+    _fields_ = [("input_scale", C.c_double), ("input_zero", C.c_int32), ("reserved", C.c_int32), ("layer", BrsQLayer * 3)]
 
 
 FLAG_AUTO_RESET, FLAG_NOISE_ON, FLAG_NOISE_OFF, FLAG_NO_LANE_GROUPING = 1, 2, 4, 8
@@ -51,7 +66,7 @@ def hipcc_path():
 def build(force=False, verbose=False, out=None, extra_flags=()):
     """compile the HIP kernels + C ABI for gfx950 in-tree (hipcc cross-compiles without a GPU).  `out` / `extra_flags`: an A/B
     build next to the product library (tools/ab_build.py; loaded only when BRS_HIP_LIB points at it)"""
-    srcs = [SRC, SRC_POLICY, SRC_RENDER] + HEADERS + HEADERS_RENDER
+    srcs = [SRC, SRC_POLICY, SRC_RENDER, SRC_QPOLICY] + HEADERS + HEADERS_RENDER + HEADERS_QPOLICY
     if out is not None:
         return _compile(out, verbose, list(extra_flags), tag="_" + os.path.splitext(os.path.basename(out))[0])
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -91,7 +106,10 @@ def _compile(lib_path, verbose, extra_flags, tag):
     # renderer: IEEE math, like its host build in tests/renderhost that the CPU tests compare with the numpy reference
     obj_ren = os.path.join(_PKG, "csrc", f"brs_render{tag}.o")
     subprocess.check_call(base + (["-Rpass-analysis=kernel-resource-usage"] if verbose else []) + ["-c", "-o", obj_ren, SRC_RENDER])
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path, obj_sim, obj_pol, obj_ren])
+    # int8 actor: IEEE math (the fp64 division and the NaN test of its input quantiser), like its host build in tests/qpolicyhost
+    obj_qp = os.path.join(_PKG, "csrc", f"brs_qpolicy{tag}.o")
+    subprocess.check_call(base + (["-Rpass-analysis=kernel-resource-usage"] if verbose else []) + ["-c", "-o", obj_qp, SRC_QPOLICY])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path, obj_sim, obj_pol, obj_ren, obj_qp])
     return lib_path
 
 
@@ -145,6 +163,13 @@ def lib():
     L.brs_render.argtypes = [i32, i32, i32, vp, C.POINTER(BrsCamera), vp, vp, vp, vp]
     L.brs_render_last_error.argtypes = []
     L.brs_render_last_error.restype = C.c_char_p
+    L.brs_qpolicy_create.argtypes = [i32, C.POINTER(vp)]
+    L.brs_qpolicy_destroy.argtypes = [vp]
+    L.brs_qpolicy_last_error.argtypes = [vp]
+    L.brs_qpolicy_last_error.restype = C.c_char_p
+    L.brs_qpolicy_quantize_multiplier.argtypes = [C.c_double, C.POINTER(i32), C.POINTER(i32)]
+    L.brs_qpolicy_set_model.argtypes = [vp, C.POINTER(BrsQModel)]
+    L.brs_qpolicy_act.argtypes = [vp, i32, vp, vp, vp, vp]
     _lib = L
     return L
 

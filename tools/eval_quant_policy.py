@@ -1,0 +1,78 @@
+#!/usr/bin/env python3
+"""Does a policy survive int8?  The reference answers this with its `test-tflite-quant` command (src/sb_rl.py:285-364): one
+env, the TFLite interpreter, a person watching the viewer.  This tool runs the same deployment check on a registered id of
+THIS simulator for thousands of envs without leaving the GPU: once with the float network (DevicePolicy, deterministic) and
+once with the int8 network (QuantPolicy, the bit-exact integer kernel of include/brs_qpolicy.h), same seed, and prints the
+episode statistics of tools/eval_reference_policy.py for both, then their differences.  Both runs apply the network's raw
+output, unclipped, as the reference does (envs/RobotMoveBaseEnv.py:178-208).
+
+    python tools/eval_quant_policy.py --env Env01-v3 --envs 4096 --steps 1500                    # the reference's own export
+    python tools/eval_quant_policy.py --env Env03-v2 --params policy.npy --save policy_int8.npz  # a policy trained here
+
+--npz PATH     an int8 export in the key set of tests/golden/robot_move_policy.npz (default: that file); the float run uses
+               its dequantised weights
+--params PATH  a float parameter vector (.npy, the order of include/brs_policy.h): quantised here with quantize_policy and
+               the reference's calibration rows; the float run uses the vector itself
+"""
+import argparse, json, os, sys
+import numpy as np
+import torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from balance_robot_mujoco_rl_amd import BatchedSim, QuantModel, QuantPolicy, _lib, quantize_policy  # noqa: E402
+from balance_robot_mujoco_rl_amd.policy import DevicePolicy  # noqa: E402
+
+FIXTURE = os.path.join(ROOT, "tests", "golden", "robot_move_policy.npz")
+
+
+def evaluate(env, n, steps, act, seed=123):
+    """deterministic evaluation with auto-reset; act(obs, t) -> actions [n, 2]"""
+    sim = BatchedSim(env, n, device=0, seed=seed, auto_reset=True)
+    obs = sim.reset().clone()
+    ep_len = torch.zeros(n, device=sim.device); lens = []; ntr = nte = 0
+    ever = torch.zeros(n, dtype=torch.bool, device=sim.device)
+    ret = torch.zeros(n, device=sim.device); total_reward = 0.0
+    for t in range(steps):
+        o, r, te, tr, _ = sim.step(act(obs, t))
+        ep_len += 1; ret += r
+        done = (te | tr).bool()
+        if done.any():
+            lens.append(ep_len[done].clone()); ntr += int((tr.bool() & ~te.bool()).sum()); nte += int(te.bool().sum()); ep_len[done] = 0; ever |= done
+        obs = o.clone()
+    total_reward = float(ret.sum()) / (n * steps)
+    lens = torch.cat(lens) if lens else torch.zeros(0)
+    sim.close()
+    return dict(episodes=int(lens.numel()), first_episode_still_running=int((~ever).sum()), fell=nte, reached_time_limit=ntr,
+                mean_ep_len=float(lens.mean()) if lens.numel() else None, median_ep_len=float(lens.median()) if lens.numel() else None,
+                mean_reward_per_step=total_reward)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--env", default="Env01-v3"); ap.add_argument("--envs", type=int, default=4096); ap.add_argument("--steps", type=int, default=1500)
+    src = ap.add_mutually_exclusive_group()
+    src.add_argument("--npz"); src.add_argument("--params")
+    ap.add_argument("--head", choices=("mean", "actions"), default="mean")
+    ap.add_argument("--save", help="write the int8 model that was evaluated to this .npz")
+    a = ap.parse_args()
+    if a.params:
+        flat = np.load(a.params).astype(np.float32).ravel()
+        qm, what = quantize_policy(flat), f"{os.path.basename(a.params)} (quantised here)"
+    else:
+        qm = QuantModel.load(a.npz or FIXTURE, a.head)
+        flat, what = qm.float_params(), f"{os.path.basename(a.npz or FIXTURE)} ({a.head} output)"
+    if a.save:
+        qm.save(a.save)
+    fpol = DevicePolicy(device=0); fpol.set_weights(flat)
+    qpol = QuantPolicy(qm, device=0)
+    common = dict(env=a.env, envs=a.envs, steps=a.steps, policy=what, build_id=_lib.build_id())
+    f = evaluate(a.env, a.envs, a.steps, lambda obs, t: fpol.act(obs, t, deterministic=True)[0])
+    print(json.dumps(dict(common, network="float (DevicePolicy, deterministic)", **f)))
+    q = evaluate(a.env, a.envs, a.steps, lambda obs, t: qpol.act(obs))
+    print(json.dumps(dict(common, network="int8 (QuantPolicy)", **q)))
+    diff = {k: (None if f[k] is None or q[k] is None else q[k] - f[k]) for k in f}
+    print(json.dumps(dict(common, network="int8 - float", **diff)))
+
+
+if __name__ == "__main__":
+    main()
