@@ -1,35 +1,34 @@
 """ctypes binding of libbrs_hip.so (C ABI: include/brs.h).  Loading never needs a GPU; brs_create does."""
 import ctypes as C
+import glob
 import hashlib
 import os
 import subprocess
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libbrs_hip.so")
-SRC = os.path.join(_PKG, "csrc", "brs_kernels.hip")
-SRC_POLICY = os.path.join(_PKG, "csrc", "brs_policy.hip")
-SRC_RENDER = os.path.join(_PKG, "csrc", "brs_render.hip")
-HEADERS = [os.path.join(_PKG, "csrc", h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp")] + \
-          [os.path.join(os.path.dirname(_PKG), "include", h) for h in ("brs.h", "brs_policy.h")]
-# the renderer (include/brs_render.h) is built into the same library but stays out of the build id, which identifies the
-# step and policy kernels that committed profiles were measured on
-HEADERS_RENDER = [os.path.join(_PKG, "csrc", "brs_render.hpp"), os.path.join(os.path.dirname(_PKG), "include", "brs_render.h")]
-# the int8 actor (include/brs_qpolicy.h): same library, out of the build id for the same reason
-SRC_QPOLICY = os.path.join(_PKG, "csrc", "brs_qpolicy.hip")
-HEADERS_QPOLICY = [os.path.join(_PKG, "csrc", "brs_qpolicy.hpp"), os.path.join(os.path.dirname(_PKG), "include", "brs_qpolicy.h")]
+_CSRC, _INCLUDE = os.path.join(_PKG, "csrc"), os.path.join(os.path.dirname(_PKG), "include")
+BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
+# step kernels: -ffast-math on the DEVICE side only (the host-side state conversion keeps IEEE semantics): no IEEE
+# division/sqrt expansions and free reassociation inside the fp32 force path (parity budget is 1e-4, rounding noise 1e-7);
+# NaN detection in the kernel is done on the bit pattern.
+SIM_FLAGS = ["-Xarch_device", "-ffast-math", "-Xarch_device", "-fgpu-flush-denormals-to-zero",
+             # the dense algebra is packed by hand (V2 -> v_pk_fma_f32); the SLP vectoriser's extra packing of the scalar
+             # code only adds pack/unpack moves (measured: +13 % env-steps/s without it)
+             "-Xarch_device", "-fno-slp-vectorize",
+             # one wave per SIMD at 512 registers: there is no occupancy to protect, yet the default strategy schedules
+             # for register pressure and leaves serial chains (a dependent VALU instruction issues ~1.7x slower than
+             # an independent one for a lone wave).  The ILP strategy: +4.3 % Env03, +2.7 % Env01 (same-box A/B)
+             "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
+# the translation units of libbrs_hip.so: (source, its own flags, in the build id).  Policy / GAE kernels, renderer and int8 actor
+# keep IEEE math (checked against fp32 torch at rtol 1e-5 / bit for bit against their host builds under tests/); the build id
+# names the step and policy kernels that committed profiles were measured on, so the other two units stay out of it.
+UNITS = [("brs_kernels.hip", SIM_FLAGS, True), ("brs_policy.hip", [], True), ("brs_render.hip", [], False), ("brs_qpolicy.hip", [], False)]
+SRC = os.path.join(_CSRC, UNITS[0][0])  # the unit that takes the A/B flags and the build id stamp
+# what the build id hashes next to the sources of its units; brs_host.hpp holds no kernel code and stays out of it
+HEADERS = [os.path.join(_CSRC, h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp")] + \
+          [os.path.join(_INCLUDE, h) for h in ("brs.h", "brs_policy.h")]
 
-# every symbol include/brs.h declares
-SYMBOLS = ["brs_create", "brs_destroy", "brs_last_error", "brs_sizes", "brs_reset", "brs_step", "brs_physics",
-           "brs_get_state", "brs_set_state", "brs_get_aux", "brs_set_aux", "brs_get_xpose", "brs_set_xpose",
-           "brs_step_bytes_per_env", "brs_step_kernel_name", "brs_build_id",
-           # include/brs_policy.h
-           "brs_policy_create", "brs_policy_destroy", "brs_policy_last_error", "brs_policy_set_weights",
-           "brs_policy_use_device_weights", "brs_policy_act", "brs_policy_value", "brs_rollout_bootstrap", "brs_gae"]
-# every symbol include/brs_render.h declares
-RENDER_SYMBOLS = ["brs_render_default_camera", "brs_render", "brs_render_last_error"]
-# every symbol include/brs_qpolicy.h declares
-QPOLICY_SYMBOLS = ["brs_qpolicy_create", "brs_qpolicy_destroy", "brs_qpolicy_last_error", "brs_qpolicy_quantize_multiplier",
-                   "brs_qpolicy_set_model", "brs_qpolicy_act"]
 POLICY_NPARAM = (64 * 6 + 64 + 64 * 64 + 64 + 2 * 64 + 2) + (64 * 6 + 64 + 64 * 64 + 64 + 64 + 1) + 2
 
 
@@ -66,52 +65,88 @@ def hipcc_path():
 def build(force=False, verbose=False, out=None, extra_flags=()):
     """compile the HIP kernels + C ABI for gfx950 in-tree (hipcc cross-compiles without a GPU).  `out` / `extra_flags`: an A/B
     build next to the product library (tools/ab_build.py; loaded only when BRS_HIP_LIB points at it)"""
-    srcs = [SRC, SRC_POLICY, SRC_RENDER, SRC_QPOLICY] + HEADERS + HEADERS_RENDER + HEADERS_QPOLICY
     if out is not None:
         return _compile(out, verbose, list(extra_flags), tag="_" + os.path.splitext(os.path.basename(out))[0])
+    srcs = glob.glob(os.path.join(_CSRC, "*.h*")) + glob.glob(os.path.join(_INCLUDE, "*.h"))  # every .hip, .hpp and ABI header
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if not (force or stale):
         return LIB_PATH
     return _compile(LIB_PATH, verbose, [], tag="")
 
 
-def _compile(lib_path, verbose, extra_flags, tag):
-    hipcc = hipcc_path()
-    base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
-    # step kernels: -ffast-math on the DEVICE side only (the host-side state conversion keeps IEEE semantics): no IEEE
-    # division/sqrt expansions and free reassociation inside the fp32 force path (parity budget is 1e-4, rounding noise 1e-7);
-    # NaN detection in the kernel is done on the bit pattern.
-    sim_flags = ["-Xarch_device", "-ffast-math", "-Xarch_device", "-fgpu-flush-denormals-to-zero",
-                 # the dense algebra is packed by hand (V2 -> v_pk_fma_f32); the SLP vectoriser's extra packing of the scalar
-                 # code only adds pack/unpack moves (measured: +13 % env-steps/s without it)
-                 "-Xarch_device", "-fno-slp-vectorize",
-                 # one wave per SIMD at 512 registers: there is no occupancy to protect, yet the default strategy schedules
-                 # for register pressure and leaves serial chains (a dependent VALU instruction issues ~1.7x slower than
-                 # an independent one for a lone wave).  The ILP strategy: +4.3 % Env03, +2.7 % Env01 (same-box A/B)
-                 "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
-    sim_flags += os.environ.get("BRS_EXTRA_HIPCC_FLAGS", "").split()  # builds with a compile-time switch (DESIGN.md 5.5, e.g. -DBRS_NO_COUPLED); not for production
-    sim_flags += extra_flags
-    if verbose:
-        sim_flags.append("-Rpass-analysis=kernel-resource-usage")
-    obj_sim, obj_pol = os.path.join(_PKG, "csrc", f"brs_kernels{tag}.o"), os.path.join(_PKG, "csrc", f"brs_policy{tag}.o")
-    # build id = hash of every source the library is made from + the flags: ties a committed rocprof summary to the code that ran
+def _build_id(sim_flags):
+    """hash of every source of the step and policy kernels + the flags: ties a committed rocprof summary to the code that ran"""
     hsh = hashlib.sha256()
-    for f in sorted([SRC, SRC_POLICY] + HEADERS):
+    for f in sorted([os.path.join(_CSRC, u[0]) for u in UNITS if u[2]] + HEADERS):
         hsh.update(open(f, "rb").read())
-    hsh.update(" ".join(base[1:] + [a for a in sim_flags if not a.startswith("-Rpass")]).encode())
-    sim_flags = sim_flags + [f'-DBRS_BUILD_ID="{hsh.hexdigest()[:16]}"']
-    subprocess.check_call(base + sim_flags + ["-c", "-o", obj_sim, SRC])
-    # policy / GAE kernels: IEEE math (tanh, exp, log at libm accuracy): the parity test is rtol 1e-5 against fp32 torch
-    subprocess.check_call(base + ["-c", "-o", obj_pol, SRC_POLICY])
-    # renderer: IEEE math, like its host build in tests/renderhost that the CPU tests compare with the numpy reference
-    obj_ren = os.path.join(_PKG, "csrc", f"brs_render{tag}.o")
-    subprocess.check_call(base + (["-Rpass-analysis=kernel-resource-usage"] if verbose else []) + ["-c", "-o", obj_ren, SRC_RENDER])
-    # int8 actor: IEEE math (the fp64 division and the NaN test of its input quantiser), like its host build in tests/qpolicyhost
-    obj_qp = os.path.join(_PKG, "csrc", f"brs_qpolicy{tag}.o")
-    subprocess.check_call(base + (["-Rpass-analysis=kernel-resource-usage"] if verbose else []) + ["-c", "-o", obj_qp, SRC_QPOLICY])
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path, obj_sim, obj_pol, obj_ren, obj_qp])
+    hsh.update(" ".join(BASE_FLAGS + [a for a in sim_flags if not a.startswith("-Rpass")]).encode())
+    return hsh.hexdigest()[:16]
+
+
+def _compile(lib_path, verbose, extra_flags, tag):
+    hipcc, objs = hipcc_path(), []
+    # BRS_EXTRA_HIPCC_FLAGS: builds with a compile-time switch (DESIGN.md 5.5, e.g. -DBRS_NO_COUPLED); not for production
+    sim_flags = SIM_FLAGS + os.environ.get("BRS_EXTRA_HIPCC_FLAGS", "").split() + extra_flags
+    for name, flags, _ in UNITS:
+        src, obj = os.path.join(_CSRC, name), os.path.join(_CSRC, os.path.splitext(name)[0] + tag + ".o")
+        if src == SRC:
+            flags = sim_flags + [f'-DBRS_BUILD_ID="{_build_id(sim_flags)}"']
+        remarks = ["-Rpass-analysis=kernel-resource-usage"] if verbose else []
+        subprocess.check_call([hipcc] + BASE_FLAGS + flags + remarks + ["-c", "-o", obj, src])
+        objs.append(obj)
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path] + objs)
     return lib_path
 
+
+_vp, _i32, _f32, _dp, _i32p = C.c_void_p, C.c_int32, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_int32)
+# the C ABI, header by header: name -> (restype, argtypes).  lib() applies it; tests/test_c_abi.py holds it against the headers
+SIGNATURES = {
+    "brs.h": {
+        "brs_create": (C.c_int, [C.POINTER(BrsConfig), C.POINTER(_vp)]),
+        "brs_destroy": (C.c_int, [_vp]),
+        "brs_last_error": (C.c_char_p, [_vp]),
+        "brs_sizes": (C.c_int, [_i32, _i32p, _i32p, _i32p, _i32p]),
+        "brs_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
+        "brs_step": (C.c_int, [_vp] * 8),
+        "brs_physics": (C.c_int, [_vp, _vp, _i32, _vp]),
+        "brs_get_state": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
+        "brs_set_state": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
+        "brs_get_aux": (C.c_int, [_vp, _dp]),
+        "brs_set_aux": (C.c_int, [_vp, _dp]),
+        "brs_get_xpose": (C.c_int, [_vp, _dp, _dp]),
+        "brs_set_xpose": (C.c_int, [_vp, _dp, _dp]),
+        "brs_step_bytes_per_env": (C.c_int64, [_vp]),
+        "brs_step_kernel_name": (C.c_char_p, [_vp]),
+        "brs_build_id": (C.c_char_p, []),
+    },
+    "brs_policy.h": {
+        "brs_policy_create": (C.c_int, [_i32, C.POINTER(_vp)]),
+        "brs_policy_destroy": (C.c_int, [_vp]),
+        "brs_policy_last_error": (C.c_char_p, [_vp]),
+        "brs_policy_set_weights": (C.c_int, [_vp, C.POINTER(C.c_float)]),
+        "brs_policy_use_device_weights": (C.c_int, [_vp, _vp]),
+        "brs_policy_act": (C.c_int, [_vp, _i32, _vp, C.c_uint64, C.c_int64, C.c_uint32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "brs_policy_value": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+        "brs_rollout_bootstrap": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
+        "brs_gae": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp]),
+    },
+    "brs_render.h": {
+        "brs_render_default_camera": (None, [C.POINTER(BrsCamera)]),
+        "brs_render": (C.c_int, [_i32, _i32, _i32, _vp, C.POINTER(BrsCamera), _vp, _vp, _vp, _vp]),
+        "brs_render_last_error": (C.c_char_p, []),
+    },
+    "brs_qpolicy.h": {
+        "brs_qpolicy_create": (C.c_int, [_i32, C.POINTER(_vp)]),
+        "brs_qpolicy_destroy": (C.c_int, [_vp]),
+        "brs_qpolicy_last_error": (C.c_char_p, [_vp]),
+        "brs_qpolicy_quantize_multiplier": (C.c_int, [C.c_double, _i32p, _i32p]),
+        "brs_qpolicy_set_model": (C.c_int, [_vp, C.POINTER(BrsQModel)]),
+        "brs_qpolicy_act": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    },
+}
+SYMBOLS = list(SIGNATURES["brs.h"]) + list(SIGNATURES["brs_policy.h"])
+RENDER_SYMBOLS = list(SIGNATURES["brs_render.h"])
+QPOLICY_SYMBOLS = list(SIGNATURES["brs_qpolicy.h"])
 
 _lib = None
 
@@ -126,50 +161,10 @@ def lib():
         raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     L = C.CDLL(path)
-    vp, dp, fp, u8p = C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p
-    L.brs_create.argtypes = [C.POINTER(BrsConfig), C.POINTER(vp)]
-    L.brs_destroy.argtypes = [vp]
-    L.brs_last_error.argtypes = [vp]
-    L.brs_last_error.restype = C.c_char_p
-    L.brs_sizes.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 4
-    L.brs_reset.argtypes = [vp, u8p, fp, vp]
-    L.brs_step.argtypes = [vp, fp, fp, fp, u8p, u8p, fp, vp]
-    L.brs_physics.argtypes = [vp, fp, C.c_int32, vp]
-    L.brs_get_state.argtypes = [vp, dp, dp, dp, dp]
-    L.brs_set_state.argtypes = [vp, dp, dp, dp, dp]
-    L.brs_get_aux.argtypes = [vp, dp]
-    L.brs_set_aux.argtypes = [vp, dp]
-    L.brs_get_xpose.argtypes = [vp, dp, dp]
-    L.brs_set_xpose.argtypes = [vp, dp, dp]
-    L.brs_step_bytes_per_env.argtypes = [vp]
-    L.brs_step_bytes_per_env.restype = C.c_int64
-    L.brs_step_kernel_name.argtypes = [vp]
-    L.brs_step_kernel_name.restype = C.c_char_p
-    L.brs_build_id.argtypes = []
-    L.brs_build_id.restype = C.c_char_p
-    i32, u64, i64, u32, f32 = C.c_int32, C.c_uint64, C.c_int64, C.c_uint32, C.c_float
-    L.brs_policy_create.argtypes = [i32, C.POINTER(vp)]
-    L.brs_policy_destroy.argtypes = [vp]
-    L.brs_policy_last_error.argtypes = [vp]
-    L.brs_policy_last_error.restype = C.c_char_p
-    L.brs_policy_set_weights.argtypes = [vp, C.POINTER(C.c_float)]
-    L.brs_policy_use_device_weights.argtypes = [vp, vp]
-    L.brs_policy_act.argtypes = [vp, i32, vp, u64, i64, u32, i32, vp, vp, vp, vp, vp, vp]
-    L.brs_policy_value.argtypes = [vp, i32, vp, vp, vp]
-    L.brs_rollout_bootstrap.argtypes = [vp, i32, vp, vp, vp, f32, vp, vp]
-    L.brs_gae.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp]
-    L.brs_render_default_camera.argtypes = [C.POINTER(BrsCamera)]
-    L.brs_render_default_camera.restype = None
-    L.brs_render.argtypes = [i32, i32, i32, vp, C.POINTER(BrsCamera), vp, vp, vp, vp]
-    L.brs_render_last_error.argtypes = []
-    L.brs_render_last_error.restype = C.c_char_p
-    L.brs_qpolicy_create.argtypes = [i32, C.POINTER(vp)]
-    L.brs_qpolicy_destroy.argtypes = [vp]
-    L.brs_qpolicy_last_error.argtypes = [vp]
-    L.brs_qpolicy_last_error.restype = C.c_char_p
-    L.brs_qpolicy_quantize_multiplier.argtypes = [C.c_double, C.POINTER(i32), C.POINTER(i32)]
-    L.brs_qpolicy_set_model.argtypes = [vp, C.POINTER(BrsQModel)]
-    L.brs_qpolicy_act.argtypes = [vp, i32, vp, vp, vp, vp]
+    for functions in SIGNATURES.values():
+        for name, (restype, argtypes) in functions.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

@@ -1,5 +1,9 @@
 // brs_kernels.hip -- HIP kernels (gfx950 / CDNA4) and the C ABI of include/brs.h.
 //
+// Host side: device guard, error slots and device check are brs_host.hpp's, shared with the library's other three units; every
+// entry point that touches the device constructs the guard and returns BRS_ERR_HIP if it is not `ok`.  What differs between
+// the two model families is one row of FamilyOps, which the handle points to.
+//
 // Kernel design:
 //   * one wavefront LANE per environment instance; a 64-thread workgroup is one wave.  At the benchmark size
 //     (65,536 envs) the grid is 1,024 waves = one wave per SIMD of the 256 CUs, so the register budget is the
@@ -21,6 +25,7 @@
 #include <vector>
 
 #include "../../include/brs.h"
+#include "brs_host.hpp"
 #if defined(BRS_TIMING)
 __device__ unsigned long long brs_dbg[16];
 // per-wave record of the last launch, 16 words per wave (waves 0-1023): phase slots 0-11 (brs_core.hpp: BRS_TIC ids), HW_ID,
@@ -251,14 +256,27 @@ __global__ void __launch_bounds__(GROUP_THREADS) brs_group_kernel(const int N, c
   }
 }
 
-thread_local std::string g_create_error;
+// What the host side has to know about a model family (Env01: robot alone; Env03: robot and block), filled once per family
+// (make_family_ops below): the entry points read the handle's row instead of branching on the family.
+struct FamilyOps {
+  int nq, nv, lds_words;                 // row widths of brs_get_state / brs_set_state; LDS words per lane (step, physics)
+  size_t ND, NF, NI, bytes_per_env;      // state fields per env (fp64, fp32, int32) and their size
+  const void *reset_kernel, *physics_kernel;
+  // brs_state.hpp: the conversions between MuJoCo-style rows and the device layout (same signatures in both families)
+  decltype(&hostconv::init_state<true, float>) init_state;
+  decltype(&hostconv::mark_bad_start<true, float>) mark_bad_start;
+  decltype(&hostconv::get_state<true, float>) get_state;   decltype(&hostconv::set_state<true, float>) set_state;
+  decltype(&hostconv::get_aux<true, float>) get_aux;       decltype(&hostconv::set_aux<true, float>) set_aux;
+  decltype(&hostconv::get_xpose<true>) get_xpose;          decltype(&hostconv::set_xpose<true>) set_xpose;
+};
 
 }  // namespace
 
 struct brs_handle {
   Params<float> P;
   int N = 0, device = 0, bt = 64;
-  bool blk = false;
+  const FamilyOps* ops = nullptr;
+  bool blk = false;          // Env03 family: the step kernel maintains the lane map and the bucket counters
   double* d = nullptr;
   float* f = nullptr;
   int* ii = nullptr;
@@ -275,34 +293,18 @@ struct brs_handle {
 
 namespace {
 
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-int fail(brs_handle* h, int code, const std::string& msg) {
-  if (h) h->err = msg; else g_create_error = msg;
-  return code;
-}
-#define BRS_HIP_TRY(h, expr)                                                                              \
-  do {                                                                                                    \
-    hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess) return fail(h, BRS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
+using host::DeviceGuard, host::fail;  // fail<brs_handle>(nullptr, ...): the error of a failed brs_create
 #if defined(BRS_TIMING)
 size_t lds_bytes(const brs_handle* h) { return (size_t)h->bt * BRS_TIMING_LANE_WORDS * sizeof(float) + (size_t)(h->bt / 64) * 128; }
 #else
-size_t lds_bytes(const brs_handle* h) { return (size_t)h->bt * (h->blk ? LDS_WORDS_ENV03 : LDS_WORDS_ENV01) * sizeof(float); }
+size_t lds_bytes(const brs_handle* h) { return (size_t)h->bt * h->ops->lds_words * sizeof(float); }
 #endif
-int grid_of(const brs_handle* h) { return (h->N + h->bt - 1) / h->bt; }
+// one lane per env, workgroups of the handle's size; the launch's status is what hipGetLastError returns
+int launch_per_env(brs_handle* h, const void* kernel, void** args, size_t lds, void* stream) {
+  (void)hipLaunchKernel(kernel, dim3((h->N + h->bt - 1) / h->bt), dim3(h->bt), args, lds, (hipStream_t)stream);
+  BRS_HIP_TRY(h, hipGetLastError());
+  return BRS_OK;
+}
 
 // every step-kernel instantiation there is: brs_create prepares a handle's rows, brs_step launches the one step_kernel_of selects
 struct StepKernel { bool blk, occ2; int variant; const void* fn; };
@@ -331,19 +333,37 @@ const StepKernel* step_kernel_of(const brs_handle* h) {
   return nullptr;
 }
 
-template <bool BLK> int upload_state(brs_handle* h, const std::vector<double>& d, const std::vector<float>& f, const std::vector<int>& ii) {
+// The reset and physics kernels, Env03 family first.  Like STEP_KERNELS this names its kernels for the first time, and the order
+// of first mention is the order the device code is emitted in: keep it, and a build's device code can be compared with its parent's.
+const void* const PHYSICS_KERNELS[] = {(const void*)brs_physics_kernel<true>, (const void*)brs_physics_kernel<false>};
+const void* const RESET_KERNELS[] = {(const void*)brs_reset_kernel<true>, (const void*)brs_reset_kernel<false>};
+
+template <bool BLK> FamilyOps make_family_ops() {
+  using L = Layout<BLK>;
+  return {L::NQ, L::NV, lane_words<BLK>(), L::ND, L::NF, L::NI, L::bytes_per_env, RESET_KERNELS[BLK ? 0 : 1], PHYSICS_KERNELS[BLK ? 0 : 1],
+          hostconv::init_state<BLK, float>, hostconv::mark_bad_start<BLK, float>, hostconv::get_state<BLK, float>, hostconv::set_state<BLK, float>,
+          hostconv::get_aux<BLK, float>, hostconv::set_aux<BLK, float>, hostconv::get_xpose<BLK>, hostconv::set_xpose<BLK>};
+}
+const FamilyOps FAMILY_OPS[] = {make_family_ops<false>(), make_family_ops<true>()};  // [has_block]
+
+int upload_state(brs_handle* h, const std::vector<double>& d, const std::vector<float>& f, const std::vector<int>& ii) {
   BRS_HIP_TRY(h, hipMemcpy(h->d, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice));
   BRS_HIP_TRY(h, hipMemcpy(h->f, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
   BRS_HIP_TRY(h, hipMemcpy(h->ii, ii.data(), ii.size() * sizeof(int), hipMemcpyHostToDevice));
   return BRS_OK;
 }
-int download_state(brs_handle* h, std::vector<double>& d, std::vector<float>& f, std::vector<int>& ii) {
-  d.resize(h->nd); f.resize(h->nf); ii.resize(h->ni);
+// the state accessors: copy the state to the host, let `edit(d, f, ii, N)` read or change the copy, copy it back if `write`
+template <class Edit> int state_roundtrip(brs_handle* h, const char* who, bool write, Edit edit) {
+  if (!h) return BRS_ERR_STATE;
+  DeviceGuard g(h->device);
+  if (!g.ok) return fail(h, BRS_ERR_HIP, std::string(who) + ": hipSetDevice failed");
+  std::vector<double> d(h->nd); std::vector<float> f(h->nf); std::vector<int> ii(h->ni);
   BRS_HIP_TRY(h, hipDeviceSynchronize());
   BRS_HIP_TRY(h, hipMemcpy(d.data(), h->d, h->nd * sizeof(double), hipMemcpyDeviceToHost));
   BRS_HIP_TRY(h, hipMemcpy(f.data(), h->f, h->nf * sizeof(float), hipMemcpyDeviceToHost));
   BRS_HIP_TRY(h, hipMemcpy(ii.data(), h->ii, h->ni * sizeof(int), hipMemcpyDeviceToHost));
-  return BRS_OK;
+  edit(d.data(), f.data(), ii.data(), (size_t)h->N);
+  return write ? upload_state(h, d, f, ii) : BRS_OK;
 }
 
 }  // namespace
@@ -351,51 +371,44 @@ int download_state(brs_handle* h, std::vector<double>& d, std::vector<float>& f,
 extern "C" {
 
 int brs_sizes(int32_t variant, int32_t* nq, int32_t* nv, int32_t* nobs, int32_t* nact) {
-  if (variant < 0 || variant > 5) return BRS_ERR_ARG;
-  bool blk = variant == 2 || variant == 3;
-  if (nq) *nq = blk ? 16 : 9;
-  if (nv) *nv = blk ? 14 : 8;
+  if (!host::known_variant(variant)) return BRS_ERR_ARG;
+  const FamilyOps* ops = &FAMILY_OPS[host::has_block(variant)];
+  if (nq) *nq = ops->nq;
+  if (nv) *nv = ops->nv;
   if (nobs) *nobs = 6;
   if (nact) *nact = 2;
   return BRS_OK;
 }
 
 int brs_create(const brs_config* cfg, brs_handle** out) {
-  if (!cfg || !out) return fail(nullptr, BRS_ERR_ARG, "brs_create: null argument");
+  if (!cfg || !out) return fail<brs_handle>(nullptr, BRS_ERR_ARG, "brs_create: null argument");
   *out = nullptr;
-  if (cfg->variant < 0 || cfg->variant > 5) return fail(nullptr, BRS_ERR_ARG, "brs_create: unknown variant");
-  if (cfg->num_envs <= 0) return fail(nullptr, BRS_ERR_ARG, "brs_create: num_envs must be > 0");
+  if (!host::known_variant(cfg->variant)) return fail<brs_handle>(nullptr, BRS_ERR_ARG, "brs_create: unknown variant");
+  if (cfg->num_envs <= 0) return fail<brs_handle>(nullptr, BRS_ERR_ARG, "brs_create: num_envs must be > 0");
   if ((cfg->flags & BRS_FLAG_NOISE_ON) && (cfg->flags & BRS_FLAG_NOISE_OFF))
-    return fail(nullptr, BRS_ERR_ARG, "brs_create: NOISE_ON and NOISE_OFF are exclusive");
+    return fail<brs_handle>(nullptr, BRS_ERR_ARG, "brs_create: NOISE_ON and NOISE_OFF are exclusive");
   int bt = cfg->block_threads > 0 ? cfg->block_threads : 64;
-  if (bt % 64 != 0 || bt > 256) return fail(nullptr, BRS_ERR_ARG, "brs_create: block_threads must be 64, 128, 192 or 256");
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0)
-    return fail(nullptr, BRS_ERR_HIP, std::string("brs_create: no HIP device (") + hipGetErrorString(e) + "); there is no CPU fallback");
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, BRS_ERR_ARG, "brs_create: device ordinal out of range");
+  if (bt % 64 != 0 || bt > 256) return fail<brs_handle>(nullptr, BRS_ERR_ARG, "brs_create: block_threads must be 64, 128, 192 or 256");
+  std::string why;
+  if (const int rc = host::check_device(cfg->device, "brs_create", &why)) return fail<brs_handle>(nullptr, rc, why);
   brs_handle* h = new brs_handle();
-  h->N = cfg->num_envs; h->device = cfg->device; h->bt = bt; h->blk = cfg->variant == 2 || cfg->variant == 3;
+  h->N = cfg->num_envs; h->device = cfg->device; h->bt = bt;
+  h->ops = &FAMILY_OPS[host::has_block(cfg->variant)]; h->blk = host::has_block(cfg->variant);
   int noise = (cfg->flags & BRS_FLAG_NOISE_ON) ? 1 : ((cfg->flags & BRS_FLAG_NOISE_OFF) ? 0 : -1);
   h->P = make_params<float>(cfg->variant, cfg->flags & BRS_FLAG_AUTO_RESET, noise, cfg->max_episode_steps, cfg->substeps,
                             cfg->timestep, cfg->seed, cfg->env_index_base);
   DeviceGuard g(h->device);
   size_t N = (size_t)h->N;
-  if (h->blk) { h->nd = Layout<true>::ND * N; h->nf = Layout<true>::NF * N; h->ni = Layout<true>::NI * N; }
-  else { h->nd = Layout<false>::ND * N; h->nf = Layout<false>::NF * N; h->ni = Layout<false>::NI * N; }
-  auto bail = [&](const std::string& m) { std::string mm = m; brs_destroy(h); return fail(nullptr, BRS_ERR_HIP, mm); };
+  h->nd = h->ops->ND * N; h->nf = h->ops->NF * N; h->ni = h->ops->NI * N;
+  auto bail = [&](const std::string& m) { std::string mm = m; brs_destroy(h); return fail<brs_handle>(nullptr, BRS_ERR_HIP, mm); };
   if (!g.ok) return bail("brs_create: hipSetDevice failed");
   // + 7 fp64 scratch columns addressed by lane slot (accessor pose parked during the last substep, brs_state.hpp: LaneIndex)
   if (hipMalloc(&h->d, (h->nd + 7 * N) * sizeof(double)) != hipSuccess) return bail("brs_create: hipMalloc(fp64 state) failed");
   if (hipMalloc(&h->f, h->nf * sizeof(float)) != hipSuccess) return bail("brs_create: hipMalloc(fp32 state) failed");
   if (hipMalloc(&h->ii, (h->ni + 2 * N + GROUP_WORDS) * sizeof(int)) != hipSuccess) return bail("brs_create: hipMalloc(int state) failed");
-  std::vector<double> d(h->nd);
-  std::vector<float> f(h->nf);
-  std::vector<int> ii(h->ni);
-  int rc;
-  if (h->blk) { hostconv::init_state<true>(d.data(), f.data(), ii.data(), N, cfg->seed, cfg->env_index_base); rc = upload_state<true>(h, d, f, ii); }
-  else { hostconv::init_state<false>(d.data(), f.data(), ii.data(), N, cfg->seed, cfg->env_index_base); rc = upload_state<false>(h, d, f, ii); }
-  if (rc != BRS_OK) return bail("brs_create: initial upload failed: " + h->err);
+  std::vector<double> d(h->nd); std::vector<float> f(h->nf); std::vector<int> ii(h->ni);
+  h->ops->init_state(d.data(), f.data(), ii.data(), N, cfg->seed, cfg->env_index_base);
+  if (upload_state(h, d, f, ii) != BRS_OK) return bail("brs_create: initial upload failed: " + h->err);
   {  // lane map = identity until the first regrouping (always read by the Env03 step kernel)
     std::vector<int> id(2 * N, 0);
     for (size_t k = 0; k < N; k++) id[k] = (int)k;
@@ -415,7 +428,7 @@ int brs_create(const brs_config* cfg, brs_handle** out) {
   if (!step_kernel_of(h)) return bail("brs_create: no step kernel for this variant");
   for (const StepKernel& k : STEP_KERNELS)
     if (k.blk == h->blk) want(k.fn);
-  want(h->blk ? (const void*)brs_physics_kernel<true> : (const void*)brs_physics_kernel<false>);
+  want(h->ops->physics_kernel);
   if (ea != hipSuccess) return bail(std::string("brs_create: hipFuncSetAttribute: ") + hipGetErrorString(ea));
   *out = h;
   return BRS_OK;
@@ -433,17 +446,15 @@ int brs_destroy(brs_handle* h) {
   return BRS_OK;
 }
 
-const char* brs_last_error(const brs_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+const char* brs_last_error(const brs_handle* h) { return host::last_error(h); }
 
 int brs_reset(brs_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream) {
   if (!h) return BRS_ERR_STATE;
   if (!obs_dev) return fail(h, BRS_ERR_ARG, "brs_reset: obs_dev is null");
   DeviceGuard g(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  if (h->blk) hipLaunchKernelGGL(brs_reset_kernel<true>, dim3(grid_of(h)), dim3(h->bt), 0, s, h->P, h->N, h->d, h->f, h->ii, mask_dev, obs_dev);
-  else hipLaunchKernelGGL(brs_reset_kernel<false>, dim3(grid_of(h)), dim3(h->bt), 0, s, h->P, h->N, h->d, h->f, h->ii, mask_dev, obs_dev);
-  BRS_HIP_TRY(h, hipGetLastError());
-  return BRS_OK;
+  if (!g.ok) return fail(h, BRS_ERR_HIP, "brs_reset: hipSetDevice failed");
+  void* args[] = {&h->P, &h->N, &h->d, &h->f, &h->ii, &mask_dev, &obs_dev};
+  return launch_per_env(h, h->ops->reset_kernel, args, 0, stream);
 }
 
 int brs_step(brs_handle* h, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* terminated_dev,
@@ -452,20 +463,17 @@ int brs_step(brs_handle* h, const float* actions_dev, float* obs_dev, float* rew
   if (!actions_dev || !obs_dev || !reward_dev || !terminated_dev || !truncated_dev)
     return fail(h, BRS_ERR_ARG, "brs_step: null buffer");
   DeviceGuard g(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  size_t lb = lds_bytes(h);
-  const dim3 grid(grid_of(h)), block(h->bt);
+  if (!g.ok) return fail(h, BRS_ERR_HIP, "brs_step: hipSetDevice failed");
   void* args[] = {&h->P, &h->N, &h->d, &h->f, &h->ii, &actions_dev, &obs_dev, &reward_dev, &terminated_dev, &truncated_dev, &terminal_obs_dev};
-  (void)hipLaunchKernel(step_kernel_of(h)->fn, grid, block, args, lb, s);  // its status is what hipGetLastError returns below
   // a step launch that failed left no bucket counts: the grouping kernel must not run on them (its output would not be a
   // permutation, and later steps would skip or double envs)
-  BRS_HIP_TRY(h, hipGetLastError());
+  if (const int rc = launch_per_env(h, step_kernel_of(h)->fn, args, lds_bytes(h), stream)) return rc;
   if (h->blk) {  // lanes of the NEXT step; without grouping the counts the step kernel left are just cleared
     if (h->grouping) {
-      hipLaunchKernelGGL(brs_group_kernel, dim3((h->N + GROUP_ENVS - 1) / GROUP_ENVS), dim3(GROUP_THREADS), 0, s, h->N, h->keys(), h->perm(), h->counters(), h->wheel_cap);
+      hipLaunchKernelGGL(brs_group_kernel, dim3((h->N + GROUP_ENVS - 1) / GROUP_ENVS), dim3(GROUP_THREADS), 0, (hipStream_t)stream, h->N, h->keys(), h->perm(), h->counters(), h->wheel_cap);
       BRS_HIP_TRY(h, hipGetLastError());
     } else
-      BRS_HIP_TRY(h, hipMemsetAsync(h->counters(), 0, GROUP_WORDS * sizeof(int), s));
+      BRS_HIP_TRY(h, hipMemsetAsync(h->counters(), 0, GROUP_WORDS * sizeof(int), (hipStream_t)stream));
   }
   return BRS_OK;
 }
@@ -474,59 +482,39 @@ int brs_physics(brs_handle* h, const float* ctrl_dev, int32_t nsub, void* stream
   if (!h) return BRS_ERR_STATE;
   if (!ctrl_dev || nsub < 0) return fail(h, BRS_ERR_ARG, "brs_physics: bad argument");
   DeviceGuard g(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  size_t lb = lds_bytes(h);
-  if (h->blk) hipLaunchKernelGGL(brs_physics_kernel<true>, dim3(grid_of(h)), dim3(h->bt), lb, s, h->P, h->N, h->d, h->f, h->ii, ctrl_dev, nsub);
-  else hipLaunchKernelGGL(brs_physics_kernel<false>, dim3(grid_of(h)), dim3(h->bt), lb, s, h->P, h->N, h->d, h->f, h->ii, ctrl_dev, nsub);
-  BRS_HIP_TRY(h, hipGetLastError());
-  return BRS_OK;
+  if (!g.ok) return fail(h, BRS_ERR_HIP, "brs_physics: hipSetDevice failed");
+  void* args[] = {&h->P, &h->N, &h->d, &h->f, &h->ii, &ctrl_dev, &nsub};
+  return launch_per_env(h, h->ops->physics_kernel, args, lds_bytes(h), stream);
 }
-
-#define BRS_STATE_ROUNDTRIP(h, MODIFY_T, MODIFY_F, WRITE)                                   \
-  do {                                                                                     \
-    if (!h) return BRS_ERR_STATE;                                                          \
-    DeviceGuard g(h->device);                                                              \
-    std::vector<double> d; std::vector<float> f; std::vector<int> ii;                      \
-    int rc = download_state(h, d, f, ii);                                                  \
-    if (rc != BRS_OK) return rc;                                                           \
-    size_t N = (size_t)h->N; (void)N;                                                      \
-    if (h->blk) { MODIFY_T; } else { MODIFY_F; }                                           \
-    if (WRITE) { rc = h->blk ? upload_state<true>(h, d, f, ii) : upload_state<false>(h, d, f, ii); } \
-    return rc;                                                                             \
-  } while (0)
 
 int brs_get_state(brs_handle* h, double* qpos, double* qvel, double* warm, double* time) {
-  BRS_STATE_ROUNDTRIP(h, hostconv::get_state<true>(d.data(), f.data(), N, qpos, qvel, warm, time),
-                      hostconv::get_state<false>(d.data(), f.data(), N, qpos, qvel, warm, time), false);
+  return state_roundtrip(h, "brs_get_state", false, [&](double* d, float* f, int*, size_t N) { h->ops->get_state(d, f, N, qpos, qvel, warm, time); });
 }
 int brs_set_state(brs_handle* h, const double* qpos, const double* qvel, const double* warm, const double* time) {
-  BRS_STATE_ROUNDTRIP(h, (hostconv::set_state<true>(d.data(), f.data(), N, qpos, qvel, warm, time),
-                          hostconv::mark_bad_start<true>(d.data(), f.data(), ii.data(), N)),
-                      (hostconv::set_state<false>(d.data(), f.data(), N, qpos, qvel, warm, time),
-                       hostconv::mark_bad_start<false>(d.data(), f.data(), ii.data(), N)), true);
+  return state_roundtrip(h, "brs_set_state", true, [&](double* d, float* f, int* ii, size_t N) {
+    h->ops->set_state(d, f, N, qpos, qvel, warm, time);
+    h->ops->mark_bad_start(d, f, ii, N);
+  });
 }
 int brs_get_aux(brs_handle* h, double* aux) {
   if (!aux) return BRS_ERR_ARG;
-  BRS_STATE_ROUNDTRIP(h, hostconv::get_aux<true>(d.data(), f.data(), ii.data(), N, aux),
-                      hostconv::get_aux<false>(d.data(), f.data(), ii.data(), N, aux), false);
+  return state_roundtrip(h, "brs_get_aux", false, [&](double* d, float* f, int* ii, size_t N) { h->ops->get_aux(d, f, ii, N, aux); });
 }
 int brs_set_aux(brs_handle* h, const double* aux) {
   if (!aux) return BRS_ERR_ARG;
-  BRS_STATE_ROUNDTRIP(h, hostconv::set_aux<true>(d.data(), f.data(), ii.data(), N, aux),
-                      hostconv::set_aux<false>(d.data(), f.data(), ii.data(), N, aux), true);
+  return state_roundtrip(h, "brs_set_aux", true, [&](double* d, float* f, int* ii, size_t N) { h->ops->set_aux(d, f, ii, N, aux); });
 }
 int brs_get_xpose(brs_handle* h, double* xquat, double* xpos) {
-  BRS_STATE_ROUNDTRIP(h, hostconv::get_xpose<true>(d.data(), N, xquat, xpos), hostconv::get_xpose<false>(d.data(), N, xquat, xpos), false);
+  return state_roundtrip(h, "brs_get_xpose", false, [&](double* d, float*, int*, size_t N) { h->ops->get_xpose(d, N, xquat, xpos); });
 }
 int brs_set_xpose(brs_handle* h, const double* xquat, const double* xpos) {
-  BRS_STATE_ROUNDTRIP(h, hostconv::set_xpose<true>(d.data(), N, xquat, xpos), hostconv::set_xpose<false>(d.data(), N, xquat, xpos), true);
+  return state_roundtrip(h, "brs_set_xpose", true, [&](double* d, float*, int*, size_t N) { h->ops->set_xpose(d, N, xquat, xpos); });
 }
 
 int64_t brs_step_bytes_per_env(const brs_handle* h) {
   if (!h) return 0;
-  size_t st = h->blk ? Layout<true>::bytes_per_env : Layout<false>::bytes_per_env;
   // state read + state written + action (8) + obs (24) + terminal obs (24) + reward (4) + two flags (2)
-  return (int64_t)(2 * st + 8 + 24 + 24 + 4 + 2);
+  return (int64_t)(2 * h->ops->bytes_per_env + 8 + 24 + 24 + 4 + 2);
 }
 #if defined(BRS_TIMING)
 // diagnostic builds only: read and clear the per-phase cycle sums

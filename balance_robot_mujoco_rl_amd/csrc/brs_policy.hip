@@ -21,6 +21,7 @@
 
 #include "../../include/brs.h"
 #include "../../include/brs_policy.h"
+#include "brs_host.hpp"
 #include "brs_core.hpp"  // philox4x32_10 (same generator as the simulator)
 
 namespace {
@@ -238,45 +239,22 @@ struct brs_policy {
   std::string err;
 };
 
-namespace {
-thread_local std::string g_policy_create_error;
-int pfail(brs_policy* p, int code, const std::string& m) {
-  if (p) p->err = m; else g_policy_create_error = m;
-  return code;
-}
-struct PGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit PGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~PGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-#define BRS_P_TRY(p, expr)                                                                                 \
-  do {                                                                                                     \
-    hipError_t e_ = (expr);                                                                                \
-    if (e_ != hipSuccess) return pfail(p, BRS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-}  // namespace
+using brs::host::DeviceGuard, brs::host::fail;  // fail<brs_policy>(nullptr, ...): the error of a failed brs_policy_create
 
 extern "C" {
 
 int brs_policy_create(int32_t device, brs_policy** out) {
-  if (!out) return pfail(nullptr, BRS_ERR_ARG, "brs_policy_create: null argument");
+  if (!out) return fail<brs_policy>(nullptr, BRS_ERR_ARG, "brs_policy_create: null argument");
   *out = nullptr;
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0)
-    return pfail(nullptr, BRS_ERR_HIP, std::string("brs_policy_create: no HIP device (") + hipGetErrorString(e) + "); there is no CPU fallback");
-  if (device < 0 || device >= ndev) return pfail(nullptr, BRS_ERR_ARG, "brs_policy_create: device ordinal out of range");
+  std::string why;
+  if (const int rc = brs::host::check_device(device, "brs_policy_create", &why)) return fail<brs_policy>(nullptr, rc, why);
   brs_policy* p = new brs_policy();
   p->device = device;
-  PGuard g(device);
+  DeviceGuard g(device);
   if (!g.ok || hipMalloc(&p->w_own, BRS_POLICY_NPARAM * sizeof(float)) != hipSuccess ||
       hipMemset(p->w_own, 0, BRS_POLICY_NPARAM * sizeof(float)) != hipSuccess) {
     delete p;
-    return pfail(nullptr, BRS_ERR_HIP, "brs_policy_create: device allocation failed");
+    return fail<brs_policy>(nullptr, BRS_ERR_HIP, "brs_policy_create: device allocation failed");
   }
   p->w = p->w_own;
   *out = p;
@@ -286,31 +264,31 @@ int brs_policy_create(int32_t device, brs_policy** out) {
 int brs_policy_destroy(brs_policy* p) {
   if (!p) return BRS_ERR_STATE;
   {
-    PGuard g(p->device);
+    DeviceGuard g(p->device);
     if (p->w_own) (void)hipFree(p->w_own);
   }
   delete p;
   return BRS_OK;
 }
 
-const char* brs_policy_last_error(const brs_policy* p) { return p ? p->err.c_str() : g_policy_create_error.c_str(); }
+const char* brs_policy_last_error(const brs_policy* p) { return brs::host::last_error(p); }
 
 int brs_policy_set_weights(brs_policy* p, const float* params_host) {
   if (!p) return BRS_ERR_STATE;
-  if (!params_host) return pfail(p, BRS_ERR_ARG, "brs_policy_set_weights: null pointer");
-  PGuard g(p->device);
-  if (!g.ok) return pfail(p, BRS_ERR_HIP, "brs_policy_set_weights: hipSetDevice failed");
+  if (!params_host) return fail(p, BRS_ERR_ARG, "brs_policy_set_weights: null pointer");
+  DeviceGuard g(p->device);
+  if (!g.ok) return fail(p, BRS_ERR_HIP, "brs_policy_set_weights: hipSetDevice failed");
   // kernels enqueued earlier on ANY stream (PyTorch's side streams do not synchronise with the null stream) may still be
   // reading w_own: drain the device before overwriting it.  Not on the rollout path (weights change once per update).
-  BRS_P_TRY(p, hipDeviceSynchronize());
-  BRS_P_TRY(p, hipMemcpy(p->w_own, params_host, BRS_POLICY_NPARAM * sizeof(float), hipMemcpyHostToDevice));
+  BRS_HIP_TRY(p, hipDeviceSynchronize());
+  BRS_HIP_TRY(p, hipMemcpy(p->w_own, params_host, BRS_POLICY_NPARAM * sizeof(float), hipMemcpyHostToDevice));
   p->w = p->w_own;
   return BRS_OK;
 }
 
 int brs_policy_use_device_weights(brs_policy* p, const float* params_dev) {
   if (!p) return BRS_ERR_STATE;
-  if (!params_dev) return pfail(p, BRS_ERR_ARG, "brs_policy_use_device_weights: null pointer");
+  if (!params_dev) return fail(p, BRS_ERR_ARG, "brs_policy_use_device_weights: null pointer");
   p->w = params_dev;
   return BRS_OK;
 }
@@ -320,22 +298,22 @@ int brs_policy_act(brs_policy* p, int32_t n, const float* obs_dev, uint64_t seed
                    float* noise_dev, void* stream) {
   if (!p) return BRS_ERR_STATE;
   if (n <= 0 || !obs_dev || !action_dev || !action_clipped_dev || !logp_dev || !value_dev)
-    return pfail(p, BRS_ERR_ARG, "brs_policy_act: bad argument");
-  PGuard g(p->device);
-  if (!g.ok) return pfail(p, BRS_ERR_HIP, "brs_policy_act: hipSetDevice failed");
+    return fail(p, BRS_ERR_ARG, "brs_policy_act: bad argument");
+  DeviceGuard g(p->device);
+  if (!g.ok) return fail(p, BRS_ERR_HIP, "brs_policy_act: hipSetDevice failed");
   hipLaunchKernelGGL(policy_act_kernel, dim3((n + POLICY_THREADS - 1) / POLICY_THREADS), dim3(POLICY_THREADS), 0, (hipStream_t)stream, p->w, n, obs_dev, seed, env_index_base,
                      step, deterministic, action_dev, action_clipped_dev, logp_dev, value_dev, noise_dev);
-  BRS_P_TRY(p, hipGetLastError());
+  BRS_HIP_TRY(p, hipGetLastError());
   return BRS_OK;
 }
 
 int brs_policy_value(brs_policy* p, int32_t n, const float* obs_dev, float* value_dev, void* stream) {
   if (!p) return BRS_ERR_STATE;
-  if (n <= 0 || !obs_dev || !value_dev) return pfail(p, BRS_ERR_ARG, "brs_policy_value: bad argument");
-  PGuard g(p->device);
-  if (!g.ok) return pfail(p, BRS_ERR_HIP, "brs_policy_value: hipSetDevice failed");
+  if (n <= 0 || !obs_dev || !value_dev) return fail(p, BRS_ERR_ARG, "brs_policy_value: bad argument");
+  DeviceGuard g(p->device);
+  if (!g.ok) return fail(p, BRS_ERR_HIP, "brs_policy_value: hipSetDevice failed");
   hipLaunchKernelGGL(policy_value_kernel, dim3((n + POLICY_THREADS - 1) / POLICY_THREADS), dim3(POLICY_THREADS), 0, (hipStream_t)stream, p->w, n, obs_dev, value_dev);
-  BRS_P_TRY(p, hipGetLastError());
+  BRS_HIP_TRY(p, hipGetLastError());
   return BRS_OK;
 }
 
@@ -343,12 +321,12 @@ int brs_rollout_bootstrap(brs_policy* p, int32_t n, const float* terminal_obs_de
                           const uint8_t* truncated_dev, float gamma, float* reward_dev, void* stream) {
   if (!p) return BRS_ERR_STATE;
   if (n <= 0 || !terminal_obs_dev || !terminated_dev || !truncated_dev || !reward_dev)
-    return pfail(p, BRS_ERR_ARG, "brs_rollout_bootstrap: bad argument");
-  PGuard g(p->device);
-  if (!g.ok) return pfail(p, BRS_ERR_HIP, "brs_rollout_bootstrap: hipSetDevice failed");
+    return fail(p, BRS_ERR_ARG, "brs_rollout_bootstrap: bad argument");
+  DeviceGuard g(p->device);
+  if (!g.ok) return fail(p, BRS_ERR_HIP, "brs_rollout_bootstrap: hipSetDevice failed");
   hipLaunchKernelGGL(bootstrap_kernel, dim3((n + POLICY_THREADS - 1) / POLICY_THREADS), dim3(POLICY_THREADS), 0, (hipStream_t)stream, p->w, n, terminal_obs_dev, terminated_dev,
                      truncated_dev, gamma, reward_dev);
-  BRS_P_TRY(p, hipGetLastError());
+  BRS_HIP_TRY(p, hipGetLastError());
   return BRS_OK;
 }
 
@@ -357,7 +335,7 @@ int brs_gae(int32_t device, int32_t T, int32_t N, const float* reward_dev, const
             void* stream) {
   if (T <= 0 || N <= 0 || !reward_dev || !value_dev || !episode_start_dev || !last_value_dev || !last_done_dev || !adv_dev || !ret_dev)
     return BRS_ERR_ARG;
-  PGuard g(device);
+  DeviceGuard g(device);
   if (!g.ok) return BRS_ERR_HIP;
   hipLaunchKernelGGL(gae_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, N, reward_dev, value_dev, episode_start_dev,
                      last_value_dev, last_done_dev, gamma, lam, adv_dev, ret_dev);

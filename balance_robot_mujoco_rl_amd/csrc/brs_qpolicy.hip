@@ -18,6 +18,7 @@
 
 #include <string>
 
+#include "brs_host.hpp"
 #include "brs_qpolicy.hpp"
 
 namespace {
@@ -136,39 +137,21 @@ struct brs_qpolicy {
   std::string err;
 };
 
-namespace {
-thread_local std::string g_qpolicy_error;  // of calls without a handle
-int qfail(brs_qpolicy* p, int code, const std::string& m) {
-  if (p) p->err = m; else g_qpolicy_error = m;
-  return code;
-}
-struct QGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit QGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~QGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-}  // namespace
+using brs::host::DeviceGuard, brs::host::fail;  // fail<brs_qpolicy>(nullptr, ...): the error of a call without a handle
 
 extern "C" {
 
 int brs_qpolicy_create(int32_t device, brs_qpolicy** out) {
-  if (!out) return qfail(nullptr, BRS_ERR_ARG, "brs_qpolicy_create: null argument");
+  if (!out) return fail<brs_qpolicy>(nullptr, BRS_ERR_ARG, "brs_qpolicy_create: null argument");
   *out = nullptr;
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0)
-    return qfail(nullptr, BRS_ERR_HIP, std::string("brs_qpolicy_create: no HIP device (") + hipGetErrorString(e) + "); there is no CPU fallback");
-  if (device < 0 || device >= ndev) return qfail(nullptr, BRS_ERR_ARG, "brs_qpolicy_create: device ordinal out of range");
+  std::string why;
+  if (const int rc = brs::host::check_device(device, "brs_qpolicy_create", &why)) return fail<brs_qpolicy>(nullptr, rc, why);
   brs_qpolicy* p = new brs_qpolicy();
   p->device = device;
-  QGuard g(device);
+  DeviceGuard g(device);
   if (!g.ok || hipMalloc(&p->image_dev, sizeof(brs::qpolicy::Image)) != hipSuccess) {
     delete p;
-    return qfail(nullptr, BRS_ERR_HIP, "brs_qpolicy_create: device allocation failed");
+    return fail<brs_qpolicy>(nullptr, BRS_ERR_HIP, "brs_qpolicy_create: device allocation failed");
   }
   *out = p;
   return BRS_OK;
@@ -177,14 +160,14 @@ int brs_qpolicy_create(int32_t device, brs_qpolicy** out) {
 int brs_qpolicy_destroy(brs_qpolicy* p) {
   if (!p) return BRS_ERR_STATE;
   {
-    QGuard g(p->device);
+    DeviceGuard g(p->device);
     if (p->image_dev) (void)hipFree(p->image_dev);
   }
   delete p;
   return BRS_OK;
 }
 
-const char* brs_qpolicy_last_error(const brs_qpolicy* p) { return p ? p->err.c_str() : g_qpolicy_error.c_str(); }
+const char* brs_qpolicy_last_error(const brs_qpolicy* p) { return brs::host::last_error(p); }
 
 int brs_qpolicy_quantize_multiplier(double M, int32_t* m, int32_t* t) { return brs::qpolicy::quantize_multiplier(M, m, t); }
 
@@ -192,27 +175,27 @@ int brs_qpolicy_set_model(brs_qpolicy* p, const brs_qmodel* model) {
   brs::qpolicy::Image im;
   std::string why;
   const int rc = brs::qpolicy::build_image(model, &im, &why);  // before the handle: a model can be checked without a device
-  if (rc != BRS_OK) return qfail(p, rc, why);
+  if (rc != BRS_OK) return fail(p, rc, why);
   if (!p) return BRS_ERR_STATE;
-  QGuard g(p->device);
-  if (!g.ok) return qfail(p, BRS_ERR_HIP, "brs_qpolicy_set_model: hipSetDevice failed");
+  DeviceGuard g(p->device);
+  if (!g.ok) return fail(p, BRS_ERR_HIP, "brs_qpolicy_set_model: hipSetDevice failed");
   // kernels enqueued earlier on any stream may still be reading the image: drain the device before overwriting it
   hipError_t e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(p->image_dev, &im, sizeof(im), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return qfail(p, BRS_ERR_HIP, std::string("brs_qpolicy_set_model: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(p, BRS_ERR_HIP, std::string("brs_qpolicy_set_model: ") + hipGetErrorString(e));
   p->has_model = true;
   return BRS_OK;
 }
 
 int brs_qpolicy_act(brs_qpolicy* p, int32_t n, const float* obs_dev, float* action_dev, int8_t* action_q_dev, void* stream) {
   if (!p) return BRS_ERR_STATE;
-  if (n <= 0 || !obs_dev || !action_dev) return qfail(p, BRS_ERR_ARG, "brs_qpolicy_act: bad argument");
-  if (!p->has_model) return qfail(p, BRS_ERR_STATE, "brs_qpolicy_act: no model has been set");
-  QGuard g(p->device);
-  if (!g.ok) return qfail(p, BRS_ERR_HIP, "brs_qpolicy_act: hipSetDevice failed");
+  if (n <= 0 || !obs_dev || !action_dev) return fail(p, BRS_ERR_ARG, "brs_qpolicy_act: bad argument");
+  if (!p->has_model) return fail(p, BRS_ERR_STATE, "brs_qpolicy_act: no model has been set");
+  DeviceGuard g(p->device);
+  if (!g.ok) return fail(p, BRS_ERR_HIP, "brs_qpolicy_act: hipSetDevice failed");
   hipLaunchKernelGGL(qpolicy_act_kernel, dim3((n + QPOLICY_THREADS - 1) / QPOLICY_THREADS), dim3(QPOLICY_THREADS), 0, (hipStream_t)stream,
                      p->image_dev, n, obs_dev, action_dev, action_q_dev);
-  if (hipGetLastError() != hipSuccess) return qfail(p, BRS_ERR_HIP, "brs_qpolicy_act: kernel launch failed");
+  if (hipGetLastError() != hipSuccess) return fail(p, BRS_ERR_HIP, "brs_qpolicy_act: kernel launch failed");
   return BRS_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "../../include/brs_render.h"
+#include "brs_host.hpp"
 #include "brs_render.hpp"
 
 namespace {
@@ -57,7 +58,8 @@ const char* brs_render_last_error(void) { return g_err; }
 int brs_render(int32_t device, int32_t variant, int32_t k, const double* qpos_dev, const brs_camera* cam,
                uint8_t* rgb_dev, float* depth_dev, uint8_t* seg_dev, void* stream) {
   g_err[0] = 0;
-  if (variant < BRS_ENV01_V1 || variant > BRS_ENV02_V1) return fail(BRS_ERR_ARG, "unknown variant");
+  int32_t nq = 0;
+  if (brs_sizes(variant, &nq, nullptr, nullptr, nullptr) != BRS_OK) return fail(BRS_ERR_ARG, "unknown variant");
   if (k < 1) return fail(BRS_ERR_ARG, "k must be >= 1");
   if (!cam) return fail(BRS_ERR_ARG, "cam is NULL");
   if (!qpos_dev) return fail(BRS_ERR_ARG, "qpos_dev is NULL");
@@ -70,20 +72,17 @@ int brs_render(int32_t device, int32_t variant, int32_t k, const double* qpos_de
   const int tiles_x = (cam->width + TILE_W - 1) / TILE_W, tiles_y = (cam->height + TILE_H - 1) / TILE_H;
   const long long blocks = (long long)k * tiles_x * tiles_y;
   if (blocks > 0x7fffffffLL) return fail(BRS_ERR_ARG, "k x tiles exceeds the grid limit");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(BRS_ERR_ARG, "bad device ordinal");
+  std::string why;  // (unused: this entry point has always reported any unusable ordinal as an argument error)
+  if (brs::host::check_device(device, "brs_render", &why) != BRS_OK) return fail(BRS_ERR_ARG, "bad device ordinal");
 
-  const int has_block = variant == BRS_ENV03_V1 || variant == BRS_ENV03_V2;
-  const int nq = has_block ? 16 : 9;
+  const int has_block = brs::host::has_block(variant);
   const brs::render::Camera c = brs::render::make_camera(cam->width, cam->height, cam->fovy_deg, cam->distance,
                                                           cam->azimuth_deg, cam->elevation_deg);
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) return fail(BRS_ERR_HIP, "hipGetDevice failed");
-  if (prev != device && hipSetDevice(device) != hipSuccess) return fail(BRS_ERR_HIP, "hipSetDevice failed");
+  brs::host::DeviceGuard g(device);
+  if (!g.ok) return fail(BRS_ERR_HIP, "hipSetDevice failed");
   hipLaunchKernelGGL(brs_render_kernel, dim3((unsigned)blocks), dim3(TILE_W * TILE_H), 0, (hipStream_t)stream, qpos_dev,
-                     nq, has_block, c, tiles_x, tiles_y, rgb_dev, depth_dev, seg_dev);
+                     (int)nq, has_block, c, tiles_x, tiles_y, rgb_dev, depth_dev, seg_dev);
   hipError_t e = hipGetLastError();
-  if (prev != device) (void)hipSetDevice(prev);
   if (e != hipSuccess) {
     snprintf(g_err, sizeof g_err, "brs_render: launch failed: %s", hipGetErrorString(e));
     return BRS_ERR_HIP;

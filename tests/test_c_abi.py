@@ -9,24 +9,37 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared():
-    names = set()
-    for h in ("brs.h", "brs_policy.h"):
-        txt = open(os.path.join(ROOT, "include", h)).read()
-        txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-        names |= set(re.findall(r"\b(brs_[a-z_0-9]+)\s*\(", txt))
-    return sorted(names)
+HEADERS = ("brs.h", "brs_policy.h", "brs_render.h", "brs_qpolicy.h")
+
+
+def _declared(header):
+    """{function name: number of parameters} of every function the header declares"""
+    txt = open(os.path.join(ROOT, "include", header)).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return {name: 0 if params.strip() in ("", "void") else params.count(",") + 1
+            for name, params in re.findall(r"\b(brs_[a-z_0-9]+)\s*\(([^()]*)\)", txt)}
 
 
 def test_header_symbols_exported():
+    """one table (_lib.SIGNATURES) holds the C ABI: every function a header declares has an entry under that header with
+    as many arguments as the declaration, every entry is declared, exported and applied, and the symbol lists derive from it"""
     from balance_robot_mujoco_rl_amd import _lib
     _lib.build()
     L = _lib.lib()
-    names = _declared()
-    assert len(names) >= 15
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/*.h but not exported by libbrs_hip.so"
-    assert sorted(_lib.SYMBOLS) == names
+    assert sorted(_lib.SIGNATURES) == sorted(HEADERS)
+    for header in HEADERS:
+        declared, table = _declared(header), _lib.SIGNATURES[header]
+        assert sorted(declared) == sorted(table), (header, sorted(set(declared) ^ set(table)))
+        for name, nparam in declared.items():
+            restype, argtypes = table[name]
+            assert hasattr(L, name), f"{name} declared in include/{header} but not exported by libbrs_hip.so"
+            assert len(argtypes) == nparam, f"{name}: include/{header} declares {nparam} parameters, the table {len(argtypes)}"
+            fn = getattr(L, name)
+            assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    assert len(_declared("brs.h")) + len(_declared("brs_policy.h")) >= 15
+    assert sorted(_lib.SYMBOLS) == sorted(list(_declared("brs.h")) + list(_declared("brs_policy.h")))
+    assert sorted(_lib.RENDER_SYMBOLS) == sorted(_declared("brs_render.h"))
+    assert sorted(_lib.QPOLICY_SYMBOLS) == sorted(_declared("brs_qpolicy.h"))
 
 
 def test_sizes_and_bad_args_without_device():
@@ -62,6 +75,38 @@ def test_no_cpu_fallback():
     cfg = _lib.BrsConfig(1, 8, 0, 0, 0, 0, 0, 0, 0.0, 0, 0)
     assert L.brs_create(C.byref(cfg), C.byref(h)) == -2  # BRS_ERR_HIP
     assert b"no CPU fallback" in L.brs_last_error(None)
+
+
+def test_every_family_fails_loudly_without_a_device():
+    """all three handle families go through the same device check (csrc/brs_host.hpp): BRS_ERR_HIP, and each family's
+    handle-less error text says that there is no CPU fallback"""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present: the loud-failure path is for machines without one")
+    from balance_robot_mujoco_rl_amd import _lib
+    L = _lib.lib()
+    h = C.c_void_p()
+    cfg = _lib.BrsConfig(3, 65, 0, 0, 0, 0, 0, 0, 0.0, 0, 0)
+    for create, last_error, who in ((lambda: L.brs_create(C.byref(cfg), C.byref(h)), L.brs_last_error, b"brs_create"),
+                                    (lambda: L.brs_policy_create(0, C.byref(h)), L.brs_policy_last_error, b"brs_policy_create"),
+                                    (lambda: L.brs_qpolicy_create(0, C.byref(h)), L.brs_qpolicy_last_error, b"brs_qpolicy_create")):
+        assert create() == -2 and h.value is None, who   # BRS_ERR_HIP
+        msg = last_error(None)
+        assert msg.startswith(who + b": no HIP device (") and msg.endswith(b"); there is no CPU fallback"), msg
+    # the slots are per family: the last failure of one is not overwritten by another's
+    assert L.brs_create(None, C.byref(h)) == -1 and b"null argument" in L.brs_last_error(None)
+    assert b"no CPU fallback" in L.brs_policy_last_error(None) and b"no CPU fallback" in L.brs_qpolicy_last_error(None)
+
+
+def test_render_reports_a_bad_ordinal_as_an_argument_error():
+    """with or without a device: brs_render has no handle, and an ordinal this machine does not have is BRS_ERR_ARG"""
+    from balance_robot_mujoco_rl_amd import _lib
+    L = _lib.lib()
+    cam = _lib.BrsCamera(); L.brs_render_default_camera(C.byref(cam))
+    buf = C.c_void_p(1)
+    for ordinal in (-1, 1 << 20):
+        assert L.brs_render(ordinal, 3, 1, buf, C.byref(cam), buf, None, None, None) == -1
+        assert L.brs_render_last_error() == b"brs_render: bad device ordinal"
 
 
 def test_product_never_imports_oracle():
