@@ -59,10 +59,12 @@ class HostSim:
         self.n = num_envs
         self.nq, self.nv = self.L.hs_nq(self.h), self.L.hs_nv(self.h)
 
-    def __del__(self):
+    def close(self):
         if getattr(self, "h", None):
             self.L.hs_destroy(self.h)
             self.h = None
+
+    __del__ = close
 
     def set_state(self, qpos=None, qvel=None, warm=None, time=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)

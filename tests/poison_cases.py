@@ -157,7 +157,7 @@ def check_healthy_identical(run, control, who):
 
 def check_reset_matches_oracle(run, oracle_run, who):
     """a guard reset draws what any reset draws: obs of the poisoned step within the suite's tolerance for reset observations
-    (tests/test_gpu_parity.py: _shared_rng_parity), elapsed / RNG counter / attack side exactly the oracle's"""
+    (tests/test_gpu_parity.py: shared_rng_parity), elapsed / RNG counter / attack side exactly the oracle's"""
     rs = np.flatnonzero(run.expected & oracle_run.expected)
     assert rs.size > 0
     a, b = run.steps[0], oracle_run.steps[0]

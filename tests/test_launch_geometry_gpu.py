@@ -14,10 +14,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests import constructed_states as cs
-from tests import test_gpu_parity as gp
-from tests.test_gpu_parity import (_block_robot_caps, _constructed, _edge_edge_caps, _floor_caps, _floor_ctrl,
-                                   _runtime_parameter_parity, _shared_rng_parity)
+from tests import constructed_states as cs, parity as P, test_gpu_parity as gp
 from tests.test_policy_kernels import _ref_gae
 
 pytestmark = pytest.mark.gpu
@@ -184,9 +181,8 @@ def _physics_bitwise(env_id, qpos, qvel, ctrl, nsub):
 
 def _coupled_in_every_wave(qpos, qvel):
     """the oracle's block<->robot contact count of every env -> assert that every 64-lane wave holds some"""
-    from oracle import oracle as O
     n = len(qpos)
-    orc = O.Oracle("Env03-v2", n, seed=0)
+    orc = P.make("oracle", "Env03-v2", n, threads=1)
     orc.set_state(qpos, qvel)
     cnt = cs.coupled_contact_count(orc, n)
     orc.close()
@@ -198,14 +194,12 @@ def _coupled_in_every_wave(qpos, qvel):
 def test_b_env03_physics_on_constructed_contact_states_across_workgroup_sizes(which, n):
     """constructed block<->robot states tiled so that every wave of every workgroup holds coupled contacts: bit-identical at
     every size, and within the oracle caps of test_constructed_*_on_the_hip_path at 256 threads"""
-    qpos, qvel = cs.block_robot_states() if which == "block_robot" else cs.edge_edge_states()
-    idx = _tile(len(qpos), n, seed=3)
-    qpos, qvel = qpos[idx], qvel[idx]
+    sc = cs.SCENARIOS[which]
+    idx = _tile(len(sc["states"]()[0]), n, seed=3)
+    qpos, qvel, ctrl = cs.scenario_inputs(which, idx)
     _coupled_in_every_wave(qpos, qvel)
-    ctrl = np.zeros((n, 2))
-    _physics_bitwise("Env03-v2", qpos, qvel, ctrl, 5)
-    caps = _block_robot_caps if which == "block_robot" else _edge_edge_caps
-    caps(*_constructed("Env03-v2", qpos, qvel, ctrl, 5, block_threads=256))
+    _physics_bitwise(sc["env"], qpos, qvel, ctrl, sc["nsub"])
+    cs.check_hip_caps(which, *cs.run_scenario_on("hip", which, idx, block_threads=256))
 
 
 def test_b_env03_reset_across_workgroup_sizes():
@@ -241,14 +235,14 @@ def test_b_env03_reset_across_workgroup_sizes():
 @pytest.mark.parametrize("env_id,bt", [("Env01-v1", 128), ("Env01-v2", 128), ("Env01-v3", 128), ("Env02-v1", 128), ("Env01-v2", 256)])
 def test_c_uncapped_env01_kernels_vs_oracle(env_id, bt):
     """the assertions of test_env_step_parity_with_shared_rng at N = 2 x block_threads + 37, and G1-G3 on qpos"""
-    g, kernel = _shared_rng_parity(env_id, 2 * bt + 37, 40, block_threads=bt)
+    g, kernel = gp.shared_rng_parity(env_id, 2 * bt + 37, 40, block_threads=bt)
     _exercised(kernel, "test_c_uncapped_env01_kernels_vs_oracle")
     g.check(f"{env_id} ({kernel}, {bt} threads)")
     assert g.n["up"] > 0.25 * (2 * bt + 37) * 40
 
 
 def test_c_uncapped_runtime_constant_kernel_vs_oracle():
-    kernel = _runtime_parameter_parity("Env01-v2", 2 * 128 + 37, 60, block_threads=128)
+    kernel = gp.runtime_parameter_parity("Env01-v2", 2 * 128 + 37, 60, block_threads=128)
     _exercised(kernel, "test_c_uncapped_runtime_constant_kernel_vs_oracle")
 
 
@@ -301,12 +295,11 @@ def test_c_uncapped_and_capped_env01_v2_kernels_on_the_same_inputs():
 def test_c_uncapped_physics_on_floor_states_at_256_threads():
     """brs_physics<false> on the constructed floor states tiled over four waves of a 256-thread workgroup (plus a partial
     one): within the caps of test_constructed_floor_contact_states_on_the_hip_path, and bit-identical at every size"""
-    qpos, qvel = cs.floor_states()
-    n = 256 + 37
-    idx = _tile(len(qpos), n, seed=7)
-    ctrl = _floor_ctrl(len(qpos))[idx]
-    _physics_bitwise("Env01-v2", qpos[idx], qvel[idx], ctrl, 5)
-    _floor_caps(*_constructed("Env01-v2", qpos[idx], qvel[idx], ctrl, 5, block_threads=256))
+    sc = cs.SCENARIOS["floor"]
+    idx = _tile(len(sc["states"]()[0]), 256 + 37, seed=7)
+    qpos, qvel, ctrl = cs.scenario_inputs("floor", idx)
+    _physics_bitwise(sc["env"], qpos, qvel, ctrl, sc["nsub"])
+    cs.check_hip_caps("floor", *cs.run_scenario_on("hip", "floor", idx, block_threads=256))
 
 
 # ---- D: nothing is written past row N (the C ABI as BatchedSim calls it, outputs with block_threads guard rows)

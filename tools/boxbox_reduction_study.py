@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What does a k-point budget for a box-box patch cost?  MuJoCo keeps up to 8 clipped points; oracle and kernel keep the 6
-deepest (with 4, the budget of the first half of round 2, 4.8 % of env-steps differed).  Two oracles, one with the study switch on, are teacher-forced from the SAME states of
+deepest (with 4, the budget of the first half of round 2, 4.8 % of env-steps differed).  Two oracles, one with the study switch on, are teacher-forced (tests/parity.py) from the SAME states of
 the bench workload (Env03-v2, random policy, auto-reset); the per-env-step difference of their results is the effect of the
 reduction alone (CPU only).    python tools/boxbox_reduction_study.py [--envs 512 --steps 200]"""
 import argparse, json, os, sys
@@ -8,26 +8,28 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import oracle as O
+from tests import parity as P
 
 ap = argparse.ArgumentParser(); ap.add_argument("--envs", type=int, default=512); ap.add_argument("--steps", type=int, default=200)
 ap.add_argument("--keep", type=int, default=6, help="points the reduced side keeps (6 = the specification)")
 ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "boxbox_reduction_study.json"))
 a = ap.parse_args()
-n, thr = a.envs, min(os.cpu_count() or 1, 64)
-A = O.Oracle("Env03-v2", n, seed=0, auto_reset=True, noise=False, threads=thr)   # --keep deepest
-B = O.Oracle("Env03-v2", n, seed=0, auto_reset=True, noise=False, threads=thr)   # all <= 8 points
+n = a.envs
+A = P.make("oracle", "Env03-v2", n, seed=0, auto_reset=True, noise=False)   # --keep deepest
+B = P.make("oracle", "Env03-v2", n, seed=0, auto_reset=True, noise=False)   # all <= 8 points
 A.reset(); B.reset()
-rng = np.random.default_rng(1234)
-errs, touched = [], 0
-for t in range(a.steps):
-    qpos, qvel, warm, tm = A.get_state()
-    B.set_state(qpos, qvel, warm, tm); B.set_aux(A.get_aux()); B.set_xpose(*A.get_xpose())
-    act = rng.uniform(-1, 1, size=(n, 2)).astype(np.float32)
-    O.set_boxbox_max(a.keep); oa = A.step(act)
-    O.set_boxbox_max(8); ob = B.step(act)
-    O.set_boxbox_max(6)
-    skip = oa[2] | oa[3] | ob[2] | ob[3] | (np.isnan(A.get_aux()[:, 1]) != np.isnan(B.get_aux()[:, 1]))
-    d = np.abs(A.get_state()[0] - B.get_state()[0])[~skip]
+
+
+def keeping(orc, keep):
+    """the study switch is process-wide: this oracle steps with it at `keep` points"""
+    step = orc.step
+    orc.step = lambda act: (O.set_boxbox_max(keep), step(act), O.set_boxbox_max(6))[1]
+    return orc
+
+
+errs = []
+for r in P.env_steps(keeping(A, a.keep), keeping(B, 8), a.steps, "random", np.random.default_rng(1234)):
+    d = np.abs(r.post_t[0] - r.post_s[0])[~r.skip]
     errs.append(np.stack([d[:, :9].max(axis=1), d[:, 9:].max(axis=1)], 1))
 e = np.concatenate(errs)
 rep = dict(kept_points=a.keep, env_steps=int(e.shape[0]), affected_env_steps=int((e.max(axis=1) > 1e-9).sum()),

@@ -9,24 +9,22 @@ import json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from balance_robot_mujoco_rl_amd import BatchedSim  # noqa: E402
-from oracle import oracle as O  # noqa: E402
+from tests import parity as P  # noqa: E402
 
 rep = json.load(open(sys.argv[1]))
 env_id = rep["env"]
-sim = BatchedSim(env_id, 1, device=0, seed=0, auto_reset=False, obs_noise=False)
-orc = O.Oracle(env_id, 1, seed=0, auto_reset=False, noise=False)
+sim = P.make("hip", env_id, 1, seed=0, auto_reset=False, noise=False)
+orc = P.make("oracle", env_id, 1, seed=0, auto_reset=False, noise=False)
 for o in rep["outliers"]:
-    pre = o["pre"]
-    qpos, qvel, warm = (np.array(pre[k], dtype=np.float64)[None] for k in ("qpos", "qvel", "warm"))
-    tm = np.array([pre["time"]]); ctrl = np.array(pre["ctrl"], dtype=np.float64)
-    orc.set_state(qpos, qvel, warm, tm); orc.physics(ctrl[None], 250)
+    pre = P.outlier_arrays(o["pre"])
+    ctrl = P.round_ctrl(pre["ctrl"], sim)[None]
+    P.force(orc, pre); orc.physics(ctrl, 250)
     qo = orc.get_state()[0][0]
     out = {}
     for chunks in ([250], [125, 125], [50] * 5, [10] * 25, [1] * 250):
-        sim.set_state(qpos, qvel, warm, tm)
+        P.force(sim, pre)
         for n in chunks:
-            sim.physics(ctrl.astype(np.float32)[None], n)
+            sim.physics(ctrl, n)
         qg = sim.get_state()[0][0]
         d = np.abs(qg - qo)
         out[f"{len(chunks)}x{chunks[0]}"] = (float(d[:9].max()), float(d[9:].max()) if d.size > 9 else 0.0)

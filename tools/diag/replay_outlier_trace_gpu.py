@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostic (GPU box): one substep per launch from a dumped pre-step state, HIP path vs oracle; prints the per-dof velocity
-difference and the oracle's contacts (pairs and distances) around the first substep where the difference jumps.
+difference and the oracle's contacts (pairs and distances) at the substeps where the difference jumps (tests/parity.py: replay_substeps).
 
     python tools/diag/replay_outlier_trace_gpu.py dump.json [outlier index]
 """
@@ -8,28 +8,30 @@ import json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from balance_robot_mujoco_rl_amd import BatchedSim  # noqa: E402
-from oracle import oracle as O  # noqa: E402
+from tests import parity as P  # noqa: E402
 
 rep = json.load(open(sys.argv[1]))
 o = rep["outliers"][int(sys.argv[2]) if len(sys.argv) > 2 else 0]
-env_id, pre = rep["env"], o["pre"]
-sim = BatchedSim(env_id, 1, device=0, seed=0, auto_reset=False, obs_noise=False)
-orc = O.Oracle(env_id, 1, seed=0, auto_reset=False, noise=False)
-qpos, qvel, warm = (np.array(pre[k], dtype=np.float64)[None] for k in ("qpos", "qvel", "warm"))
-tm, ctrl = np.array([pre["time"]]), np.array(pre["ctrl"], dtype=np.float64)
-sim.set_state(qpos, qvel, warm, tm); orc.set_state(qpos, qvel, warm, tm)
-prev, shown = 0.0, 0
+env_id, pre = rep["env"], P.outlier_arrays(o["pre"])
+sim = P.make("hip", env_id, 1, seed=0, auto_reset=False, noise=False)
+orc = P.make("oracle", env_id, 1, seed=0, auto_reset=False, noise=False)
+seen = dict(prev=0.0, shown=0, cons=None)
 np.set_printoptions(precision=3, linewidth=200, suppress=False)
-for k in range(250):
-    fw = orc.forward(env=0, ctrl=(float(ctrl[0]), float(ctrl[1])))
-    cons = [(int(c["body1"]), int(c["body2"]), round(float(c["dist"]), 6)) for c in fw["contacts"]]
-    sim.physics(ctrl.astype(np.float32)[None], 1); orc.physics(ctrl[None], 1)
-    vg, vo = sim.get_state()[1][0], orc.get_state()[1][0]
-    ev = float(np.abs(vg - vo).max())
-    if (ev > 1e-5 and ev > 5 * max(prev, 1e-8)) and shown < 6:
-        shown += 1
-        print(f"substep {k}: max |dqvel| {ev:.3g} (before {prev:.3g}); dqvel per dof {vg - vo}")
-        print(f"   oracle contacts entering the substep: {cons}; oracle qvel {vo}")
-    prev = ev
-print("final |dqpos|", float(np.abs(sim.get_state()[0][0] - orc.get_state()[0][0]).max()))
+
+
+def show(k):
+    """after substep k - 1: report it if the velocity difference jumped; then note the contacts entering substep k"""
+    if k:
+        vg, vo = sim.get_state()[1][0], orc.get_state()[1][0]
+        ev = float(np.abs(vg - vo).max())
+        if (ev > 1e-5 and ev > 5 * max(seen["prev"], 1e-8)) and seen["shown"] < 6:
+            seen["shown"] += 1
+            print(f"substep {k - 1}: max |dqvel| {ev:.3g} (before {seen['prev']:.3g}); dqvel per dof {vg - vo}")
+            print(f"   oracle contacts entering the substep: {seen['cons']}; oracle qvel {vo}")
+        seen["prev"] = ev
+    fw = orc.forward(env=0, ctrl=(float(pre["ctrl"][0]), float(pre["ctrl"][1])))
+    seen["cons"] = [(int(c["body1"]), int(c["body2"]), round(float(c["dist"]), 6)) for c in fw["contacts"]]
+
+
+_, trace = P.replay_substeps(orc, sim, pre, pre["ctrl"], jump_abs=1e-5, jump_ratio=5, floor=1e-8, on_substep=show)
+print("final |dqpos|", trace[-1][0])

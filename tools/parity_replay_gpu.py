@@ -7,44 +7,25 @@ velocity difference jumps, and the oracle's contact list (body pairs) just befor
 contact point appearing or disappearing is the "switches on one substep apart" mechanism of DESIGN.md 2.1.
 
     python tools/parity_replay_gpu.py profiles/r02_parity_config3_large.json   (rewrites the file with replay_gpu_vs_oracle added)
+The replay and its first-jump rule: tests/parity.py, replay_substeps.
 """
 import json, os, sys
-import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-def contact_pairs(orc, ctrl):
-    fw = orc.forward(env=0, ctrl=(float(ctrl[0]), float(ctrl[1])))
-    return sorted((int(c["body1"]), int(c["body2"])) for c in fw["contacts"])
+from tests import parity as P  # noqa: E402
 
 
 def main():
     path = sys.argv[1]
     rep = json.load(open(path))
-    from balance_robot_mujoco_rl_amd import BatchedSim
-    from oracle import oracle as O
     env_id = rep["env"]
-    sim = BatchedSim(env_id, 1, device=0, seed=0, auto_reset=False, obs_noise=False)
-    orc = O.Oracle(env_id, 1, seed=0, auto_reset=False, noise=False)
+    sim = P.make("hip", env_id, 1, seed=0, auto_reset=False, noise=False)
+    orc = P.make("oracle", env_id, 1, seed=0, auto_reset=False, noise=False)
     for o in rep["outliers"]:
-        pre = o["pre"]
-        qpos, qvel, warm = (np.array(pre[k], dtype=np.float64)[None] for k in ("qpos", "qvel", "warm"))
-        tm = np.array([pre["time"]])
-        ctrl = np.array(pre["ctrl"], dtype=np.float64)
-        sim.set_state(qpos, qvel, warm, tm); orc.set_state(qpos, qvel, warm, tm)
-        c32 = ctrl.astype(np.float32)[None]
-        first_jump, prev, trace, pairs = None, 0.0, [], []
-        for k in range(250):
-            pairs.append(contact_pairs(orc, ctrl))
-            sim.physics(c32, 1); orc.physics(c32.astype(np.float64), 1)
-            qg, vg, _, _ = sim.get_state(); qo, vo, _, _ = orc.get_state()
-            ev = float(np.abs(vg - vo).max())
-            trace.append((float(np.abs(qg - qo).max()), ev))
-            if first_jump is None and ev > 1e-3 and ev > 20 * max(prev, 1e-7):
-                first_jump = k
-            prev = ev
-        pairs.append(contact_pairs(orc, ctrl))
+        pre = P.outlier_arrays(o["pre"])
+        pairs = []
+        first_jump, trace = P.replay_substeps(orc, sim, pre, pre["ctrl"], jump_abs=1e-3, jump_ratio=20, floor=1e-7,
+                                              on_substep=lambda k: pairs.append(P.contact_pairs(orc, pre["ctrl"])))
         rec = dict(first_substep_dqvel_jump=first_jump, final_dqpos=trace[-1][0], final_dqvel=trace[-1][1])
         if first_jump is not None:
             lo, hi = max(0, first_jump - 2), min(250, first_jump + 2)
