@@ -21,9 +21,11 @@ SIM_FLAGS = ["-Xarch_device", "-ffast-math", "-Xarch_device", "-fgpu-flush-denor
              # an independent one for a lone wave).  The ILP strategy: +4.3 % Env03, +2.7 % Env01 (same-box A/B)
              "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 # the translation units of libbrs_hip.so: (source, its own flags, in the build id).  Policy / GAE kernels, renderer and int8 actor
-# keep IEEE math (checked against fp32 torch at rtol 1e-5 / bit for bit against their host builds under tests/); the build id
-# names the step and policy kernels that committed profiles were measured on, so the other two units stay out of it.
-UNITS = [("brs_kernels.hip", SIM_FLAGS, True), ("brs_policy.hip", [], True), ("brs_render.hip", [], False), ("brs_qpolicy.hip", [], False)]
+# keep IEEE math (checked against fp32 torch at rtol 1e-5 / bit for bit against their host builds under tests/), and so does the
+# episode monitor; the build id names the step and policy kernels that committed profiles were measured on, so the other three
+# units stay out of it.
+UNITS = [("brs_kernels.hip", SIM_FLAGS, True), ("brs_policy.hip", [], True), ("brs_render.hip", [], False), ("brs_qpolicy.hip", [], False),
+         ("brs_monitor.hip", [], False)]
 SRC = os.path.join(_CSRC, UNITS[0][0])  # the unit that takes the A/B flags and the build id stamp
 # what the build id hashes next to the sources of its units; brs_host.hpp holds no kernel code and stays out of it
 HEADERS = [os.path.join(_CSRC, h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp")] + \
@@ -41,6 +43,12 @@ class BrsConfig(C.Structure):
 class BrsCamera(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fovy_deg", C.c_float), ("distance", C.c_float),
                 ("azimuth_deg", C.c_float), ("elevation_deg", C.c_float)]
+
+
+class BrsEpisodeStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("episodes", "ended", "terminated", "time_limit", "sum_len", "sum_len2", "steps")] + \
+               [(k, C.c_double) for k in ("sum_ret", "sum_ret2", "min_ret", "max_ret", "running_ret")] + \
+               [(k, C.c_int32) for k in ("min_len", "max_len", "first_running", "pending")]
 
 
 class BrsQLayer(C.Structure):
@@ -129,6 +137,14 @@ SIGNATURES = {
         "brs_policy_value": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
         "brs_rollout_bootstrap": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
         "brs_gae": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp]),
+        "brs_monitor_create": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_vp)]),
+        "brs_monitor_destroy": (C.c_int, [_vp]),
+        "brs_monitor_last_error": (C.c_char_p, [_vp]),
+        "brs_monitor_reset": (C.c_int, [_vp, _i32p, _vp]),
+        "brs_monitor_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+        "brs_monitor_stats": (C.c_int, [_vp, C.POINTER(BrsEpisodeStats), _vp]),
+        "brs_monitor_histogram": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp]),
+        "brs_monitor_episodes": (C.c_int, [_vp, _i32p, _dp, _i32p, C.POINTER(C.c_uint8), _vp]),
     },
     "brs_render.h": {
         "brs_render_default_camera": (None, [C.POINTER(BrsCamera)]),

@@ -155,10 +155,13 @@ def gae(reward, value, episode_start, last_value, last_done, gamma, lam, adv=Non
 
 class DeviceRollout:
     """[T][N] rollout buffer resident in HBM (SB3's RolloutBuffer, without the host): collect() alternates
-    brs_policy_act -> brs_step -> brs_rollout_bootstrap with no synchronisation and no allocation, finish() runs GAE."""
+    brs_policy_act -> brs_step -> brs_rollout_bootstrap with no synchronisation and no allocation, finish() runs GAE.
+    `monitor`: an EpisodeMonitor (monitor.py) that is fed the env's own reward and done flags of every step (one more kernel
+    per step, still no synchronisation); its statistics are read by the caller, whenever it wants them."""
 
-    def __init__(self, sim, policy, n_steps, gamma=0.99, gae_lambda=0.95):
+    def __init__(self, sim, policy, n_steps, gamma=0.99, gae_lambda=0.95, monitor=None):
         self.sim, self.policy, self.T, self.gamma, self.lam = sim, policy, int(n_steps), float(gamma), float(gae_lambda)
+        self.monitor = monitor
         n, d, T = sim.n, sim.device, self.T
         f = lambda *s: torch.zeros(s, dtype=torch.float32, device=d)
         self.obs, self.action, self.logp, self.value, self.reward = f(T, n, 6), f(T, n, 2), f(T, n), f(T, n), f(T, n)
@@ -180,6 +183,8 @@ class DeviceRollout:
             pol.act(self.obs[t], self._step, out=(self.action[t], self._clipped, self.logp[t], self.value[t]))
             self._step += 1
             obs, rew, term, trunc, tobs = sim.step(self._clipped)
+            if self.monitor is not None:
+                self.monitor.update(rew, term, trunc)
             self.reward[t].copy_(rew)
             pol.bootstrap(tobs, term, trunc, self.gamma, self.reward[t])
             self._last_obs.copy_(obs)

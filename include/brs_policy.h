@@ -9,6 +9,10 @@
  *   brs_rollout_bootstrap collect_rollouts' time-limit handling: rewards[i] += gamma * V(terminal_observation[i]) for
  *                         envs whose episode was truncated, not terminated
  *   brs_gae               RolloutBuffer.compute_returns_and_advantage (GAE(lambda) over the [T][N] buffer)
+ *   brs_monitor_update    Monitor / VecMonitor (src/sb_rl.py:501): the return and the length of every episode, summed step
+ *                         by step and closed when the env reports terminated or truncated
+ *   brs_monitor_reset     evaluate_policy (under EvalCallback, src/sb_rl.py:536-543): with targets, the first target[i]
+ *   (with targets)        episodes of env i count and the others are ignored, target[i] = (n_eval_episodes + i) / n
  *
  * These entry points do the same arithmetic on the GPU, reading the simulator's outputs in place (device pointers),
  * so that a rollout of 65,536 envs needs no per-env Python and no PCIe traffic.  All buffers are DEVICE pointers owned
@@ -63,6 +67,51 @@ int brs_rollout_bootstrap(brs_policy*, int32_t n, const float* terminal_obs_dev,
 int brs_gae(int32_t device, int32_t T, int32_t N, const float* reward_dev, const float* value_dev,
             const uint8_t* episode_start_dev, const float* last_value_dev, const uint8_t* last_done_dev, float gamma,
             float lam, float* adv_dev, float* ret_dev, void* stream);
+
+/* ---- episode statistics.  A monitor watches n envs: brs_monitor_update is called once per env step
+ * with the three arrays brs_step wrote (the env's own reward, not a rollout buffer's bootstrapped copy) and keeps, per env,
+ * the running return (fp64, summed in step order) and length, and per finished episode the accumulators below, a histogram
+ * of episode lengths and -- when targets are set -- a log with one row per counted episode.  Everything lives on the device;
+ * no floating-point atomic is used, so two runs on the same inputs return identical bytes. */
+typedef struct brs_monitor brs_monitor;
+
+typedef struct brs_episode_stats {
+  int64_t episodes;      /* counted episodes: all that ended (no targets), or the first target[i] of env i */
+  int64_t ended;         /* episodes that ended, counted or not */
+  int64_t terminated;    /* counted episodes that ended with terminated != 0 */
+  int64_t time_limit;    /* counted episodes that ended with truncated != 0 and terminated == 0 */
+  int64_t sum_len;       /* over counted episodes */
+  int64_t sum_len2;
+  int64_t steps;         /* brs_monitor_update calls since the last reset */
+  double sum_ret;        /* over counted episodes */
+  double sum_ret2;
+  double min_ret;        /* 0 while no episode is counted */
+  double max_ret;
+  double running_ret;    /* sum of the returns of the episodes still running */
+  int32_t min_len;       /* 0 while no episode is counted */
+  int32_t max_len;
+  int32_t first_running; /* envs whose first episode has not ended */
+  int32_t pending;       /* envs with target[i] > 0 that have not reached it; n without targets */
+} brs_episode_stats;
+
+/* max_len: the histogram has bins 1..max_len and bin 0 for longer episodes; log_capacity: rows of the episode log */
+int brs_monitor_create(int32_t device, int32_t n, int32_t max_len, int32_t log_capacity, brs_monitor** out);
+int brs_monitor_destroy(brs_monitor*);
+const char* brs_monitor_last_error(const brs_monitor*);
+/* zeroes everything, running episodes included (the caller resets the simulator with it).  targets_host NULL = unlimited;
+ * else n entries, each >= 0, their sum <= log_capacity.  Waits for the stream. */
+int brs_monitor_reset(brs_monitor*, const int32_t* targets_host, void* stream);
+/* one env step of all n envs; only enqueues, no allocation */
+int brs_monitor_update(brs_monitor*, const float* reward_dev, const uint8_t* terminated_dev,
+                       const uint8_t* truncated_dev, void* stream);
+/* reduce kernel + one small device-to-host copy; waits for the stream */
+int brs_monitor_stats(brs_monitor*, brs_episode_stats* out_host, void* stream);
+/* hist_host has max_len + 1 entries */
+int brs_monitor_histogram(brs_monitor*, int64_t* hist_host, void* stream);
+/* the sum(targets) rows of the log: episode k of env i is row base[i] + k, base = exclusive prefix sum of the targets;
+ * a row that is not filled yet has length 0 */
+int brs_monitor_episodes(brs_monitor*, int32_t* env_host, double* ret_host, int32_t* len_host,
+                         uint8_t* time_limit_host, void* stream);
 
 #ifdef __cplusplus
 }

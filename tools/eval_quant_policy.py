@@ -19,32 +19,25 @@ import numpy as np
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from balance_robot_mujoco_rl_amd import BatchedSim, QuantModel, QuantPolicy, _lib, quantize_policy  # noqa: E402
+from balance_robot_mujoco_rl_amd import BatchedSim, EpisodeMonitor, QuantModel, QuantPolicy, _lib, quantize_policy  # noqa: E402
 from balance_robot_mujoco_rl_amd.policy import DevicePolicy  # noqa: E402
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "robot_move_policy.npz")
 
 
 def evaluate(env, n, steps, act, seed=123):
-    """deterministic evaluation with auto-reset; act(obs, t) -> actions [n, 2]"""
+    """deterministic evaluation with auto-reset; act(obs, t) -> actions [n, 2].  Every episode that ends within `steps` steps
+    counts (an EpisodeMonitor without targets)"""
     sim = BatchedSim(env, n, device=0, seed=seed, auto_reset=True)
-    obs = sim.reset().clone()
-    ep_len = torch.zeros(n, device=sim.device); lens = []; ntr = nte = 0
-    ever = torch.zeros(n, dtype=torch.bool, device=sim.device)
-    ret = torch.zeros(n, device=sim.device); total_reward = 0.0
+    mon = EpisodeMonitor(n, device=0, max_len=sim.max_episode_steps)
+    obs = sim.reset()
     for t in range(steps):
-        o, r, te, tr, _ = sim.step(act(obs, t))
-        ep_len += 1; ret += r
-        done = (te | tr).bool()
-        if done.any():
-            lens.append(ep_len[done].clone()); ntr += int((tr.bool() & ~te.bool()).sum()); nte += int(te.bool().sum()); ep_len[done] = 0; ever |= done
-        obs = o.clone()
-    total_reward = float(ret.sum()) / (n * steps)
-    lens = torch.cat(lens) if lens else torch.zeros(0)
-    sim.close()
-    return dict(episodes=int(lens.numel()), first_episode_still_running=int((~ever).sum()), fell=nte, reached_time_limit=ntr,
-                mean_ep_len=float(lens.mean()) if lens.numel() else None, median_ep_len=float(lens.median()) if lens.numel() else None,
-                mean_reward_per_step=total_reward)
+        obs, r, te, tr, _ = sim.step(act(obs, t))
+        mon.update(r, te, tr)
+    s, median = mon.stats(), mon.median_len(lower=True)
+    sim.close(); mon.close()
+    return dict(episodes=s.episodes, first_episode_still_running=s.first_running, fell=s.terminated, reached_time_limit=s.time_limit,
+                mean_ep_len=s.mean_len, median_ep_len=median, mean_reward_per_step=(s.sum_ret + s.running_ret) / (n * steps))
 
 
 def main():

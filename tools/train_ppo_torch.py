@@ -13,7 +13,7 @@ import torch.distributed as dist
 import torch.nn as nn
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from balance_robot_mujoco_rl_amd import BatchedSim
+from balance_robot_mujoco_rl_amd import BatchedSim, EpisodeMonitor, evaluate_policy
 
 
 def flat_params(model):
@@ -86,7 +86,8 @@ class MixedSim:
 
 
 def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, log, tag, ent=0.0, reward_clip=None,
-          critic_warmup=0, lr_end=None, norm_returns=False, target_kl=None, device_rollout=False, seed=0, env_index_base=0):
+          critic_warmup=0, lr_end=None, norm_returns=False, target_kl=None, device_rollout=False, seed=0, env_index_base=0,
+          after_iter=None):
     n = sim.n
     dev = sim.device
     pol = None
@@ -95,6 +96,8 @@ def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, 
         pol = DevicePolicy(device=dev.index, seed=seed, env_index_base=env_index_base)
         a_buf = torch.zeros((n, 2), device=dev); start = torch.ones(n, dtype=torch.uint8, device=dev)
         S = torch.zeros((n_steps, n), dtype=torch.uint8, device=dev); gstep = 0
+        mon = EpisodeMonitor(n, device=dev.index)   # episode returns and lengths stay on the device: read once per iteration
+        seen = (0, 0.0, 0)
     obs = sim.reset().clone()
     ep_len = torch.zeros(n, device=dev); ep_ret = torch.zeros(n, device=dev)
     done_len_sum = done_ret_sum = done_cnt = 0.0
@@ -113,6 +116,7 @@ def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, 
                     B["obs"][t] = obs; S[t] = start
                     pol.act(B["obs"][t], gstep, out=(B["act"][t], a_buf, B["logp"][t], B["val"][t])); gstep += 1
                     o, r, te, tr, to = sim.step(a_buf)
+                    mon.update(r, te, tr)   # the env's own reward, before the clip and the bootstrap
                     done = (te | tr).bool()
                     B["rew"][t] = r if reward_clip is None else r.clamp(max=reward_clip)
                     pol.bootstrap(to, te, tr, gamma, B["rew"][t])   # rew += gamma V(terminal_obs) where truncated only
@@ -128,12 +132,16 @@ def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, 
                     # learner-side reward clipping (a TransformReward-style wrapper); logged returns stay the env's own
                     B["rew"][t] = r if reward_clip is None else r.clamp(max=reward_clip)
                     B["done"][t] = done.float(); B["boot"][t] = boot
-                ep_len += 1; ep_ret += r
-                if done.any():
-                    done_len_sum += ep_len[done].sum().item(); done_ret_sum += ep_ret[done].sum().item(); done_cnt += done.sum().item()
-                    ep_len[done] = 0; ep_ret[done] = 0
+                if pol is None:
+                    ep_len += 1; ep_ret += r
+                    if done.any():
+                        done_len_sum += ep_len[done].sum().item(); done_ret_sum += ep_ret[done].sum().item(); done_cnt += done.sum().item()
+                        ep_len[done] = 0; ep_ret[done] = 0
                 obs = o.clone()
             if pol is not None:
+                st = mon.stats()   # sums since the start of the phase: this iteration's episodes are the difference
+                done_len_sum += st.sum_len - seen[0]; done_ret_sum += st.sum_ret - seen[1]; done_cnt += st.episodes - seen[2]
+                seen = (st.sum_len, st.sum_ret, st.episodes)
                 adv, ret = gae_kernel(B["rew"], B["val"], S, pol.value(obs), start, gamma, lam)
             else:
                 last_v = model.value(obs)
@@ -196,33 +204,54 @@ def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, 
             if (it % 10 == 0 or it == iters - 1) and (not dist.is_initialized() or dist.get_rank() == 0):
                 print(json.dumps(row), flush=True)
             done_len_sum = done_ret_sum = done_cnt = 0.0
+        if after_iter is not None:
+            after_iter(it, model)
+    if pol is not None:
+        mon.close()
     return total
 
 
 @torch.no_grad()
 def evaluate(env_id, model, n, steps, seed=123, device=0):
     """deterministic policy (mean action) on fresh envs: episode-length statistics and the share of episodes that
-    run into the time limit (= balanced for the whole episode)"""
+    run into the time limit (= balanced for the whole episode).  Every episode that ends within `steps` steps counts (an
+    EpisodeMonitor without targets; evaluate_policy is the SB3 measure with a quota per env)"""
     sim = BatchedSim(env_id, n, device=0, seed=seed, auto_reset=True)
-    obs = sim.reset().clone()
-    ep_len = torch.zeros(n, device=sim.device); ep_ret = torch.zeros(n, device=sim.device)
-    lens, rets, ntrunc, nterm = [], [], 0, 0
-    ever_done = torch.zeros(n, dtype=torch.bool, device=sim.device)
+    mon = EpisodeMonitor(n, device=0, max_len=sim.max_episode_steps)
+    obs = sim.reset()
     for _ in range(steps):
-        o, r, te, tr, _to = sim.step(model.pi(obs).clamp(-1, 1).contiguous())
-        ep_len += 1; ep_ret += r
-        done = (te | tr).bool()
-        if done.any():
-            lens.append(ep_len[done].clone()); rets.append(ep_ret[done].clone())
-            ntrunc += int((tr.bool() & ~te.bool()).sum()); nterm += int(te.bool().sum())
-            ep_len[done] = 0; ep_ret[done] = 0; ever_done |= done
-        obs = o.clone()
-    still = int((~ever_done).sum())   # first episode still running after `steps` steps
-    sim.close()
-    lens = torch.cat(lens) if lens else torch.zeros(0); rets = torch.cat(rets) if rets else torch.zeros(0)
-    return dict(env=env_id, envs=n, steps=steps, episodes=int(lens.numel()), first_episode_still_running=still, reached_time_limit=ntrunc, fell=nterm,
-                frac_reached_time_limit=ntrunc / max(1, ntrunc + nterm), mean_ep_len=float(lens.mean()) if lens.numel() else None,
-                median_ep_len=float(lens.median()) if lens.numel() else None, mean_ep_ret=float(rets.mean()) if rets.numel() else None)
+        obs, r, te, tr, _to = sim.step(model.pi(obs).clamp(-1, 1).contiguous())
+        mon.update(r, te, tr)
+    s, median = mon.stats(), mon.median_len(lower=True)
+    sim.close(); mon.close()
+    return dict(env=env_id, envs=n, steps=steps, episodes=s.episodes, first_episode_still_running=s.first_running,
+                reached_time_limit=s.time_limit, fell=s.terminated, frac_reached_time_limit=s.time_limit / max(1, s.time_limit + s.terminated),
+                mean_ep_len=s.mean_len, median_ep_len=median, mean_ep_ret=s.mean_ret)
+
+
+class EvalCallback:
+    """SB3's EvalCallback in small (src/sb_rl.py:536-543): every `every` iterations the deterministic policy plays `episodes`
+    episodes (evaluate_policy) on a fresh simulator of fixed seed, so that successive evaluations start from the same states;
+    the weights with the best mean return so far are saved to `save_best`"""
+
+    def __init__(self, env_id, every, episodes, envs, save_best="", device=0, seed=123):
+        self.env_id, self.every, self.episodes, self.envs, self.save_best = env_id, every, episodes, envs, save_best
+        self.device, self.seed, self.best, self.rows = device, seed, None, []
+
+    @torch.no_grad()
+    def __call__(self, it, model):
+        if self.every <= 0 or (it + 1) % self.every:
+            return
+        sim = BatchedSim(self.env_id, self.envs, device=self.device, seed=self.seed, auto_reset=True)
+        mean, std = evaluate_policy(lambda obs, t: model.pi(obs).clamp(-1, 1).contiguous(), sim, n_eval_episodes=self.episodes)
+        sim.close()
+        best = self.best is None or mean > self.best
+        if best:
+            self.best = mean
+            if self.save_best:
+                torch.save(model.state_dict(), self.save_best)
+        self.rows.append(dict(env=self.env_id, iter=it, eval_episodes=self.episodes, mean_ret=mean, std_ret=std, new_best=best))
+        print(json.dumps(self.rows[-1]), flush=True)
 
 
 def main():
@@ -249,6 +278,9 @@ def main():
     ap.add_argument("--reward-clip", type=float, default=None, help="learner-side upper clip of the per-step reward")
     ap.add_argument("--eval-steps", type=int, default=0, help="after training: deterministic evaluation for this many steps")
     ap.add_argument("--eval-envs", type=int, default=4096)
+    ap.add_argument("--eval-every", type=int, default=0, help="during training: evaluate_policy every this many iterations (rank 0)")
+    ap.add_argument("--eval-episodes", type=int, default=1024, help="... over this many episodes, spread over --eval-envs envs")
+    ap.add_argument("--save-best", default="", help="... and write the weights here whenever the mean return improves")
     ap.add_argument("--device-rollout", action="store_true",
                     help="act, bootstrap and GAE with the HIP kernels of include/brs_policy.h instead of torch ops")
     ap.add_argument("--obs-init-scale", default="", help="comma-separated factors on the INITIAL first-layer weights per observation "
@@ -277,7 +309,7 @@ def main():
     torch.manual_seed(1000 * (a.seed + 1) + rank)   # ... different action noise
     base = rank * a.envs
     opt = torch.optim.Adam(model.parameters(), lr=a.lr)
-    log = []
+    log, callbacks = [], []
     for phase, (env_id, iters) in enumerate(((a.env, a.iters), (a.then, a.iters2))):
         if not env_id:
             continue
@@ -299,9 +331,14 @@ def main():
             env_id = f"{a.env}+{env_id}"
         else:
             sim = BatchedSim(env_id, a.envs, device=local, seed=2 * a.seed, env_index_base=base, auto_reset=True)
+        cb = None
+        if a.eval_every > 0 and rank == 0:   # the phase's own env id (the second phase of a mix: the new one)
+            cb = EvalCallback((a.env, a.then)[phase], a.eval_every, a.eval_episodes, min(a.eval_envs, a.eval_episodes), a.save_best, local)
+            callbacks.append(cb)
         train(sim, model, opt, iters, a.n_steps, a.epochs, a.minibatch, a.gamma, a.lam, 0.2, log, env_id, a.ent, a.reward_clip,
               warm, a.lr2_end if phase == 1 else None, a.norm_returns or (phase == 1 and a.norm_returns2),
-              a.target_kl2 if (phase == 1 and a.target_kl2 is not None) else a.target_kl, a.device_rollout, 1000 * (a.seed + 1) + phase, base)
+              a.target_kl2 if (phase == 1 and a.target_kl2 is not None) else a.target_kl, a.device_rollout, 1000 * (a.seed + 1) + phase, base,
+              after_iter=cb)
         sim.close()
     evals = []
     if world > 1:
@@ -314,7 +351,8 @@ def main():
     if a.save:
         torch.save(model.state_dict(), a.save)
     if a.out:
-        json.dump(dict(args=vars(a), world_size=world, log=log, eval=evals), open(a.out, "w"), indent=1)
+        json.dump(dict(args=vars(a), world_size=world, log=log, eval=evals, eval_during_training=[r for c in callbacks for r in c.rows]),
+                  open(a.out, "w"), indent=1)
     if world > 1:
         dist.destroy_process_group()
 
