@@ -89,6 +89,12 @@ def skip_mask(out_s, out_t, aux_s, aux_t):
     return done | (np.isnan(aux_s[:, 1]) != np.isnan(aux_t[:, 1]))
 
 
+def timer_mask(out_s, out_t, aux_s, aux_t):
+    """skip_mask without the finished episodes, for runs with auto-reset off: nothing is re-drawn there, and robots that
+    have fallen (and so terminate at every step) are what such a run is about"""
+    return np.isnan(aux_s[:, 1]) != np.isnan(aux_t[:, 1])
+
+
 def contact_pairs(orc, ctrl):
     """body pairs of the oracle's contact list for its one env, as the campaign tools print them"""
     return sorted((int(c["body1"]), int(c["body2"])) for c in orc.forward(env=0, ctrl=(float(ctrl[0]), float(ctrl[1])))["contacts"])
@@ -102,9 +108,10 @@ def reference_policy():
     return lambda o: qp.act(torch.from_numpy(np.ascontiguousarray(o, dtype=np.float32)), "mean").numpy()
 
 
-def env_steps(teacher, student, steps, actions, rng, obs=None):
+def env_steps(teacher, student, steps, actions, rng, obs=None, skip=skip_mask):
     """teacher-forced FULL env steps, one record per step: t, pre (the forced state), act, out_s / out_t (step outputs),
-    post_s / post_t (get_state after the step), aux_s / aux_t (after the step), skip (skip_mask).  actions: "zero", "random"
+    post_s / post_t (get_state after the step), aux_s / aux_t (after the step), skip (skip_mask, or timer_mask where a run
+    with auto-reset off asks for it).  actions: "zero", "random"
     (U(-1,1)^2 from rng, one draw per step), "policy" (reference_policy on the teacher's observations) or a callable
     (t, n, rng, teacher_obs) -> float32 [n, 2].  obs: the teacher's observations before the first step.  Nothing is reset here"""
     n = teacher.n
@@ -119,7 +126,7 @@ def env_steps(teacher, student, steps, actions, rng, obs=None):
         obs, aux_s, aux_t = out_t[0], student.get_aux(), teacher.get_aux()
         yield types.SimpleNamespace(t=t, pre=pre, act=act, out_s=out_s, out_t=out_t, aux_s=aux_s, aux_t=aux_t,
                                     post_s=student.get_state(), post_t=teacher.get_state(),
-                                    skip=skip_mask(out_s, out_t, aux_s, aux_t))
+                                    skip=skip(out_s, out_t, aux_s, aux_t))
 
 
 def round_ctrl(ctrl, student):

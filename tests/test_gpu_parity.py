@@ -119,6 +119,12 @@ def test_constructed_floor_contact_states_on_the_hip_path():
     cs.check_hip_caps("floor", *cs.run_scenario_on("hip", "floor"))
 
 
+def test_constructed_pinned_block_states_on_the_hip_path():
+    """block lying on the floor and pushed against the standing robot (wheel barrel, torso face, a wheel's inner side):
+    robot<->floor, block<->floor and block<->robot contacts in the same solve"""
+    cs.check_hip_caps("pinned", *cs.run_scenario_on("hip", "pinned"))
+
+
 def test_round3_outlier_states_stay_fixed_on_the_hip_path():
     """tests/golden/round3_outlier_states.json: the env-steps round 3's campaigns found above 1e-4 (block quaternion 2.4-2.7e-4),
     replayed on the HIP path (250 fused substeps from the dumped pre-step state) against the oracle"""

@@ -82,6 +82,14 @@ def test_constructed_floor_contact_states(double, tol):
     assert np.quantile(err, 0.98) < tol and err.max() < 50 * tol, (np.quantile(err, 0.98), err.max())
 
 
+@pytest.mark.parametrize("double,tol", [(True, 1e-12), (False, 1e-5)])
+def test_constructed_pinned_block_states(double, tol):
+    """robot standing on the floor, block lying on the floor and pushed against a wheel's barrel, the torso's broad face or a
+    wheel's inner side: robot<->floor, block<->floor (4 points, the block-slot capacity) and block<->robot contacts at once"""
+    err, _ = cs.run_scenario_on("host64" if double else "host32", "pinned")
+    assert np.quantile(err, 0.98) < tol and err.max() < 50 * tol, (np.quantile(err, 0.98), err.max())
+
+
 @pytest.mark.parametrize("env_id,n,steps", [("Env03-v2", 384, 90), ("Env01-v2", 384, 90)])
 def test_float_build_stays_on_the_double_build_over_full_env_steps(env_id, n, steps):
     """kernel source in float vs in double, teacher-forced over full env steps with auto-reset (the bench workload's dynamics):

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests import constructed_states as cs, parity as P, test_gpu_parity as gp
+from tests import constructed_states as cs, parity as P, test_constructed_steps_gpu as st, test_gpu_parity as gp
 from tests.test_policy_kernels import _ref_gae
 
 pytestmark = pytest.mark.gpu
@@ -25,26 +25,33 @@ RUNTIME = dict(substeps=100, timestep=5e-5)   # a non-default timestep: the kern
 OUTPUTS = ("obs", "reward", "terminated", "truncated", "terminal_obs")
 
 # ---- A: every step kernel instantiation brs_step can launch (brs_kernels.hip: STEP_KERNELS, step_kernel_of) -> the tests
-# that run it.  Names in this module are checked to exist; "gp." names live in tests/test_gpu_parity.py.
+# that run it.  Names in this module are checked to exist; "gp." names live in tests/test_gpu_parity.py, "st." names in
+# tests/test_constructed_steps_gpu.py: every kernel has an owner there as well, which runs it on constructed contact states.
 _SHARED_RNG = "gp.test_env_step_parity_with_shared_rng"
+_FLOOR, _FLOOR_RT = "st.test_env01_step_kernels_on_floor_states", "st.test_env01_runtime_constant_step_kernels_on_floor_states"
+_BLOCKS = "st.test_env03_step_kernels_on_block_states"
+_MODULES = {"gp.": gp, "st.": st}
 KERNELS = {
     # Env01 family at 64 threads (the default): capped at 256 registers, two waves per SIMD
-    "brs_step_kernel_occ2<-1>": {"gp.test_runtime_parameter_kernel_with_non_default_timestep"},
-    "brs_step_kernel_occ2<0>": {_SHARED_RNG},
-    "brs_step_kernel_occ2<1>": {_SHARED_RNG, "test_c_uncapped_and_capped_env01_v2_kernels_on_the_same_inputs"},
-    "brs_step_kernel_occ2<4>": {_SHARED_RNG},
-    "brs_step_kernel_occ2<5>": {_SHARED_RNG},
+    "brs_step_kernel_occ2<-1>": {"gp.test_runtime_parameter_kernel_with_non_default_timestep", _FLOOR_RT},
+    "brs_step_kernel_occ2<0>": {_SHARED_RNG, _FLOOR},
+    "brs_step_kernel_occ2<1>": {_SHARED_RNG, "test_c_uncapped_and_capped_env01_v2_kernels_on_the_same_inputs", _FLOOR,
+                                "st.test_robots_that_stay_down_through_brs_step"},
+    "brs_step_kernel_occ2<4>": {_SHARED_RNG, _FLOOR},
+    "brs_step_kernel_occ2<5>": {_SHARED_RNG, _FLOOR},
     # Env03 family: the same kernel at every workgroup size
-    "brs_step_kernel<true, -1>": {"test_b_env03_runtime_constant_kernel_bitwise_across_workgroup_sizes"},
-    "brs_step_kernel<true, 2>": {"test_b_env03_folded_kernels_bitwise_across_workgroup_sizes"},
-    "brs_step_kernel<true, 3>": {"test_b_env03_folded_kernels_bitwise_across_workgroup_sizes"},
+    "brs_step_kernel<true, -1>": {"test_b_env03_runtime_constant_kernel_bitwise_across_workgroup_sizes", _BLOCKS},
+    "brs_step_kernel<true, 2>": {"test_b_env03_folded_kernels_bitwise_across_workgroup_sizes", _BLOCKS},
+    "brs_step_kernel<true, 3>": {"test_b_env03_folded_kernels_bitwise_across_workgroup_sizes", _BLOCKS,
+                                 "st.test_env03_step_kernel_on_tiled_block_states_at_256_threads",
+                                 "st.test_robots_that_stay_down_through_brs_step", "st.test_lane_map_on_constructed_populations"},
     # Env01 family without the register cap: block_threads != 64, or BRS_ENV01_OCC1=1
-    "brs_step_kernel<false, -1>": {"test_c_uncapped_runtime_constant_kernel_vs_oracle"},
-    "brs_step_kernel<false, 0>": {"test_c_uncapped_env01_kernels_vs_oracle"},
+    "brs_step_kernel<false, -1>": {"test_c_uncapped_runtime_constant_kernel_vs_oracle", _FLOOR_RT},
+    "brs_step_kernel<false, 0>": {"test_c_uncapped_env01_kernels_vs_oracle", _FLOOR},
     "brs_step_kernel<false, 1>": {"test_c_uncapped_env01_kernels_vs_oracle", "test_c_occ1_switch_launches_the_128_thread_kernel",
-                                  "test_c_uncapped_and_capped_env01_v2_kernels_on_the_same_inputs"},
-    "brs_step_kernel<false, 4>": {"test_c_uncapped_env01_kernels_vs_oracle"},
-    "brs_step_kernel<false, 5>": {"test_c_uncapped_env01_kernels_vs_oracle"},
+                                  "test_c_uncapped_and_capped_env01_v2_kernels_on_the_same_inputs", _FLOOR},
+    "brs_step_kernel<false, 4>": {"test_c_uncapped_env01_kernels_vs_oracle", _FLOOR},
+    "brs_step_kernel<false, 5>": {"test_c_uncapped_env01_kernels_vs_oracle", _FLOOR},
 }
 
 
@@ -81,9 +88,10 @@ def test_a_every_step_kernel_is_in_the_ledger_and_every_geometry_launches_a_know
         seen.add(name)
     assert seen == set(KERNELS), f"launched but not in the ledger: {seen - set(KERNELS)}; in the ledger, never launched: {set(KERNELS) - seen}"
     assert len(KERNELS) == 13
-    for owners in KERNELS.values():
+    for kernel, owners in KERNELS.items():
         for t in owners:
-            assert callable(getattr(gp, t[3:], None) if t.startswith("gp.") else globals().get(t)), f"the ledger names a missing test {t}"
+            assert callable(getattr(_MODULES[t[:3]], t[3:], None) if t[:3] in _MODULES else globals().get(t)), f"the ledger names a missing test {t}"
+        assert any(t.startswith("st.") for t in owners), f"no test runs {kernel} on constructed contact states"
     # workgroup sizes brs_create refuses
     for bt in (32, 100, 320, 512):
         with pytest.raises(BrsError, match="block_threads"):
@@ -161,11 +169,7 @@ def test_b_env03_runtime_constant_kernel_bitwise_across_workgroup_sizes():
         s.close()
 
 
-def _tile(m, n, seed):
-    """indices of n states drawn from m: whole random permutations of the m, one after another, cut at n (no two waves hold
-    the same states at the same lanes)"""
-    rng = np.random.default_rng(seed)
-    return np.concatenate([rng.permutation(m) for _ in range(-(-n // m))])[:n]
+_tile = cs.tile
 
 
 def _physics_bitwise(env_id, qpos, qvel, ctrl, nsub):
@@ -190,7 +194,7 @@ def _coupled_in_every_wave(qpos, qvel):
     assert (per_wave > 0).all(), per_wave
 
 
-@pytest.mark.parametrize("which,n", [("block_robot", 96 * 3 + 37), ("edge_edge", 64 * 5 + 37)])
+@pytest.mark.parametrize("which,n", [("block_robot", 96 * 3 + 37), ("edge_edge", 64 * 5 + 37), ("pinned", 96 * 3 + 37)])
 def test_b_env03_physics_on_constructed_contact_states_across_workgroup_sizes(which, n):
     """constructed block<->robot states tiled so that every wave of every workgroup holds coupled contacts: bit-identical at
     every size, and within the oracle caps of test_constructed_*_on_the_hip_path at 256 threads"""
