@@ -986,16 +986,28 @@ template <typename R, bool BLK> struct Sim {
       }
       if (!sep) {
         BRS_MARK("cc_branch");
+        // Both cases leave their patch behind in ONE form, and one tail (patch_begin, then the insertion loop) takes it up: the
+        // unit normal `nrm`, candidates (u, v, g) parked in the lane's scratch words, the mask `keep` of those that are patch
+        // points, and the affine map  pos = A0 + u A1 + v A2 + (half + g/2) A3  back to the torso geom frame.  The two cases
+        // exclude each other per lane, but a wave that holds a lane of each walks both arms: whatever stands in both is paid twice.
+        R A0[3], A1[3], A2[3], A3[3], nrm[3], half;
+        uint32_t keep;
+        R* scr = st.base + (SLOT_ROBOT * SLOT_WORDS) * st.stride;
+        // the fp64 poses, once per substep for both cases (sat15_f64 keeps its own: rare and out of line); last read by the fp64
+        // decisions of the face case
+        double T64[9], B64[9];
+        {
+          double qT[4] = {S.q[0], S.q[1], S.q[2], S.q[3]}, qB[4] = {S.bq[0], S.bq[1], S.bq[2], S.bq[3]};
+          quat2mat_(qT, T64); quat2mat_(qB, B64);
+        }
+        const double d64[3] = {S.bp[0] - S.p[0], S.bp[1] - S.p[1], S.bp[2] - S.p[2]};
         if (use_edge) {
           const int i = axE / 3, j = axE - 3 * i;
           const int i1 = i == 2 ? 0 : i + 1, i2 = i == 0 ? 2 : i - 1;
           // the separation along the chosen edge axis L = e_i x b_j once more from the fp64 poses: it is the distance of the
           // patch's only point, and `< margin` decides whether that point exists in this substep (like the face case below;
-          // the axis itself is the fp32 choice).  ~90 fp64 operations, only for lanes in the edge case.
+          // the axis itself is the fp32 choice).  ~50 fp64 operations, only for lanes in the edge case.
           {
-            double qT[4] = {S.q[0], S.q[1], S.q[2], S.q[3]}, qB[4] = {S.bq[0], S.bq[1], S.bq[2], S.bq[3]}, T64[9], B64[9];
-            quat2mat_(qT, T64); quat2mat_(qB, B64);
-            const double d64[3] = {S.bp[0] - S.p[0], S.bp[1] - S.p[1], S.bp[2] - S.p[2]};
             const int j1 = j == 2 ? 0 : j + 1, j2 = j == 0 ? 2 : j - 1;
             auto colT = [&](int a, double* o) { o[0] = pick3(a, T64[0], T64[1], T64[2]); o[1] = pick3(a, T64[3], T64[4], T64[5]); o[2] = pick3(a, T64[6], T64[7], T64[8]); };
             auto colB = [&](int a, double* o) { o[0] = pick3(a, B64[0], B64[1], B64[2]); o[1] = pick3(a, B64[3], B64[4], B64[5]); o[2] = pick3(a, B64[6], B64[7], B64[8]); };
@@ -1010,7 +1022,7 @@ template <typename R, bool BLK> struct Sim {
           }
           const bool edge_in = bestE64 < P.margin_d[CC_BLOCK_ROBOT];
           bestE = (R)bestE64;
-          if (edge_in) {
+          {
             R bj[3] = {pick3(j, RTB[0], RTB[1], RTB[2]), pick3(j, RTB[3], RTB[4], RTB[5]), pick3(j, RTB[6], RTB[7], RTB[8])};
             const R bji = pick3(i, bj), bji1 = pick3(i1, bj), bji2 = pick3(i2, bj);
             const R lenE2 = bji1 * bji1 + bji2 * bji2;  // = 1 - bji^2 without the cancellation
@@ -1041,18 +1053,20 @@ template <typename R, bool BLK> struct Sim {
             R pos[3];
 #pragma unroll
             for (int m = 0; m < 3; m++) pos[m] = (R)0.5 * (pA[m] + (m == i ? al : (R)0) + pB[m] + be * bj[m]);
-            pos[2] += P.torso_cz;
-            Patch Q;
-            R V0[3], W0[3];
-            patch_begin(st, F, S, L, Q, V0, W0);
-            add_patch_point(P, st, F, Q, V0, W0, pos, bestE);
+            // the one point as candidate 0 = (0, 0, bestE) of a map with A0 = pos and nothing else: the tail gets pos back
+            // bit for bit, adds torso_cz to its z, and bestE is the point's distance
+#pragma unroll
+            for (int m = 0; m < 3; m++) { A0[m] = pos[m]; A1[m] = 0; A2[m] = 0; A3[m] = 0; nrm[m] = L[m]; }
+            half = 0;
+            keep = edge_in ? 1u : 0u;
+            scr[0] = 0; scr[st.stride] = 0; scr[2 * st.stride] = bestE;
           }
         } else {
           // face case.  Reference frame coordinates (u, v, g): u, v span the reference rectangle |u| <= ra, |v| <= rb, g is
           // the signed distance to the reference face.  Incident face = centre Cc +- H1 +- H2 in those coordinates; a
           // candidate (u, v, g) maps back to the torso geom frame as  pos = u A1 + v A2 + (half + g/2) A3 + A0.
           BRS_MARK("cc_face_setup");
-          R Cc[3], H1[3], H2[3], A0[3], A1[3], A2[3], A3[3], nrm[3], ra, rb, half;
+          R Cc[3], H1[3], H2[3], ra, rb;
           // The NORMAL components of the incident face (centre and half edges along the reference normal) once more, from
           // the fp64 poses: every candidate's signed distance g is affine in these three numbers, and g < margin decides
           // whether a patch point exists in this substep -- in fp32 its rounding (~1e-8 m) put points of the patch one
@@ -1060,9 +1074,6 @@ template <typename R, bool BLK> struct Sim {
           double Cc2, H12, H22, fsg = 1.0, fsj = 1.0;
           int fsel = 0;
           {
-            double qT[4] = {S.q[0], S.q[1], S.q[2], S.q[3]}, qB[4] = {S.bq[0], S.bq[1], S.bq[2], S.bq[3]}, T64[9], B64[9];
-            quat2mat_(qT, T64); quat2mat_(qB, B64);
-            const double d64[3] = {S.bp[0] - S.p[0], S.bp[1] - S.p[1], S.bp[2] - S.p[2]};
             const double cz = P.torso_cz_d, sd = P.block_s_d;
             const double sTd[3] = {P.torso_s_d[0], P.torso_s_d[1], P.torso_s_d[2]};
             if (axF < 3) {
@@ -1210,7 +1221,7 @@ template <typename R, bool BLK> struct Sim {
           // keep the PATCH_MAX = 6 deepest (ties: lower candidate index).  tau = 6th smallest valid g from a sorting network
           // (sorted groups of 4, bitonic merges to two sorted octets, low half of their merge) -- branch-free inside: a
           // per-lane selection loop would cost every lane its worst case
-          uint32_t keep = vmask;
+          keep = vmask;
           if (__builtin_popcount(vmask) > PATCH_MAX) {  // rare with 6 slots: a wave usually skips the network
             R k_[16];
 #pragma unroll
@@ -1256,8 +1267,6 @@ template <typename R, bool BLK> struct Sim {
             keep = __builtin_popcount(vmask) > PATCH_MAX ? kp : keep;
           }
           BRS_MARK("cc_scatter");
-          const int nkeep = (int)__builtin_popcount(keep);
-          R* scr = st.base + (SLOT_ROBOT * SLOT_WORDS) * st.stride;
           // all 16 candidates parked at FIXED words of the (not yet written) robot<->floor slot region -- 48 stores at immediate
           // offsets, no address arithmetic; the insertion loop walks `keep` by bit scan (ascending candidate index = rank order)
           static_assert(16 * 3 <= N_ROBOT_SLOTS * SLOT_WORDS, "the candidate scratch must fit the robot<->floor slot region");
@@ -1265,21 +1274,22 @@ template <typename R, bool BLK> struct Sim {
           for (int q = 0; q < 16; q++) {
             scr[(3 * q) * st.stride] = cu_[q]; scr[(3 * q + 1) * st.stride] = cv_[q]; scr[(3 * q + 2) * st.stride] = gq[q];
           }
-          BRS_MARK("cc_insert");
-          if (nkeep > 0) {
-            Patch Q;
-            R V0[3], W0[3];
-            patch_begin(st, F, S, nrm, Q, V0, W0);  // one contact frame for the whole patch
-            uint32_t walk = keep;
-            for (int r = 0; r < nkeep; r++) {
-              const int qi = __builtin_ctz(walk);
-              walk &= walk - 1u;
-              const R u = scr[(3 * qi) * st.stride], v = scr[(3 * qi + 1) * st.stride], g = scr[(3 * qi + 2) * st.stride];
-              const R wv = half + (R)0.5 * g;
-              R pos[3] = {A0[0] + u * A1[0] + v * A2[0] + wv * A3[0], A0[1] + u * A1[1] + v * A2[1] + wv * A3[1],
-                          A0[2] + u * A1[2] + v * A2[2] + wv * A3[2] + P.torso_cz};
-              add_patch_point(P, st, F, Q, V0, W0, pos, g);
-            }
+        }
+        BRS_MARK("cc_insert");
+        const int nkeep = (int)__builtin_popcount(keep);
+        if (nkeep > 0) {
+          Patch Q;
+          R V0[3], W0[3];
+          patch_begin(st, F, S, nrm, Q, V0, W0);  // one contact frame for the whole patch
+          uint32_t walk = keep;
+          for (int r = 0; r < nkeep; r++) {
+            const int qi = __builtin_ctz(walk);
+            walk &= walk - 1u;
+            const R u = scr[(3 * qi) * st.stride], v = scr[(3 * qi + 1) * st.stride], g = scr[(3 * qi + 2) * st.stride];
+            const R wv = half + (R)0.5 * g;
+            R pos[3] = {A0[0] + u * A1[0] + v * A2[0] + wv * A3[0], A0[1] + u * A1[1] + v * A2[1] + wv * A3[1],
+                        A0[2] + u * A1[2] + v * A2[2] + wv * A3[2] + P.torso_cz};
+            add_patch_point(P, st, F, Q, V0, W0, pos, g);
           }
         }
       }
