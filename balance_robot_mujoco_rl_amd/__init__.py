@@ -12,16 +12,20 @@ include/brs.h (libbrs_hip.so).  This package is the host-side mirror of the refe
     monitor.EpisodeMonitor / evaluate_policy
                                            SB3's Monitor and evaluate_policy (sb_rl.py:501, 536-543): episode returns and lengths
                                            accumulated by a HIP kernel per env step (include/brs_policy.h: brs_monitor_*)
+    learner.DevicePPOLearner               SB3's PPO.train() minibatch body -- clipped-surrogate gradient, clip_grad_norm_, Adam -- as HIP
+                                           kernels (include/brs_policy.h: brs_learner_*): the learner side of sb_rl.py:552-556
     quant.quantize_policy / QuantPolicy    int8 post-training quantisation of the actor and the int8 network as a HIP kernel
                                            (include/brs_qpolicy.h): quantize_tflite.py and sb_rl.py:285-364 on the GPU
 
 There is no CPU fallback: creating a sim without a HIP device raises.
 """
 from .registry import ENV_SPECS, make_vec, spec  # noqa: F401
+from .learner import DevicePPOLearner, LearnerStats  # noqa: F401
 from .monitor import EpisodeMonitor, EpisodeStats, episode_count_targets, evaluate_policy  # noqa: F401
 from .quant import REFERENCE_CALIBRATION, QuantModel, QuantPolicy, quantize_policy  # noqa: F401
 from .sim import BatchedSim, BrsError  # noqa: F401
 from .vec_env import BalanceVecEnv  # noqa: F401
 
-__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "QuantModel", "QuantPolicy",
+__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "DevicePPOLearner", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "LearnerStats",
+           "QuantModel", "QuantPolicy",
            "REFERENCE_CALIBRATION", "episode_count_targets", "evaluate_policy", "make_vec", "quantize_policy", "spec"]

@@ -22,10 +22,10 @@ SIM_FLAGS = ["-Xarch_device", "-ffast-math", "-Xarch_device", "-fgpu-flush-denor
              "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 # the translation units of libbrs_hip.so: (source, its own flags, in the build id).  Policy / GAE kernels, renderer and int8 actor
 # keep IEEE math (checked against fp32 torch at rtol 1e-5 / bit for bit against their host builds under tests/), and so does the
-# episode monitor; the build id names the step and policy kernels that committed profiles were measured on, so the other three
-# units stay out of it.
+# episode monitor and the PPO learner (fp64 torch autograd at 1e-5 per parameter block); the build id names the step and policy
+# kernels that committed profiles were measured on, so the other four units stay out of it.
 UNITS = [("brs_kernels.hip", SIM_FLAGS, True), ("brs_policy.hip", [], True), ("brs_render.hip", [], False), ("brs_qpolicy.hip", [], False),
-         ("brs_monitor.hip", [], False)]
+         ("brs_monitor.hip", [], False), ("brs_learner.hip", [], False)]
 SRC = os.path.join(_CSRC, UNITS[0][0])  # the unit that takes the A/B flags and the build id stamp
 # what the build id hashes next to the sources of its units; brs_host.hpp holds no kernel code and stays out of it
 HEADERS = [os.path.join(_CSRC, h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp")] + \
@@ -49,6 +49,20 @@ class BrsEpisodeStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("episodes", "ended", "terminated", "time_limit", "sum_len", "sum_len2", "steps")] + \
                [(k, C.c_double) for k in ("sum_ret", "sum_ret2", "min_ret", "max_ret", "running_ret")] + \
                [(k, C.c_int32) for k in ("min_len", "max_len", "first_running", "pending")]
+
+
+LEARNER_NSTAT = 5
+
+
+class BrsPpoConfig(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("lr", "beta1", "beta2", "eps")] + \
+               [(k, C.c_float) for k in ("clip_range", "vf_coef", "ent_coef", "max_grad_norm_pi", "max_grad_norm_vf", "target_kl", "ret_scale")] + \
+               [(k, C.c_int32) for k in ("normalize_adv", "actor_on", "joint_norm")]
+
+
+class BrsLearnerInfo(C.Structure):
+    _fields_ = [("steps", C.c_int64), ("stopped", C.c_int32), ("bad_index", C.c_int32), ("stat", C.c_float * LEARNER_NSTAT),
+                ("grad_norm_pi", C.c_float), ("grad_norm_vf", C.c_float)]
 
 
 class BrsQLayer(C.Structure):
@@ -145,6 +159,13 @@ SIGNATURES = {
         "brs_monitor_stats": (C.c_int, [_vp, C.POINTER(BrsEpisodeStats), _vp]),
         "brs_monitor_histogram": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp]),
         "brs_monitor_episodes": (C.c_int, [_vp, _i32p, _dp, _i32p, C.POINTER(C.c_uint8), _vp]),
+        "brs_learner_create": (C.c_int, [_i32, _i32, C.POINTER(_vp)]),
+        "brs_learner_destroy": (C.c_int, [_vp]),
+        "brs_learner_last_error": (C.c_char_p, [_vp]),
+        "brs_learner_begin_iteration": (C.c_int, [_vp, _vp]),
+        "brs_learner_grad": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(BrsPpoConfig), _vp, _vp]),
+        "brs_learner_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(BrsPpoConfig), _vp]),
+        "brs_learner_stats": (C.c_int, [_vp, C.POINTER(BrsLearnerInfo), _vp]),
     },
     "brs_render.h": {
         "brs_render_default_camera": (None, [C.POINTER(BrsCamera)]),

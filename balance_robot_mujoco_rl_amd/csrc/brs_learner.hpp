@@ -1,0 +1,157 @@
+// brs_learner.hpp -- the PPO learner of include/brs_policy.h, the part shared by the HIP kernels
+// (brs_learner.hip) and the host build the CPU tests hold against fp64 torch autograd (tests/learnerhost): everything that is
+// not a matrix product -- the per-sample loss heads, the order in which partial sums are combined, the clip scale and the Adam
+// update.  The towers themselves are MFMA code in the kernels and plain loops in the host build.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/brs.h"
+#include "../../include/brs_policy.h"
+
+#ifndef BRS_HD
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define BRS_HD __host__ __device__ __forceinline__
+#else
+#define BRS_HD inline
+#endif
+#endif
+
+namespace brs {
+namespace learner {
+
+constexpr int OBS = BRS_POLICY_OBS, HID = BRS_POLICY_HID, ACT = BRS_POLICY_ACT, NPARAM = BRS_POLICY_NPARAM, NSTAT = BRS_LEARNER_NSTAT;
+constexpr int OFF_PI = 0, OFF_VF = BRS_POLICY_NPI, OFF_LOGSTD = BRS_POLICY_NPI + BRS_POLICY_NVF;
+// inside a tower: W1[64][6] b1[64] W2[64][64] b2[64] W3[NOUT][64] b3[NOUT]
+constexpr int O_W1 = 0, O_B1 = O_W1 + HID * OBS, O_W2 = O_B1 + HID, O_B2 = O_W2 + HID * HID, O_W3 = O_B2 + HID;
+constexpr int CHUNK = 256;  // samples a workgroup takes per trip; workgroup g takes chunks g, g + G, ... of G workgroups
+// a partial row (one per workgroup): the gradient sums, the NSTAT stat sums, the count of bad indices
+constexpr int ROW = NPARAM + NSTAT + 1;
+constexpr int APPLY_THREADS = 1024, ADV_THREADS = 1024;
+enum { S_PL = 0, S_VL = 1, S_ENT = 2, S_KL = 3, S_CLIPFRAC = 4 };
+
+// ---- per-sample loss heads.  Everything carries the 1 / M of the minibatch mean, so that sums over samples are means.
+struct ActorHead {
+  float dmean[ACT];     // d loss / d mean
+  float dlog_std[ACT];  // this sample's share of d loss / d log_std
+  float pl, ent, kl, clipfrac;
+};
+
+// adv_n: the (normalised) advantage.  loss = -min(ratio adv, clamp(ratio) adv) - ent_coef entropy
+BRS_HD ActorHead actor_head(const float mean[ACT], const float log_std[ACT], const float act[ACT], float logp_old, float adv_n,
+                            const brs_ppo_config& c, float inv_m) {
+  ActorHead o;
+  float z[ACT], inv_sigma[ACT], lp = 0.0f, ent = 0.0f;
+  for (int k = 0; k < ACT; k++) {
+    inv_sigma[k] = expf(-log_std[k]);
+    z[k] = (act[k] - mean[k]) * inv_sigma[k];
+    lp += -0.5f * z[k] * z[k] - log_std[k] - 0.9189385332046727f;
+    ent += 1.4189385332046727f + log_std[k];  // 0.5 + 0.5 log(2 pi) + log sigma
+  }
+  const float lr = lp - logp_old, ratio = expf(lr);
+  const float clamped = fminf(fmaxf(ratio, 1.0f - c.clip_range), 1.0f + c.clip_range);
+  const float s1 = ratio * adv_n, s2 = clamped * adv_n;
+  o.pl = -fminf(s1, s2) * inv_m;
+  o.ent = ent * inv_m;
+  o.kl = ((ratio - 1.0f) - lr) * inv_m;
+  o.clipfrac = fabsf(ratio - 1.0f) > c.clip_range ? inv_m : 0.0f;
+  // the clamped branch has no gradient where the clamp is active, and where it is not the two branches are the same function
+  const float g_lp = (c.actor_on && s1 <= s2) ? -adv_n * ratio * inv_m : 0.0f;
+  for (int k = 0; k < ACT; k++) {
+    if (c.actor_on) {
+      o.dmean[k] = g_lp * z[k] * inv_sigma[k];
+      o.dlog_std[k] = g_lp * (z[k] * z[k] - 1.0f) - c.ent_coef * inv_m;
+    } else {
+      o.dmean[k] = 0.0f;
+      o.dlog_std[k] = 0.0f;
+    }
+  }
+  return o;
+}
+
+struct CriticHead {
+  float dvalue, vl;
+};
+
+// loss = vf_coef * 0.5 (v - ret / ret_scale)^2
+BRS_HD CriticHead critic_head(float value, float ret, const brs_ppo_config& c, float inv_m) {
+  const float d = value - ret / c.ret_scale;
+  return CriticHead{c.vf_coef * d * inv_m, 0.5f * d * d * inv_m};
+}
+
+BRS_HD ActorHead zero_actor_head() { return ActorHead{{0.0f, 0.0f}, {0.0f, 0.0f}, 0.0f, 0.0f, 0.0f, 0.0f}; }
+
+// ---- advantage mean and std of the minibatch: thread t of ADV_THREADS folds entries t, t + ADV_THREADS, ... in ascending
+// order into (sum, sum of squares) in fp64, the partials are combined by a tree of fixed pairing (tree_pairs below)
+BRS_HD void fold_adv(const float* adv, const int32_t* idx, int m, int n_rows, int t, double& s, double& ss) {
+  s = 0.0; ss = 0.0;
+  for (int i = t; i < m; i += ADV_THREADS) {
+    const int32_t row = idx[i];
+    if (row < 0 || row >= n_rows) continue;
+    const double a = (double)adv[row];
+    s += a; ss += a * a;
+  }
+}
+// -> out[0] = mean, out[1] = unbiased std + 1e-8: adv_n = (adv - out[0]) / out[1]
+BRS_HD void adv_mean_denom(double s, double ss, int m, float* out) {
+  const double mean = s / (double)m;
+  double var = (ss - (double)m * mean * mean) / (double)(m - 1);
+  if (var < 0.0) var = 0.0;
+  out[0] = (float)mean;
+  out[1] = (float)sqrt(var) + 1e-8f;
+}
+
+// ---- column `col` of the G partial rows, summed in ascending order of the workgroup
+BRS_HD float combine_rows(const float* partial, int G, int col) {
+  double s = 0.0;
+  for (int g = 0; g < G; g++) s += (double)partial[(size_t)g * ROW + col];
+  return (float)s;
+}
+
+// ---- gradient norms: actor + log_std on one side, critic on the other; same fold and tree as the advantage statistics
+BRS_HD bool is_critic(int i) { return i >= OFF_VF && i < OFF_LOGSTD; }
+BRS_HD void fold_squares(const float* grad, int t, double& pi, double& vf) {
+  pi = 0.0; vf = 0.0;
+  for (int i = t; i < NPARAM; i += APPLY_THREADS) {
+    const double g = (double)grad[i];
+    if (is_critic(i)) vf += g * g; else pi += g * g;
+  }
+}
+// what the norms become under the config's clip mode, and torch.nn.utils.clip_grad_norm_'s scale
+BRS_HD void norms(double sq_pi, double sq_vf, const brs_ppo_config& c, float& norm_pi, float& norm_vf) {
+  if (c.joint_norm) { norm_pi = norm_vf = (float)sqrt(sq_pi + sq_vf); }
+  else { norm_pi = (float)sqrt(sq_pi); norm_vf = (float)sqrt(sq_vf); }
+}
+BRS_HD float clip_scale(float norm, float max_norm) { return fminf(1.0f, max_norm / (norm + 1e-6f)); }
+BRS_HD float param_scale(int i, float norm_pi, float norm_vf, const brs_ppo_config& c) {
+  return (is_critic(i) && !c.joint_norm) ? clip_scale(norm_vf, c.max_grad_norm_vf) : clip_scale(norm_pi, c.max_grad_norm_pi);
+}
+
+// ---- early stop: SB3's target_kl
+BRS_HD bool kl_stops(float kl, const brs_ppo_config& c) { return c.target_kl > 0.0f && kl > 1.5f * c.target_kl; }
+
+// ---- torch.optim.Adam (no amsgrad, no weight decay), step counted from 1; the bias corrections are formed in fp64 as torch forms
+// them in Python floats
+struct AdamScalars {
+  float step_size, bc2_sqrt, w1, beta2, w2, eps;
+};
+BRS_HD AdamScalars adam_scalars(const brs_ppo_config& c, int64_t step) {
+  const double bc1 = 1.0 - pow(c.beta1, (double)step), bc2 = 1.0 - pow(c.beta2, (double)step);
+  return AdamScalars{(float)(c.lr / bc1), (float)sqrt(bc2), (float)(1.0 - c.beta1), (float)c.beta2, (float)(1.0 - c.beta2), (float)c.eps};
+}
+BRS_HD void adam_update(float& p, float& m, float& v, float g, const AdamScalars& a) {
+  m = m + (g - m) * a.w1;                           // exp_avg.lerp_(grad, 1 - beta1)
+  v = v * a.beta2 + a.w2 * g * g;                   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+  p = p - a.step_size * (m / denom);                // param.addcdiv_(exp_avg, denom, value=-step_size)
+}
+
+// the tree both reductions use: partial t takes partial t + s for s = n / 2, n / 4, ... 1 (n a power of two)
+template <class F> BRS_HD void tree_pairs(int n, F&& take) {
+  for (int s = n / 2; s >= 1; s >>= 1)
+    for (int t = 0; t < s; t++) take(t, t + s);
+}
+
+}  // namespace learner
+}  // namespace brs

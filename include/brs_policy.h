@@ -13,6 +13,8 @@
  *                         by step and closed when the env reports terminated or truncated
  *   brs_monitor_reset     evaluate_policy (under EvalCallback, src/sb_rl.py:536-543): with targets, the first target[i]
  *   (with targets)        episodes of env i count and the others are ignored, target[i] = (n_eval_episodes + i) / n
+ *   brs_learner_grad      PPO.train(), the body of its minibatch loop: evaluate_actions, the clipped surrogate, the value loss and
+ *   brs_learner_apply     the entropy bonus, loss.backward(), clip_grad_norm_, Adam's step, and the target_kl early stop
  *
  * These entry points do the same arithmetic on the GPU, reading the simulator's outputs in place (device pointers),
  * so that a rollout of 65,536 envs needs no per-env Python and no PCIe traffic.  All buffers are DEVICE pointers owned
@@ -112,6 +114,57 @@ int brs_monitor_histogram(brs_monitor*, int64_t* hist_host, void* stream);
  * a row that is not filled yet has length 0 */
 int brs_monitor_episodes(brs_monitor*, int32_t* env_host, double* ret_host, int32_t* len_host,
                          uint8_t* time_limit_host, void* stream);
+
+/* ---- PPO learner: the minibatch body of SB3's PPO.train() / tools/train_ppo_torch.py::train on the device.
+ * brs_learner_grad computes the gradient of the mean loss of one minibatch, brs_learner_apply clips it by norm and takes one
+ * torch.optim.Adam step; they are two calls so that a data-parallel caller can all-reduce (and divide) the gradient buffer in
+ * between.  Every call only enqueues on `stream`, nothing is allocated after create, all arrays are device pointers owned by
+ * the caller.  No floating-point atomic and no communication between workgroups inside a kernel: two runs on the same inputs
+ * return identical bytes.  A null handle or a null config is BRS_ERR_ARG (brs_learner_destroy: BRS_ERR_STATE, as everywhere). */
+#define BRS_LEARNER_NSTAT 5 /* minibatch means after the gradient: policy loss, value loss, entropy, approx KL, clip fraction */
+
+typedef struct brs_learner brs_learner;
+
+typedef struct brs_ppo_config {
+  double lr, beta1, beta2, eps; /* torch.optim.Adam (no amsgrad, no weight decay); fp64 as torch holds them in Python floats */
+  float clip_range;
+  float vf_coef;
+  float ent_coef;
+  float max_grad_norm_pi;      /* clip_grad_norm_ of actor + log_std; of everything when joint_norm != 0 */
+  float max_grad_norm_vf;      /* ... of the critic (unused when joint_norm != 0) */
+  float target_kl;             /* <= 0: no early stop */
+  float ret_scale;             /* the value target is ret / ret_scale */
+  int32_t normalize_adv;       /* (adv - mean) / (unbiased std + 1e-8) over the minibatch */
+  int32_t actor_on;            /* 0: loss = vf_coef * value loss only (critic warm-up); actor and log_std gradients are zero */
+  int32_t joint_norm;          /* 1: one global norm (SB3); 0: actor + log_std and critic clipped separately */
+} brs_ppo_config;
+
+typedef struct brs_learner_info {
+  int64_t steps;       /* Adam steps taken */
+  int32_t stopped;     /* sticky: an apply saw approx KL > 1.5 target_kl; cleared by brs_learner_begin_iteration */
+  int32_t bad_index;   /* entries of the last idx outside [0, n_rows): they were left out, the gradient is not to be used */
+  float stat[BRS_LEARNER_NSTAT]; /* of the gradient buffer the last apply saw */
+  float grad_norm_pi;  /* before clipping; the global norm in both when joint_norm != 0 */
+  float grad_norm_vf;
+} brs_learner_info;
+
+/* max_workgroups <= 0: one per compute unit; > 0 caps the grid of the gradient kernel (each workgroup loops over 256-sample chunks) */
+int brs_learner_create(int32_t device, int32_t max_workgroups, brs_learner** out);
+int brs_learner_destroy(brs_learner*);
+const char* brs_learner_last_error(const brs_learner*);
+/* clears the stopped flag (start of a PPO iteration) */
+int brs_learner_begin_iteration(brs_learner*, void* stream);
+/* params_dev[BRS_POLICY_NPARAM] in the order above; obs[n_rows][6], act[n_rows][2], logp_old, adv, ret [n_rows]: the flat
+ * rollout; idx[m] int32 rows of the minibatch (repeats allowed), m >= 2.  Writes grad_dev[BRS_POLICY_NPARAM + BRS_LEARNER_NSTAT]:
+ * the gradient of the mean loss, then the BRS_LEARNER_NSTAT means. */
+int brs_learner_grad(brs_learner*, const float* params_dev, int32_t n_rows, const float* obs_dev, const float* act_dev,
+                     const float* logp_old_dev, const float* adv_dev, const float* ret_dev, const int32_t* idx_dev, int32_t m,
+                     const brs_ppo_config* cfg, float* grad_dev, void* stream);
+/* scale = min(1, max_norm / (norm + 1e-6)), then one Adam step on params / m / v [BRS_POLICY_NPARAM] in place, unless stopped */
+int brs_learner_apply(brs_learner*, float* params_dev, const float* grad_dev, float* m_dev, float* v_dev,
+                      const brs_ppo_config* cfg, void* stream);
+/* one small device-to-host copy; waits for the stream */
+int brs_learner_stats(brs_learner*, brs_learner_info* out_host, void* stream);
 
 #ifdef __cplusplus
 }

@@ -87,10 +87,22 @@ class MixedSim:
 
 def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, log, tag, ent=0.0, reward_clip=None,
           critic_warmup=0, lr_end=None, norm_returns=False, target_kl=None, device_rollout=False, seed=0, env_index_base=0,
-          after_iter=None):
+          after_iter=None, device_learner=False):
+    """device_learner: take the optimiser steps with the HIP learner (balance_robot_mujoco_rl_amd.learner) instead of torch autograd +
+    `opt`; True builds a DevicePPOLearner from `model` (Adam's moments start at zero), an instance is used as it is (main() keeps
+    one over both phases).  `model` receives the learner's weights after every iteration; `opt` only supplies the learning rate."""
     n = sim.n
     dev = sim.device
     pol = None
+    lrn = None
+    if device_learner:
+        if not device_rollout:
+            raise ValueError("device_learner needs device_rollout: it reads the rollout tensors of the HIP path")
+        from balance_robot_mujoco_rl_amd.learner import DevicePPOLearner
+        lrn = device_learner if isinstance(device_learner, DevicePPOLearner) else \
+            DevicePPOLearner(device=dev.index, vf_coef=0.5, max_grad_norm=0.5, separate_clip=True)
+        lrn.load(model.state_dict())
+        lrn.clip_range, lrn.ent_coef = clip, ent
     if device_rollout:   # rollout side on the HIP kernels of include/brs_policy.h (forward + sample, bootstrap, GAE)
         from balance_robot_mujoco_rl_amd.policy import DevicePolicy, gae as gae_kernel
         pol = DevicePolicy(device=dev.index, seed=seed, env_index_base=env_index_base)
@@ -110,7 +122,8 @@ def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, 
                 g_["lr"] = lr0 + (lr_end - lr0) * it / max(1, iters - 1)
         with torch.no_grad():
             if pol is not None:
-                fp = flat_params(model); pol.use_device_weights(fp)   # the learner's current weights, read in place
+                fp = flat_params(model) if lrn is None else lrn.rollout_params()
+                pol.use_device_weights(fp)   # the learner's current weights, read in place
             for t in range(n_steps):
                 if pol is not None:
                     B["obs"][t] = obs; S[t] = start
@@ -160,12 +173,33 @@ def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, 
                     # they are by folding the change of unit into its last layer
                     k = float(model.ret_scale / new_scale)
                     model.v[4].weight.mul_(k); model.v[4].bias.mul_(k)
+                    if lrn is not None:
+                        lrn.load(model.state_dict())
                 model.ret_scale.lerp_(new_scale, 0.05 if it else 1.0)
+                if lrn is not None:
+                    lrn.ret_scale = float(model.ret_scale)
         flat = {k: v.reshape((-1,) + v.shape[2:]) for k, v in B.items()}
         fadv = adv.reshape(-1); fret = ret.reshape(-1)
         N = fadv.numel()
         n_upd = 0; kl = 0.0; stop = False
-        for _ in range(epochs):
+        if lrn is not None:   # the minibatch body below as HIP kernels; the KL early stop is a flag on the device, read once
+            lrn.lr = opt.param_groups[0]["lr"]
+            lrn.actor_on = it >= critic_warmup
+            lrn.target_kl = target_kl if it >= critic_warmup else None
+            lrn.begin_iteration()
+            before = lrn.stats().steps if it == 0 else after
+            for _ in range(epochs):
+                perm = torch.randperm(N, device=dev).to(torch.int32)
+                for s in range(0, N, minibatch):
+                    g = lrn.grad(flat["obs"], flat["act"], flat["logp"], fadv, fret, perm[s:s + minibatch])
+                    _allreduce_mean_(g)   # the gradient and the stats behind it, the KL among them
+                    lrn.apply()
+            st = lrn.stats()
+            after, n_upd, kl = st.steps, st.steps - before, st.approx_kl
+            if st.bad_index:
+                raise RuntimeError(f"the device learner saw {st.bad_index} minibatch indices outside the rollout")
+            model.load_state_dict(lrn.state_dict())
+        for _ in range(epochs if lrn is None else 0):   # the torch learner, as before
             if stop:
                 break
             perm = torch.randperm(N, device=dev)
@@ -283,12 +317,18 @@ def main():
     ap.add_argument("--save-best", default="", help="... and write the weights here whenever the mean return improves")
     ap.add_argument("--device-rollout", action="store_true",
                     help="act, bootstrap and GAE with the HIP kernels of include/brs_policy.h instead of torch ops")
+    ap.add_argument("--device-learner", action="store_true",
+                    help="take the optimiser steps with the HIP learner (brs_learner_*) instead of torch; needs --device-rollout")
     ap.add_argument("--obs-init-scale", default="", help="comma-separated factors on the INITIAL first-layer weights per observation "
                     "channel (both towers), e.g. 1,0.1,1,1,1,1: Env01-v2's obs[1] is a finite difference of two noisy pitch samples "
                     "(+-10 rad/s of noise, envs/env01_v2.py:16-20 with RobotBaseEnv.py:142-157) and saturates freshly initialised tanh units")
     ap.add_argument("--save", default="", help="write the policy/value weights (torch state_dict) here")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.device_learner and not a.device_rollout:
+        ap.error("--device-learner requires --device-rollout")
+    if a.device_learner and a.fix_log_std2:
+        ap.error("--fix-log-std2 is not available with --device-learner (the learner updates every parameter)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0")); local = int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("BRS_PPO_ONE_DEVICE") == "1":   # rehearsal of N ranks on a one-GPU box (with BRS_PPO_BACKEND=gloo)
@@ -310,6 +350,10 @@ def main():
     base = rank * a.envs
     opt = torch.optim.Adam(model.parameters(), lr=a.lr)
     log, callbacks = [], []
+    learner = False
+    if a.device_learner:   # one learner for both phases: Adam's moments carry over, as `opt`'s do
+        from balance_robot_mujoco_rl_amd.learner import DevicePPOLearner
+        learner = DevicePPOLearner(device=local, vf_coef=0.5, max_grad_norm=0.5, separate_clip=True)
     for phase, (env_id, iters) in enumerate(((a.env, a.iters), (a.then, a.iters2))):
         if not env_id:
             continue
@@ -321,7 +365,7 @@ def main():
                     g["lr"] = a.lr2
             if a.log_std2 is not None:
                 with torch.no_grad():
-                    model.log_std.fill_(a.log_std2)
+                    model.log_std.fill_(a.log_std2)   # (train() loads the model into the learner at the start of a phase)
             if a.fix_log_std2:
                 model.log_std.requires_grad_(False)
         if phase == 1 and a.mix2 > 0:
@@ -338,7 +382,7 @@ def main():
         train(sim, model, opt, iters, a.n_steps, a.epochs, a.minibatch, a.gamma, a.lam, 0.2, log, env_id, a.ent, a.reward_clip,
               warm, a.lr2_end if phase == 1 else None, a.norm_returns or (phase == 1 and a.norm_returns2),
               a.target_kl2 if (phase == 1 and a.target_kl2 is not None) else a.target_kl, a.device_rollout, 1000 * (a.seed + 1) + phase, base,
-              after_iter=cb)
+              after_iter=cb, device_learner=learner)
         sim.close()
     evals = []
     if world > 1:
