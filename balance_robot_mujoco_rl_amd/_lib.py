@@ -22,16 +22,19 @@ SIM_FLAGS = ["-Xarch_device", "-ffast-math", "-Xarch_device", "-fgpu-flush-denor
              "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 # the translation units of libbrs_hip.so: (source, its own flags, in the build id).  Policy / GAE kernels, renderer and int8 actor
 # keep IEEE math (checked against fp32 torch at rtol 1e-5 / bit for bit against their host builds under tests/), and so does the
-# episode monitor and the PPO learner (fp64 torch autograd at 1e-5 per parameter block); the build id names the step and policy
-# kernels that committed profiles were measured on, so the other four units stay out of it.
+# episode monitor, the PPO learner (fp64 torch autograd at 1e-5 per parameter block) and the DDPG data path (fp64 numpy at 1e-5);
+# the build id names the step and policy kernels that committed profiles were measured on, so the other five units stay out of it.
 UNITS = [("brs_kernels.hip", SIM_FLAGS, True), ("brs_policy.hip", [], True), ("brs_render.hip", [], False), ("brs_qpolicy.hip", [], False),
-         ("brs_monitor.hip", [], False), ("brs_learner.hip", [], False)]
+         ("brs_monitor.hip", [], False), ("brs_learner.hip", [], False), ("brs_offpolicy.hip", [], False)]
 SRC = os.path.join(_CSRC, UNITS[0][0])  # the unit that takes the A/B flags and the build id stamp
 # what the build id hashes next to the sources of its units; brs_host.hpp holds no kernel code and stays out of it
 HEADERS = [os.path.join(_CSRC, h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp")] + \
           [os.path.join(_INCLUDE, h) for h in ("brs.h", "brs_policy.h")]
 
 POLICY_NPARAM = (64 * 6 + 64 + 64 * 64 + 64 + 2 * 64 + 2) + (64 * 6 + 64 + 64 * 64 + 64 + 64 + 1) + 2
+DDPG_NACTOR = 300 * 6 + 300 + 200 * 300 + 200 + 2 * 200 + 2     # BRS_DDPG_NACTOR
+DDPG_NCRITIC = 200 * 8 + 200 + 150 * 200 + 150 + 1 * 150 + 1    # BRS_DDPG_NCRITIC
+DDPG_TAG_ACT, DDPG_TAG_SAMPLE = 0x44445047, 0x5245504c
 
 
 class BrsConfig(C.Structure):
@@ -63,6 +66,10 @@ class BrsPpoConfig(C.Structure):
 class BrsLearnerInfo(C.Structure):
     _fields_ = [("steps", C.c_int64), ("stopped", C.c_int32), ("bad_index", C.c_int32), ("stat", C.c_float * LEARNER_NSTAT),
                 ("grad_norm_pi", C.c_float), ("grad_norm_vf", C.c_float)]
+
+
+class BrsReplayStorage(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("obs", "next_obs", "action", "reward", "done")]
 
 
 class BrsQLayer(C.Structure):
@@ -166,6 +173,16 @@ SIGNATURES = {
         "brs_learner_grad": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(BrsPpoConfig), _vp, _vp]),
         "brs_learner_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(BrsPpoConfig), _vp]),
         "brs_learner_stats": (C.c_int, [_vp, C.POINTER(BrsLearnerInfo), _vp]),
+        "brs_ddpg_create": (C.c_int, [_i32, C.POINTER(_vp)]),
+        "brs_ddpg_destroy": (C.c_int, [_vp]),
+        "brs_ddpg_last_error": (C.c_char_p, [_vp]),
+        "brs_ddpg_act": (C.c_int, [_vp, _vp, _i32, _vp, C.c_uint64, C.c_int64, C.c_uint32, _f32, _i32, _vp, _vp, _vp, _vp]),
+        "brs_ddpg_q": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+        "brs_ddpg_td_target": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
+        "brs_replay_add": (C.c_int, [_i32, C.POINTER(BrsReplayStorage), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "brs_replay_sample": (C.c_int, [_i32, C.POINTER(BrsReplayStorage), _i32, _i32, _i32, _i32, C.c_uint64, C.c_uint32,
+                                        C.POINTER(BrsReplayStorage), _vp, _vp]),
+        "brs_replay_last_error": (C.c_char_p, []),
     },
     "brs_render.h": {
         "brs_render_default_camera": (None, [C.POINTER(BrsCamera)]),

@@ -1,0 +1,438 @@
+// brs_offpolicy.hip -- the DDPG data path of include/brs_policy.h: actor with exploration noise, critic, TD
+// target from the two target networks, replay buffer add and fused sample, as HIP kernels for gfx950.
+//
+// One forward routine (forward_tile) serves brs_ddpg_act, brs_ddpg_q and brs_ddpg_td_target.  It is brs_policy.hip's scheme for
+// wider layers: fp32 on the MATRIX cores (v_mfma_f32_32x32x2_f32: exact fp32 products, a k-ordered fma chain), the product
+// computed TRANSPOSED, D[unit][row] = sum_k W[unit][k] h[k][row], so that the accumulator of one layer (lane l holds 16 units of
+// ITS row l % 32 per M-tile) is, after the ReLU, the B operand of the next: hidden activations never leave their registers, no
+// LDS round trip and nothing in HBM.  A wave owns 32 rows; the widths are padded to the 32-unit tile (300 -> 320, 200 -> 224,
+// 150 -> 160): 10 + 7 accumulator tiles = 272 registers for the actor, which is why a wave has one N-tile and a workgroup of
+// four waves (one per SIMD) 128 rows.  The first layer (K = 6 / 8), the biases and the output layer live in LDS for the whole
+// kernel; the second layer (200 x 300 = 240 KB) does not fit and is staged in K-chunks of 32 input units -- one chunk is
+// what one M-tile of the first layer feeds -- [H2 padded][33] words each (row stride 33: the 32 lanes of a half hit 32 banks),
+// double-buffered: the next chunk is fetched into registers before the matrix instructions of this one and written to the other
+// buffer after them, one barrier per chunk.  PADDING: padded units get zero weight rows, zero weight columns and zero bias in
+// the LDS image (written, not assumed), so a padded hidden unit is ReLU(0) = 0 and meets a zero column; rows past n are
+// computed on zero inputs (the matrix instructions need whole waves) and not stored.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/brs.h"
+#include "../../include/brs_policy.h"
+#include "brs_host.hpp"
+#include "brs_offpolicy.hpp"
+
+namespace {
+
+using namespace brs::offpolicy;
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int THREADS = 256, WAVE_ROWS = 32, WG_ROWS = WAVE_ROWS * (THREADS / 64);
+constexpr int pad32(int x) { return (x + 31) / 32 * 32; }
+
+template <class N> struct Tile {
+  static constexpr int H1P = pad32(N::H1), H2P = pad32(N::H2), MT1 = H1P / 32, MT2 = H2P / 32;
+  static constexpr int W1_LD = N::IN + 1, CH_LD = 33;  // odd strides: no bank conflict between the 32 units of an M-tile
+  static constexpr int KSTEPS1 = N::IN / 2;
+  // LDS image (floats): W1 [H1P][W1_LD], b1 [H1P], b2 [H2P], W3 [OUT][H2P], b3 [4], two chunks of W2 [H2P][CH_LD]
+  static constexpr int L_W1 = 0, L_B1 = L_W1 + H1P * W1_LD, L_B2 = L_B1 + H1P, L_W3 = L_B2 + H2P, L_B3 = L_W3 + N::OUT * H2P, L_CH = L_B3 + 4,
+                       CH_SIZE = H2P * CH_LD, L_SIZE = L_CH + 2 * CH_SIZE;
+  static constexpr int CH_PER_THREAD = H2P * 32 / THREADS;  // words of a chunk each thread moves
+  static_assert(N::IN % 2 == 0 && (H2P * 32) % THREADS == 0, "tiling");
+};
+constexpr int LDS_FLOATS = Tile<Actor>::L_SIZE > Tile<Critic>::L_SIZE ? Tile<Actor>::L_SIZE : Tile<Critic>::L_SIZE;
+
+// what stays in LDS for the whole forward; padded units and columns are written as zeros
+template <class N> __device__ __forceinline__ void stage_resident(const float* __restrict__ w, float* __restrict__ L) {
+  using T = Tile<N>;
+  using O = Offsets<N>;
+  for (int i = threadIdx.x; i < T::H1P * T::W1_LD; i += THREADS) {
+    const int u = i / T::W1_LD, k = i % T::W1_LD;
+    L[T::L_W1 + i] = (u < N::H1 && k < N::IN) ? w[O::W1 + u * N::IN + k] : 0.0f;
+  }
+  for (int i = threadIdx.x; i < T::H1P; i += THREADS) L[T::L_B1 + i] = i < N::H1 ? w[O::B1 + i] : 0.0f;
+  for (int i = threadIdx.x; i < T::H2P; i += THREADS) L[T::L_B2 + i] = i < N::H2 ? w[O::B2 + i] : 0.0f;
+  for (int i = threadIdx.x; i < N::OUT * T::H2P; i += THREADS) {
+    const int u = i / T::H2P, k = i % T::H2P;
+    L[T::L_W3 + i] = k < N::H2 ? w[O::W3 + u * N::H2 + k] : 0.0f;
+  }
+  if (threadIdx.x < 4) L[T::L_B3 + threadIdx.x] = threadIdx.x < N::OUT ? w[O::B3 + threadIdx.x] : 0.0f;
+}
+
+// chunk ch of the second layer: W2[all units][32 ch .. 32 ch + 31]; word e of the chunk is unit e / 32, input 32 ch + e % 32
+// (a wave reads two 128-byte runs per instruction)
+template <class N> __device__ __forceinline__ void load_chunk(const float* __restrict__ w, const int ch, float (&reg)[Tile<N>::CH_PER_THREAD]) {
+#pragma unroll
+  for (int j = 0; j < Tile<N>::CH_PER_THREAD; j++) {
+    const int e = threadIdx.x + THREADS * j, u = e >> 5, k = 32 * ch + (e & 31);
+    reg[j] = (u < N::H2 && k < N::H1) ? w[Offsets<N>::W2 + u * N::H1 + k] : 0.0f;
+  }
+}
+template <class N> __device__ __forceinline__ void store_chunk(float* __restrict__ buf, const float (&reg)[Tile<N>::CH_PER_THREAD]) {
+#pragma unroll
+  for (int j = 0; j < Tile<N>::CH_PER_THREAD; j++) {
+    const int e = threadIdx.x + THREADS * j;
+    buf[(e >> 5) * Tile<N>::CH_LD + (e & 31)] = reg[j];
+  }
+}
+
+// The network N for the 32 rows of this wave.  xb[s]: input 2 s + (lane / 32) of row (lane % 32) of the wave's tile, the B operand
+// of step s of the first layer (each half of the wave holds the inputs it supplies); out[k]: output unit k of that row, complete
+// in both halves.  Called by all threads of the workgroup.
+template <class N> __device__ __forceinline__ void forward_tile(const float* __restrict__ w, float* __restrict__ L,
+                                                                const float (&xb)[Tile<N>::KSTEPS1], float (&out)[N::OUT]) {
+  using T = Tile<N>;
+  const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+  // unit (inside its M-tile) held by accumulator register r in this half of the wave
+#define BRS_UNIT(r) (8 * ((r) >> 2) + 4 * h + ((r) & 3))
+  __syncthreads();  // the previous forward of this workgroup (brs_ddpg_td_target) has finished with L
+  stage_resident<N>(w, L);
+  float reg[T::CH_PER_THREAD];
+  load_chunk<N>(w, 0, reg);
+  store_chunk<N>(L + T::L_CH, reg);
+  __syncthreads();
+  // layer 1: K = IN in steps of two; this half supplies input 2 s + h
+  f32x16 h1[T::MT1];
+#pragma unroll
+  for (int mt = 0; mt < T::MT1; mt++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) h1[mt][r] = L[T::L_B1 + 32 * mt + BRS_UNIT(r)];
+#pragma unroll
+  for (int s = 0; s < T::KSTEPS1; s++) {
+    const float b = xb[s];
+#pragma unroll
+    for (int mt = 0; mt < T::MT1; mt++) {
+      const float a = L[T::L_W1 + (32 * mt + c) * T::W1_LD + 2 * s + h];
+      h1[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, h1[mt], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int mt = 0; mt < T::MT1; mt++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) h1[mt][r] = fmaxf(h1[mt][r], 0.0f);
+  // layer 2: K = H1P walked in ACCUMULATOR order: step (ch, r) contracts the two units 32 ch + BRS_UNIT(r) of the two halves
+  f32x16 acc[T::MT2];
+#pragma unroll
+  for (int mt = 0; mt < T::MT2; mt++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[mt][r] = L[T::L_B2 + 32 * mt + BRS_UNIT(r)];
+#pragma unroll
+  for (int ch = 0; ch < T::MT1; ch++) {
+    if (ch + 1 < T::MT1) load_chunk<N>(w, ch + 1, reg);
+    const float* __restrict__ B = L + T::L_CH + (ch & 1) * T::CH_SIZE;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      const float b = h1[ch][r];
+#pragma unroll
+      for (int mt = 0; mt < T::MT2; mt++) {
+        const float a = B[(32 * mt + c) * T::CH_LD + BRS_UNIT(r)];
+        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[mt], 0, 0, 0);
+      }
+    }
+    if (ch + 1 < T::MT1) store_chunk<N>(L + T::L_CH + ((ch + 1) & 1) * T::CH_SIZE, reg);
+    __syncthreads();
+  }
+  // output layer on the vector ALU: this half's units of the row, then the other half's partial sum
+  float p[N::OUT];
+#pragma unroll
+  for (int k = 0; k < N::OUT; k++) p[k] = 0.0f;
+#pragma unroll
+  for (int mt = 0; mt < T::MT2; mt++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      const float t = fmaxf(acc[mt][r], 0.0f);
+#pragma unroll
+      for (int k = 0; k < N::OUT; k++) p[k] = fmaf(L[T::L_W3 + k * T::H2P + 32 * mt + BRS_UNIT(r)], t, p[k]);
+    }
+#undef BRS_UNIT
+#pragma unroll
+  for (int k = 0; k < N::OUT; k++) {
+    const float s = p[k] + __shfl_xor(p[k], 32, 64) + L[T::L_B3 + k];
+    out[k] = N::TANH ? tanh_(s) : s;
+  }
+}
+
+// row of the batch this lane feeds into the matrix cores and, in the lower half of the wave, finishes
+__device__ __forceinline__ int tile_row() { return blockIdx.x * WG_ROWS + (threadIdx.x >> 6) * WAVE_ROWS + (threadIdx.x & 31); }
+__device__ __forceinline__ int wave_half() { return (threadIdx.x >> 5) & 1; }
+__device__ __forceinline__ bool finishes_row() { return wave_half() == 0; }
+// the observation words row i feeds into the first layer from this half of the wave; rows past n read as zero
+__device__ __forceinline__ void load_obs_operands(const float* __restrict__ obs, const int n, const int i, float* xb) {
+#pragma unroll
+  for (int s = 0; s < OBS / 2; s++) xb[s] = i < n ? obs[(size_t)OBS * i + 2 * s + wave_half()] : 0.0f;
+}
+
+__global__ void __launch_bounds__(THREADS) ddpg_act_kernel(const float* __restrict__ actor, const int n, const float* __restrict__ obs,
+                                                           const uint64_t seed, const int64_t gid_base, const uint32_t step, const float sigma,
+                                                           float* __restrict__ action, float* __restrict__ mean, float* __restrict__ noise) {
+  __shared__ float L[Tile<Actor>::L_SIZE];
+  const int i = tile_row();
+  float xb[OBS / 2], mu[ACT];
+  load_obs_operands(obs, n, i, xb);
+  forward_tile<Actor>(actor, L, xb, mu);  // (no lane leaves before the matrix instructions: they need the whole wave)
+  if (i >= n || !finishes_row()) return;
+  float a[ACT], m[ACT], z[ACT];
+  act_tail(seed, gid_base + (int64_t)i, step, sigma, 0, mu, a, m, z);
+#pragma unroll
+  for (int k = 0; k < ACT; k++) {
+    action[(size_t)ACT * i + k] = a[k];
+    if (mean) mean[(size_t)ACT * i + k] = m[k];
+    if (noise) noise[(size_t)ACT * i + k] = z[k];
+  }
+}
+
+// the learning_starts phase: no network
+__global__ void __launch_bounds__(256) ddpg_random_kernel(const int n, const uint64_t seed, const int64_t gid_base, const uint32_t step,
+                                                          const float sigma, float* __restrict__ action, float* __restrict__ mean,
+                                                          float* __restrict__ noise) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float none[ACT] = {0.0f, 0.0f};
+  float a[ACT], m[ACT], z[ACT];
+  act_tail(seed, gid_base + (int64_t)i, step, sigma, 1, none, a, m, z);
+#pragma unroll
+  for (int k = 0; k < ACT; k++) {
+    action[(size_t)ACT * i + k] = a[k];
+    if (mean) mean[(size_t)ACT * i + k] = m[k];
+    if (noise) noise[(size_t)ACT * i + k] = z[k];
+  }
+}
+
+__global__ void __launch_bounds__(THREADS) ddpg_q_kernel(const float* __restrict__ critic, const int n, const float* __restrict__ obs,
+                                                         const float* __restrict__ act, float* __restrict__ q) {
+  __shared__ float L[Tile<Critic>::L_SIZE];
+  const int i = tile_row();
+  float xb[(OBS + ACT) / 2], v[1];
+  load_obs_operands(obs, n, i, xb);
+  xb[OBS / 2] = i < n ? act[(size_t)ACT * i + wave_half()] : 0.0f;
+  forward_tile<Critic>(critic, L, xb, v);
+  if (i < n && finishes_row()) q[i] = v[0];
+}
+
+// actor' -> concat -> critic' -> combine in one launch; the two forwards share the LDS image one after the other
+__global__ void __launch_bounds__(THREADS) ddpg_td_target_kernel(const float* __restrict__ actor_t, const float* __restrict__ critic_t, const int m,
+                                                                 const float* __restrict__ next_obs, const float* __restrict__ reward,
+                                                                 const uint8_t* __restrict__ done, const float gamma, float* __restrict__ y) {
+  __shared__ float L[LDS_FLOATS];
+  const int i = tile_row();
+  float sb[OBS / 2], a[ACT], v[1];
+  load_obs_operands(next_obs, m, i, sb);
+  forward_tile<Actor>(actor_t, L, sb, a);
+  const float a_mine = wave_half() ? a[1] : a[0];
+  const float xb[(OBS + ACT) / 2] = {sb[0], sb[1], sb[2], a_mine};
+  forward_tile<Critic>(critic_t, L, xb, v);
+  if (i < m && finishes_row()) y[i] = td_combine(reward[i], done[i], gamma, v[0]);
+}
+
+// ------------------------------------------------------------------------------------------------ replay buffer
+template <int V> struct Vec;
+template <> struct Vec<1> { typedef float F; typedef uint8_t B; };
+template <> struct Vec<4> { typedef float4 F; typedef uchar4 B; };
+
+// One env step into row `pos` (cell0 = pos * n): thread t moves words V t .. V t + V - 1 of the row of every array that is
+// that long.  V = 4 needs n % 4 == 0 and 16-byte aligned pointers (the host side decides); V = 1 takes everything else.
+template <int V> __global__ void __launch_bounds__(256) replay_add_kernel(const brs_replay_storage s, const int n, const int64_t cell0,
+                                                                           const float* __restrict__ last_obs, const float* __restrict__ action,
+                                                                           const float* __restrict__ obs, const float* __restrict__ reward,
+                                                                           const uint8_t* __restrict__ term, const uint8_t* __restrict__ trunc,
+                                                                           const float* __restrict__ tobs) {
+  typedef typename Vec<V>::F F;
+  typedef typename Vec<V>::B B;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * OBS / V) return;
+  reinterpret_cast<F*>(s.obs + cell0 * OBS)[t] = reinterpret_cast<const F*>(last_obs)[t];
+  union { F v; float f[V]; } o, e;
+  o.v = reinterpret_cast<const F*>(obs)[t];
+  const int env_a = V * t / OBS, env_b = (V * t + V - 1) / OBS;  // the V words belong to at most two envs
+  const bool end_a = next_is_terminal_obs(term[env_a], trunc[env_a]), end_b = next_is_terminal_obs(term[env_b], trunc[env_b]);
+  if (end_a || end_b) {
+    e.v = reinterpret_cast<const F*>(tobs)[t];
+#pragma unroll
+    for (int j = 0; j < V; j++) o.f[j] = ((V * t + j) / OBS == env_a ? end_a : end_b) ? e.f[j] : o.f[j];
+  }
+  reinterpret_cast<F*>(s.next_obs + cell0 * OBS)[t] = o.v;
+  if (t < n * ACT / V) reinterpret_cast<F*>(s.action + cell0 * ACT)[t] = reinterpret_cast<const F*>(action)[t];
+  if (t < n / V) {
+    reinterpret_cast<F*>(s.reward + cell0)[t] = reinterpret_cast<const F*>(reward)[t];
+    union { B v; uint8_t b[V]; } d;
+    d.v = reinterpret_cast<const B*>(term)[t];
+#pragma unroll
+    for (int j = 0; j < V; j++) d.b[j] = stored_done(d.b[j]);
+    reinterpret_cast<B*>(s.done + cell0)[t] = d.v;
+  }
+}
+
+// Index and gather in one kernel.  Eight lanes per sample, each moving one 8-byte piece (obs 3, next_obs 3, action 1) and the
+// eighth the reward, the done byte and the indices: the pieces of consecutive samples are contiguous in the outputs, so a wave's
+// stores are runs of 24 / 8 / 4 bytes per sample back to back.  Every lane of a sample computes the same Philox block.
+template <bool V2> __global__ void __launch_bounds__(256) replay_sample_kernel(const brs_replay_storage s, const int n, const int size, const int m,
+                                                                               const uint64_t seed, const uint32_t draw, const brs_replay_storage out,
+                                                                               int32_t* __restrict__ idx) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t j = t >> 3;
+  const int part = (int)(t & 7);
+  if (j >= m) return;
+  uint32_t w[4];
+  sample_block(seed, draw, (uint32_t)j, w);
+  int32_t row, env;
+  sample_cell(w[0], w[1], size, n, &row, &env);
+  const int64_t cell = (int64_t)row * n + env;
+  if (part == 7) {
+    out.reward[j] = s.reward[cell];
+    out.done[j] = s.done[cell];
+    if (idx) { idx[2 * j] = row; idx[2 * j + 1] = env; }
+    return;
+  }
+  const float* src;
+  float* dst;
+  if (part < 3) { src = s.obs + cell * OBS + 2 * part; dst = out.obs + j * OBS + 2 * part; }
+  else if (part < 6) { src = s.next_obs + cell * OBS + 2 * (part - 3); dst = out.next_obs + j * OBS + 2 * (part - 3); }
+  else { src = s.action + cell * ACT; dst = out.action + j * ACT; }
+  if (V2) *reinterpret_cast<float2*>(dst) = *reinterpret_cast<const float2*>(src);
+  else { dst[0] = src[0]; dst[1] = src[1]; }
+}
+
+struct brs_replay { std::string err; };  // the family of the handle-less replay calls: only its error slot exists
+
+bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+}  // namespace
+
+struct brs_ddpg {
+  int device = 0;
+  std::string err;
+};
+
+using brs::host::DeviceGuard, brs::host::fail;
+
+extern "C" {
+
+int brs_ddpg_create(int32_t device, brs_ddpg** out) {
+  if (!out) return fail<brs_ddpg>(nullptr, BRS_ERR_ARG, "brs_ddpg_create: null argument");
+  *out = nullptr;
+  std::string why;
+  if (const int rc = brs::host::check_device(device, "brs_ddpg_create", &why)) return fail<brs_ddpg>(nullptr, rc, why);
+  brs_ddpg* d = new brs_ddpg();
+  d->device = device;
+  *out = d;
+  return BRS_OK;
+}
+
+int brs_ddpg_destroy(brs_ddpg* d) {
+  if (!d) return BRS_ERR_STATE;
+  delete d;
+  return BRS_OK;
+}
+
+const char* brs_ddpg_last_error(const brs_ddpg* d) { return brs::host::last_error(d); }
+
+int brs_ddpg_act(brs_ddpg* d, const float* actor_dev, int32_t n, const float* obs_dev, uint64_t seed, int64_t env_index_base, uint32_t step,
+                 float sigma, int32_t random, float* action_dev, float* mean_dev, float* noise_dev, void* stream) {
+  // what needs no handle is checked first (fail() records it in the family's slot when there is none)
+  if (n < 1) return fail(d, BRS_ERR_ARG, "brs_ddpg_act: n must be at least 1");
+  if (!(sigma >= 0.0f)) return fail(d, BRS_ERR_ARG, "brs_ddpg_act: sigma must be >= 0");
+  if (!action_dev || (!random && (!actor_dev || !obs_dev))) return fail(d, BRS_ERR_ARG, "brs_ddpg_act: null argument");
+  if (!d) return fail(d, BRS_ERR_ARG, "brs_ddpg_act: null handle");
+  DeviceGuard g(d->device);
+  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_ddpg_act: hipSetDevice failed");
+  if (random)
+    hipLaunchKernelGGL(ddpg_random_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, env_index_base, step, sigma,
+                       action_dev, mean_dev, noise_dev);
+  else
+    hipLaunchKernelGGL(ddpg_act_kernel, dim3((n + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_dev, n, obs_dev, seed,
+                       env_index_base, step, sigma, action_dev, mean_dev, noise_dev);
+  BRS_HIP_TRY(d, hipGetLastError());
+  return BRS_OK;
+}
+
+int brs_ddpg_q(brs_ddpg* d, const float* critic_dev, int32_t n, const float* obs_dev, const float* act_dev, float* q_dev, void* stream) {
+  if (n < 1) return fail(d, BRS_ERR_ARG, "brs_ddpg_q: n must be at least 1");
+  if (!critic_dev || !obs_dev || !act_dev || !q_dev) return fail(d, BRS_ERR_ARG, "brs_ddpg_q: null argument");
+  if (!d) return fail(d, BRS_ERR_ARG, "brs_ddpg_q: null handle");
+  DeviceGuard g(d->device);
+  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_ddpg_q: hipSetDevice failed");
+  hipLaunchKernelGGL(ddpg_q_kernel, dim3((n + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, critic_dev, n, obs_dev, act_dev, q_dev);
+  BRS_HIP_TRY(d, hipGetLastError());
+  return BRS_OK;
+}
+
+int brs_ddpg_td_target(brs_ddpg* d, const float* actor_target_dev, const float* critic_target_dev, int32_t m, const float* next_obs_dev,
+                       const float* reward_dev, const uint8_t* done_dev, float gamma, float* y_dev, void* stream) {
+  if (m < 1) return fail(d, BRS_ERR_ARG, "brs_ddpg_td_target: m must be at least 1");
+  if (!actor_target_dev || !critic_target_dev || !next_obs_dev || !reward_dev || !done_dev || !y_dev)
+    return fail(d, BRS_ERR_ARG, "brs_ddpg_td_target: null argument");
+  if (!d) return fail(d, BRS_ERR_ARG, "brs_ddpg_td_target: null handle");
+  DeviceGuard g(d->device);
+  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_ddpg_td_target: hipSetDevice failed");
+  hipLaunchKernelGGL(ddpg_td_target_kernel, dim3((m + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_target_dev,
+                     critic_target_dev, m, next_obs_dev, reward_dev, done_dev, gamma, y_dev);
+  BRS_HIP_TRY(d, hipGetLastError());
+  return BRS_OK;
+}
+
+const char* brs_replay_last_error(void) { return brs::host::last_error<brs_replay>(nullptr); }
+
+static int replay_fail(int code, const std::string& msg) { return fail<brs_replay>(nullptr, code, msg); }
+
+// the checks brs_replay_add and brs_replay_sample share; BRS_OK or the code to return, the text recorded
+static int check_storage(const char* who, const brs_replay_storage* s, int32_t n, int32_t cap) {
+  const std::string w(who);
+  if (!s || !s->obs || !s->next_obs || !s->action || !s->reward || !s->done) return replay_fail(BRS_ERR_ARG, w + ": null storage pointer");
+  if (n < 1 || cap < 1) return replay_fail(BRS_ERR_ARG, w + ": n and cap must be at least 1");
+  if (n > 0x7fffffff / OBS) return replay_fail(BRS_ERR_ARG, w + ": n * 6 exceeds 2^31 - 1");
+  if ((int64_t)cap * (int64_t)n > 0x7fffffffLL) return replay_fail(BRS_ERR_ARG, w + ": cap * n exceeds 2^31 - 1");
+  return BRS_OK;
+}
+
+int brs_replay_add(int32_t device, const brs_replay_storage* storage, int32_t n, int32_t cap, int32_t pos, const float* last_obs_dev,
+                   const float* action_dev, const float* obs_dev, const float* reward_dev, const uint8_t* terminated_dev,
+                   const uint8_t* truncated_dev, const float* terminal_obs_dev, void* stream) {
+  if (const int rc = check_storage("brs_replay_add", storage, n, cap)) return rc;
+  if (pos < 0 || pos >= cap) return replay_fail(BRS_ERR_ARG, "brs_replay_add: pos must be in [0, cap)");
+  if (!last_obs_dev || !action_dev || !obs_dev || !reward_dev || !terminated_dev || !truncated_dev || !terminal_obs_dev)
+    return replay_fail(BRS_ERR_ARG, "brs_replay_add: null argument");
+  std::string why;
+  if (const int rc = brs::host::check_device(device, "brs_replay_add", &why)) return replay_fail(rc, why);
+  DeviceGuard g(device);
+  if (!g.ok) return replay_fail(BRS_ERR_HIP, "brs_replay_add: hipSetDevice failed");
+  const int64_t cell0 = (int64_t)pos * n;
+  bool v4 = n % 4 == 0;
+  for (const void* p : {(const void*)storage->obs, (const void*)storage->next_obs, (const void*)storage->action, (const void*)storage->reward,
+                        (const void*)storage->done, (const void*)last_obs_dev, (const void*)action_dev, (const void*)obs_dev, (const void*)reward_dev,
+                        (const void*)terminated_dev, (const void*)terminal_obs_dev})
+    v4 = v4 && aligned(p, 16);
+  if (v4)
+    hipLaunchKernelGGL(replay_add_kernel<4>, dim3((n * OBS / 4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, *storage, n, cell0, last_obs_dev,
+                       action_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, terminal_obs_dev);
+  else
+    hipLaunchKernelGGL(replay_add_kernel<1>, dim3((int)(((int64_t)n * OBS + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *storage, n, cell0,
+                       last_obs_dev, action_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, terminal_obs_dev);
+  if (hipGetLastError() != hipSuccess) return replay_fail(BRS_ERR_HIP, "brs_replay_add: kernel launch failed");
+  return BRS_OK;
+}
+
+int brs_replay_sample(int32_t device, const brs_replay_storage* storage, int32_t n, int32_t cap, int32_t size, int32_t m, uint64_t seed,
+                      uint32_t draw, const brs_replay_storage* out, int32_t* idx_dev, void* stream) {
+  if (const int rc = check_storage("brs_replay_sample", storage, n, cap)) return rc;
+  if (size < 1 || size > cap) return replay_fail(BRS_ERR_ARG, "brs_replay_sample: size must be in [1, cap]");
+  if (m < 1 || m > (1 << 27)) return replay_fail(BRS_ERR_ARG, "brs_replay_sample: m must be in [1, 2^27]");
+  if (!out || !out->obs || !out->next_obs || !out->action || !out->reward || !out->done)
+    return replay_fail(BRS_ERR_ARG, "brs_replay_sample: null output pointer");
+  std::string why;
+  if (const int rc = brs::host::check_device(device, "brs_replay_sample", &why)) return replay_fail(rc, why);
+  DeviceGuard g(device);
+  if (!g.ok) return replay_fail(BRS_ERR_HIP, "brs_replay_sample: hipSetDevice failed");
+  bool v2 = true;
+  for (const void* p : {(const void*)storage->obs, (const void*)storage->next_obs, (const void*)storage->action, (const void*)out->obs,
+                        (const void*)out->next_obs, (const void*)out->action})
+    v2 = v2 && aligned(p, 8);
+  const dim3 grid((unsigned)(((int64_t)m * 8 + 255) / 256));
+  if (v2) hipLaunchKernelGGL(replay_sample_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, *storage, n, size, m, seed, draw, *out, idx_dev);
+  else hipLaunchKernelGGL(replay_sample_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, *storage, n, size, m, seed, draw, *out, idx_dev);
+  if (hipGetLastError() != hipSuccess) return replay_fail(BRS_ERR_HIP, "brs_replay_sample: kernel launch failed");
+  return BRS_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,261 @@
+"""DDPG's data path on the device (include/brs_policy.h: brs_ddpg_*, brs_replay_*).
+
+The reference's algorithm_factory configures two algorithms by hand, PPO and DDPG (src/sb_rl.py:40-83); DDPG gets
+net_arch = dict(pi=[300, 200], qf=[200, 150]) and NormalActionNoise(sigma=0.1).  Between two gradient steps SB3's DDPG runs the
+deterministic actor, adds the noise, steps the env, stores the transition in a host-side numpy ReplayBuffer (terminal observation
+and time-limit rules per env, in Python), samples a uniform minibatch and evaluates the two target networks.  `DeviceDDPGNets`,
+`DeviceReplayBuffer` and `DeviceOffPolicyCollector` do all of that in HIP kernels of libbrs_hip.so on the simulator's own output
+tensors.  The gradient step is the caller's (tools/train_ddpg_torch.py does it in torch).  PyTorch only owns the buffers and the
+stream."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .policy import _need, _p
+from .sim import BrsError
+
+NACTOR, NCRITIC = _lib.DDPG_NACTOR, _lib.DDPG_NCRITIC
+# (layer, shape) of the two networks in the order of their flat parameter vectors
+ACTOR_SHAPES = [((300, 6), (300,)), ((200, 300), (200,)), ((2, 200), (2,))]
+CRITIC_SHAPES = [((200, 8), (200,)), ((150, 200), (150,)), ((1, 150), (1,))]
+# state_dict prefixes of the three Linear layers: SB3's TD3Policy and tools/train_ddpg_torch.py
+NAMINGS = {"sb3": {"actor": "actor.mu.{}.", "critic": "critic.qf0.{}.", "actor_target": "actor_target.mu.{}.",
+                   "critic_target": "critic_target.qf0.{}."},
+           "tool": {"actor": "actor.{}.", "critic": "critic.{}.", "actor_target": "actor_target.{}.", "critic_target": "critic_target.{}."}}
+_LAYER_INDEX = (0, 2, 4)   # Linear, ReLU, Linear, ReLU, Linear in an nn.Sequential
+
+
+def naming_of(sd):
+    """'sb3' or 'tool', by the keys of a state_dict"""
+    keys = [k.split(".") for k in sd if isinstance(k, str)]
+    if any(len(k) == 4 and k[0] in NAMINGS["sb3"] and k[1] in ("mu", "qf0") for k in keys):
+        return "sb3"
+    if any(len(k) == 3 and k[0] in NAMINGS["tool"] and k[1].isdigit() for k in keys):
+        return "tool"
+    raise ValueError("neither SB3's TD3Policy naming (actor.mu.0.weight) nor the tool's (actor.0.weight)")
+
+
+def _layout(net, naming):
+    shapes = ACTOR_SHAPES if net.startswith("actor") else CRITIC_SHAPES
+    prefix = NAMINGS[naming][net]
+    return [(prefix.format(i) + kind, shape) for i, pair in zip(_LAYER_INDEX, shapes) for kind, shape in zip(("weight", "bias"), pair)]
+
+
+def flatten_ddpg_state_dict(sd, net="actor"):
+    """state_dict in either naming -> the flat float32 vector of `net` ('actor', 'critic', 'actor_target', 'critic_target')"""
+    parts = []
+    for name, shape in _layout(net, naming_of(sd)):
+        if name not in sd:
+            raise ValueError(f"{name}: missing")
+        a = sd[name]
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        if tuple(a.shape) != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
+        parts.append(a.astype(np.float32).ravel())
+    flat = np.concatenate(parts)
+    assert flat.size == (NACTOR if net.startswith("actor") else NCRITIC)
+    return flat
+
+
+def unflatten_ddpg_state_dict(flat, net="actor", naming="sb3"):
+    """the flat vector of `net` -> {name: tensor} in `naming`"""
+    flat = np.ascontiguousarray(flat.detach().cpu().numpy() if hasattr(flat, "detach") else flat, dtype=np.float32)
+    want = NACTOR if net.startswith("actor") else NCRITIC
+    if flat.shape != (want,):
+        raise ValueError(f"{net}: expected {want} parameters, got shape {flat.shape}")
+    out, at = {}, 0
+    for name, shape in _layout(net, naming):
+        k = int(np.prod(shape))
+        out[name] = torch.from_numpy(flat[at:at + k].reshape(shape).copy())
+        at += k
+    return out
+
+
+def _device(device):
+    return torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+
+
+class DeviceDDPGNets:
+    """SB3's TD3Policy networks with the reference's widths, evaluated by the HIP kernels.  The parameter vectors are arguments of
+    every call (flat float32 device tensors, read in place): the caller's optimiser and Polyak update write them."""
+
+    def __init__(self, device=0, seed=0, env_index_base=0):
+        if not torch.cuda.is_available():
+            raise BrsError("no HIP device visible to PyTorch: the on-device DDPG networks have no CPU fallback")
+        self.L = _lib.lib()
+        self.device = _device(device)
+        h = C.c_void_p()
+        rc = self.L.brs_ddpg_create(self.device.index, C.byref(h))
+        if rc != 0:
+            raise BrsError(f"brs_ddpg_create failed ({rc}): {self.L.brs_ddpg_last_error(None).decode()}")
+        self.h = h
+        self.seed, self.env_index_base = int(seed), int(env_index_base)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.brs_ddpg_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise BrsError(f"{what} failed ({rc}): {self.L.brs_ddpg_last_error(self.h).decode()}")
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def act(self, actor_params, obs, step, sigma, random=False, out=None, mean=None, noise=None):
+        """SB3 _sample_action: obs [n,6] -> action [n,2] = clip(mean + sigma z); `random`: the learning_starts phase (uniform mean,
+        actor_params and obs may be None, n is then taken from `out`); mean / noise: optional [n,2] outputs"""
+        d, f32 = self.device, torch.float32
+        n = out.shape[0] if random and obs is None else obs.shape[0]
+        if not random:
+            _need(actor_params, "actor_params", f32, (NACTOR,), d); _need(obs, "obs", f32, (n, 6), d)
+        if out is None:
+            out = torch.empty((n, 2), dtype=f32, device=d)
+        _need(out, "action", f32, (n, 2), d)
+        for t, name in ((mean, "mean"), (noise, "noise")):
+            if t is not None:
+                _need(t, name, f32, (n, 2), d)
+        self._check(self.L.brs_ddpg_act(self.h, None if random else _p(actor_params), n, None if random else _p(obs), self.seed,
+                                        self.env_index_base, int(step) & 0xffffffff, float(sigma), int(bool(random)), _p(out), _p(mean),
+                                        _p(noise), self._stream()), "brs_ddpg_act")
+        return out
+
+    def q(self, critic_params, obs, action, out=None):
+        """Q(s, a): obs [n,6], action [n,2] -> [n]"""
+        d, f32, n = self.device, torch.float32, obs.shape[0]
+        _need(critic_params, "critic_params", f32, (NCRITIC,), d); _need(obs, "obs", f32, (n, 6), d); _need(action, "action", f32, (n, 2), d)
+        if out is None:
+            out = torch.empty(n, dtype=f32, device=d)
+        _need(out, "q", f32, (n,), d)
+        self._check(self.L.brs_ddpg_q(self.h, _p(critic_params), n, _p(obs), _p(action), _p(out), self._stream()), "brs_ddpg_q")
+        return out
+
+    def td_target(self, actor_target_params, critic_target_params, next_obs, reward, done, gamma, out=None):
+        """y = reward + (1 - done) gamma Q'(next_obs, pi'(next_obs)) from the two target networks: [m]"""
+        d, f32, m = self.device, torch.float32, next_obs.shape[0]
+        _need(actor_target_params, "actor_target_params", f32, (NACTOR,), d); _need(critic_target_params, "critic_target_params", f32, (NCRITIC,), d)
+        _need(next_obs, "next_obs", f32, (m, 6), d); _need(reward, "reward", f32, (m,), d); _need(done, "done", torch.uint8, (m,), d)
+        if out is None:
+            out = torch.empty(m, dtype=f32, device=d)
+        _need(out, "y", f32, (m,), d)
+        self._check(self.L.brs_ddpg_td_target(self.h, _p(actor_target_params), _p(critic_target_params), m, _p(next_obs), _p(reward), _p(done),
+                                              float(gamma), _p(out), self._stream()), "brs_ddpg_td_target")
+        return out
+
+
+def _storage(obs, next_obs, action, reward, done):
+    return _lib.BrsReplayStorage(obs.data_ptr(), next_obs.data_ptr(), action.data_ptr(), reward.data_ptr(), done.data_ptr())
+
+
+class DeviceReplayBuffer:
+    """SB3's ReplayBuffer for the n envs of a BatchedSim, resident in HBM, time-major: obs / next_obs [cap][n][6], action
+    [cap][n][2], reward / done [cap][n].  add() and sample() each enqueue one kernel; `pos` and `full` are host integers."""
+
+    def __init__(self, n_envs, capacity_steps, device=0, seed=0):
+        if not torch.cuda.is_available():
+            raise BrsError("no HIP device visible to PyTorch: the on-device replay buffer has no CPU fallback")
+        self.L = _lib.lib()
+        self.device = _device(device)
+        self.n, self.cap = int(n_envs), int(capacity_steps)
+        if self.n < 1 or self.cap < 1 or self.n * self.cap > 2 ** 31 - 1:
+            raise ValueError(f"need n_envs >= 1, capacity_steps >= 1 and their product <= 2^31 - 1, got {n_envs}, {capacity_steps}")
+        d, n, cap = self.device, self.n, self.cap
+        f = lambda *s: torch.zeros(s, dtype=torch.float32, device=d)
+        self.obs, self.next_obs, self.action, self.reward = f(cap, n, 6), f(cap, n, 6), f(cap, n, 2), f(cap, n)
+        self.done = torch.zeros((cap, n), dtype=torch.uint8, device=d)
+        self._store = _storage(self.obs, self.next_obs, self.action, self.reward, self.done)
+        self.pos, self.full, self.seed, self.draw = 0, False, int(seed), 0
+
+    @property
+    def rows(self):
+        """valid rows (env steps): pos until the first wrap, then the capacity"""
+        return self.cap if self.full else self.pos
+
+    @property
+    def size(self):
+        """valid transitions"""
+        return self.rows * self.n
+
+    def __len__(self):
+        return self.size
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise BrsError(f"{what} failed ({rc}): {self.L.brs_replay_last_error().decode()}")
+
+    def add(self, last_obs, action, obs, terminal_obs, reward, terminated, truncated):
+        """one env step of all envs into row `pos`: last_obs is what `action` was computed from, the other five are BatchedSim.step's
+        outputs (consumed in stream order: the views may be overwritten by the next step afterwards)"""
+        n, d, f32, u8 = self.n, self.device, torch.float32, torch.uint8
+        _need(last_obs, "last_obs", f32, (n, 6), d); _need(action, "action", f32, (n, 2), d); _need(obs, "obs", f32, (n, 6), d)
+        _need(terminal_obs, "terminal_obs", f32, (n, 6), d); _need(reward, "reward", f32, (n,), d)
+        _need(terminated, "terminated", u8, (n,), d); _need(truncated, "truncated", u8, (n,), d)
+        self._check(self.L.brs_replay_add(d.index, C.byref(self._store), n, self.cap, self.pos, _p(last_obs), _p(action), _p(obs), _p(reward),
+                                          _p(terminated), _p(truncated), _p(terminal_obs), self._stream()), "brs_replay_add")
+        self.pos = (self.pos + 1) % self.cap
+        self.full = self.full or self.pos == 0
+
+    def new_batch(self, m):
+        d = self.device
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=d)
+        return f(m, 6), f(m, 6), f(m, 2), f(m), torch.empty(m, dtype=torch.uint8, device=d)
+
+    def sample(self, m, out=None, idx=None):
+        """m uniform transitions -> (obs [m,6], next_obs [m,6], action [m,2], reward [m], done [m] uint8); `out`: the same five
+        preallocated; idx: optional int32 [m,2] that receives (row, env).  Every call uses the next value of the draw counter."""
+        m = int(m)
+        if self.rows < 1:
+            raise ValueError("sample() from an empty buffer")
+        if out is None:
+            out = self.new_batch(m)
+        d, f32 = self.device, torch.float32
+        o, no, a, r, dn = out
+        _need(o, "obs", f32, (m, 6), d); _need(no, "next_obs", f32, (m, 6), d); _need(a, "action", f32, (m, 2), d); _need(r, "reward", f32, (m,), d)
+        _need(dn, "done", torch.uint8, (m,), d)
+        if idx is not None:
+            _need(idx, "idx", torch.int32, (m, 2), d)
+        dst = _storage(o, no, a, r, dn)
+        self._check(self.L.brs_replay_sample(d.index, C.byref(self._store), self.n, self.cap, self.rows, m, self.seed, self.draw & 0xffffffff,
+                                             C.byref(dst), _p(idx), self._stream()), "brs_replay_sample")
+        self.draw += 1
+        return out
+
+
+class DeviceOffPolicyCollector:
+    """SB3's OffPolicyAlgorithm.collect_rollouts on the device: collect() alternates brs_ddpg_act -> brs_step -> (monitor) ->
+    brs_replay_add with no synchronisation and no allocation.  `actor_params`: the flat device tensor the learner updates in place.
+    `monitor`: an EpisodeMonitor that is fed every step."""
+
+    def __init__(self, sim, nets, actor_params, replay, sigma=0.1, monitor=None):
+        self.sim, self.nets, self.actor_params, self.replay, self.sigma, self.monitor = sim, nets, actor_params, replay, float(sigma), monitor
+        if replay.n != sim.n:
+            raise ValueError(f"the replay buffer holds {replay.n} envs, the simulator {sim.n}")
+        self._action = torch.zeros((sim.n, 2), dtype=torch.float32, device=sim.device)
+        self._last_obs = None   # a private copy: sim.step returns views that the next step overwrites
+        self.step = 0
+
+    def collect(self, steps, random=False):
+        sim, nets, replay = self.sim, self.nets, self.replay
+        if self._last_obs is None:
+            self._last_obs = sim.reset().clone()
+        for _ in range(int(steps)):
+            nets.act(self.actor_params, self._last_obs, self.step, self.sigma, random=random, out=self._action)
+            self.step += 1
+            obs, rew, term, trunc, tobs = sim.step(self._action)
+            if self.monitor is not None:
+                self.monitor.update(rew, term, trunc)
+            replay.add(self._last_obs, self._action, obs, tobs, rew, term, trunc)
+            self._last_obs.copy_(obs)
+        return self

@@ -16,6 +16,17 @@
  *   brs_learner_grad      PPO.train(), the body of its minibatch loop: evaluate_actions, the clipped surrogate, the value loss and
  *   brs_learner_apply     the entropy bonus, loss.backward(), clip_grad_norm_, Adam's step, and the target_kl early stop
  *
+ * and for the reference's second algorithm, DDPG with net_arch = dict(pi=[300, 200], qf=[200, 150]) and
+ * NormalActionNoise(sigma=0.1) (src/sb_rl.py:72-83), what SB3's OffPolicyAlgorithm / TD3 do between two gradient steps:
+ *
+ *   brs_ddpg_act          OffPolicyAlgorithm._sample_action: the deterministic actor (or a uniform action during learning_starts),
+ *                         plus the action noise, clipped to the Box
+ *   brs_replay_add        ReplayBuffer.add as _store_transition calls it: next_obs is the terminal observation where an episode
+ *                         ended, done is cleared where it ended at the time limit only (handle_timeout_termination)
+ *   brs_replay_sample     ReplayBuffer.sample: uniform rows and envs, gathered into contiguous minibatch arrays
+ *   brs_ddpg_td_target    TD3.train's target with target_policy_noise = 0 and one critic: r + (1 - done) gamma Q'(s', pi'(s'))
+ *   brs_ddpg_q            the critic forward Q(s, a)
+ *
  * These entry points do the same arithmetic on the GPU, reading the simulator's outputs in place (device pointers),
  * so that a rollout of 65,536 envs needs no per-env Python and no PCIe traffic.  All buffers are DEVICE pointers owned
  * by the caller; every call only enqueues work on `stream`.  Same library (libbrs_hip.so), same status codes as brs.h.
@@ -165,6 +176,64 @@ int brs_learner_apply(brs_learner*, float* params_dev, const float* grad_dev, fl
                       const brs_ppo_config* cfg, void* stream);
 /* one small device-to-host copy; waits for the stream */
 int brs_learner_stats(brs_learner*, brs_learner_info* out_host, void* stream);
+
+/* ---- DDPG data path: everything SB3's DDPG does between two gradient steps.  The networks are SB3's TD3Policy
+ * with the reference's net_arch, widths fixed at compile time; each is a flat fp32 device vector, torch.nn.Linear layout:
+ *   actor : W1[300][6] b1[300] W2[200][300] b2[200] W3[2][200] b3[2], ReLU ReLU tanh   (actor.mu.0/.2/.4.{weight,bias})
+ *   critic: W1[200][8] b1[200] W2[150][200] b2[150] W3[1][150] b3[1], ReLU ReLU linear (critic.qf0.0/.2/.4.{weight,bias}),
+ *           input = concat(obs[6], action[2])
+ * The parameter vectors are arguments of every call (read in place: the caller's optimiser and Polyak update write them).  Every
+ * call only enqueues on `stream`, nothing is allocated after create, no floating-point atomic: two runs on the same inputs
+ * return identical bytes.  The forwards run in fp32 on the matrix cores; hidden activations stay on the chip. */
+#define BRS_DDPG_NACTOR (300 * 6 + 300 + 200 * 300 + 200 + 2 * 200 + 2)  /* 62,702 */
+#define BRS_DDPG_NCRITIC (200 * 8 + 200 + 150 * 200 + 150 + 1 * 150 + 1) /* 32,101 */
+#define BRS_DDPG_TAG_ACT 0x44445047u    /* "DDPG": second Philox counter word of brs_ddpg_act */
+#define BRS_DDPG_TAG_SAMPLE 0x5245504cu /* "REPL": ... of brs_replay_sample */
+
+typedef struct brs_ddpg brs_ddpg;
+
+int brs_ddpg_create(int32_t device, brs_ddpg** out);
+int brs_ddpg_destroy(brs_ddpg*);
+const char* brs_ddpg_last_error(const brs_ddpg*);
+/* SB3's _sample_action for n envs.  mean = actor(obs), or with random != 0 (the learning_starts phase) a uniform draw per
+ * component; action = clip(mean + sigma z, -1, 1) in both modes (SB3 adds the action noise during warm-up too); sigma == 0 is
+ * predict(deterministic=True).  One action: what the buffer stores is what the env consumes.  mean_dev and noise_dev [n][2] may
+ * be NULL.  Randomness: Philox4x32-10(counter = (step, BRS_DDPG_TAG_ACT, gid_lo, gid_hi), key = seed), gid = env_index_base + i;
+ * words 0 and 1 -> z[0], z[1] by the Box-Muller of brs_policy_act (u = ((w >> 8) + 0.5) / 2^24, r = sqrt(-2 ln u1),
+ * z = r cos / sin(2 pi u2)); words 2 and 3 -> the uniform components, ((w >> 8) - 2^23) / 2^23 in [-1, 1 - 2^-23]. */
+int brs_ddpg_act(brs_ddpg*, const float* actor_dev, int32_t n, const float* obs_dev, uint64_t seed, int64_t env_index_base,
+                 uint32_t step, float sigma, int32_t random, float* action_dev, float* mean_dev, float* noise_dev, void* stream);
+/* q[n] = critic(concat(obs[n][6], act[n][2])) */
+int brs_ddpg_q(brs_ddpg*, const float* critic_dev, int32_t n, const float* obs_dev, const float* act_dev, float* q_dev, void* stream);
+/* y[m] = reward + (1 - done) gamma Q'(next_obs, pi'(next_obs)) from the two TARGET networks, one launch; a row with done != 0
+ * gets y == reward exactly */
+int brs_ddpg_td_target(brs_ddpg*, const float* actor_target_dev, const float* critic_target_dev, int32_t m, const float* next_obs_dev,
+                       const float* reward_dev, const uint8_t* done_dev, float gamma, float* y_dev, void* stream);
+
+/* Replay buffer: the caller owns the storage, time is the major axis as in SB3: obs[cap][n][6], next_obs[cap][n][6],
+ * action[cap][n][2], reward[cap][n], done[cap][n].  The same struct names the five contiguous [m]-leading outputs of a sample.
+ * No handle: errors go to a per-thread slot (brs_replay_last_error).  cap * n <= 2^31 - 1; offsets are 64-bit. */
+typedef struct brs_replay_storage {
+  float* obs;
+  float* next_obs;
+  float* action;
+  float* reward;
+  uint8_t* done;
+} brs_replay_storage;
+
+/* writes row pos (0 <= pos < cap; the caller advances it modulo cap) from one env step: last_obs (what the action was computed
+ * from), the action, and brs_step's five outputs.  next_obs[i] = terminal_obs[i] where terminated[i] | truncated[i], else
+ * obs[i]; done[i] = terminated[i] != 0 (SB3: dones * (1 - timeouts)): a time-limit end bootstraps, a fall does not. */
+int brs_replay_add(int32_t device, const brs_replay_storage* storage, int32_t n, int32_t cap, int32_t pos, const float* last_obs_dev,
+                   const float* action_dev, const float* obs_dev, const float* reward_dev, const uint8_t* terminated_dev,
+                   const uint8_t* truncated_dev, const float* terminal_obs_dev, void* stream);
+/* m uniform samples from the first `size` rows (1 <= size <= cap: pos until the first wrap, then cap), index and gather in one
+ * kernel.  Sample j takes Philox4x32-10(counter = (draw, BRS_DDPG_TAG_SAMPLE, j, 0), key = seed): row = (w0 * size) >> 32,
+ * env = (w1 * n) >> 32, two independent draws as SB3 makes them; the probability of a cell deviates from 1 / (size n) by at most
+ * n / 2^32 relative (size / 2^32 for the row).  idx_dev [m][2] int32 (row, env) may be NULL. */
+int brs_replay_sample(int32_t device, const brs_replay_storage* storage, int32_t n, int32_t cap, int32_t size, int32_t m,
+                      uint64_t seed, uint32_t draw, const brs_replay_storage* out, int32_t* idx_dev, void* stream);
+const char* brs_replay_last_error(void);
 
 #ifdef __cplusplus
 }
