@@ -18,6 +18,8 @@ include/brs.h (libbrs_hip.so).  This package is the host-side mirror of the refe
                                            SB3's DDPG between two gradient steps -- actor with action noise, replay buffer with the
                                            terminal-observation and time-limit rules, uniform sampling, TD targets -- as HIP kernels
                                            (include/brs_policy.h: brs_ddpg_*, brs_replay_*): the data path of sb_rl.py:72-83
+    offpolicy.DeviceDDPGLearner            SB3's TD3.train as DDPG uses it -- critic and actor gradient, Adam, Polyak update -- as HIP
+                                           kernels (include/brs_policy.h: brs_ddpg_learner_*): the learner side of sb_rl.py:72-83
     quant.quantize_policy / QuantPolicy    int8 post-training quantisation of the actor and the int8 network as a HIP kernel
                                            (include/brs_qpolicy.h): quantize_tflite.py and sb_rl.py:285-364 on the GPU
 
@@ -25,14 +27,14 @@ There is no CPU fallback: creating a sim without a HIP device raises.
 """
 from .registry import ENV_SPECS, make_vec, spec  # noqa: F401
 from .learner import DevicePPOLearner, LearnerStats  # noqa: F401
-from .offpolicy import (DeviceDDPGNets, DeviceOffPolicyCollector, DeviceReplayBuffer, flatten_ddpg_state_dict,  # noqa: F401
+from .offpolicy import (DeviceDDPGLearner, DeviceDDPGNets, DeviceOffPolicyCollector, DeviceReplayBuffer, flatten_ddpg_state_dict,  # noqa: F401
                         unflatten_ddpg_state_dict)
 from .monitor import EpisodeMonitor, EpisodeStats, episode_count_targets, evaluate_policy  # noqa: F401
 from .quant import REFERENCE_CALIBRATION, QuantModel, QuantPolicy, quantize_policy  # noqa: F401
 from .sim import BatchedSim, BrsError  # noqa: F401
 from .vec_env import BalanceVecEnv  # noqa: F401
 
-__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "DeviceDDPGNets", "DeviceOffPolicyCollector", "DevicePPOLearner", "DeviceReplayBuffer", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "LearnerStats",
+__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "DeviceDDPGLearner", "DeviceDDPGNets", "DeviceOffPolicyCollector", "DevicePPOLearner", "DeviceReplayBuffer", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "LearnerStats",
            "QuantModel", "QuantPolicy",
            "REFERENCE_CALIBRATION", "episode_count_targets", "evaluate_policy", "flatten_ddpg_state_dict", "make_vec", "quantize_policy", "spec",
            "unflatten_ddpg_state_dict"]

@@ -22,10 +22,12 @@ SIM_FLAGS = ["-Xarch_device", "-ffast-math", "-Xarch_device", "-fgpu-flush-denor
              "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 # the translation units of libbrs_hip.so: (source, its own flags, in the build id).  Policy / GAE kernels, renderer and int8 actor
 # keep IEEE math (checked against fp32 torch at rtol 1e-5 / bit for bit against their host builds under tests/), and so does the
-# episode monitor, the PPO learner (fp64 torch autograd at 1e-5 per parameter block) and the DDPG data path (fp64 numpy at 1e-5);
-# the build id names the step and policy kernels that committed profiles were measured on, so the other five units stay out of it.
+# episode monitor, the PPO learner (fp64 torch autograd at 1e-5 per parameter block), the DDPG data path (fp64 numpy at 1e-5) and
+# the DDPG learner (fp64 torch autograd at 1e-5 per block); the build id names the step and policy kernels that committed profiles
+# were measured on, so the other six units stay out of it.
 UNITS = [("brs_kernels.hip", SIM_FLAGS, True), ("brs_policy.hip", [], True), ("brs_render.hip", [], False), ("brs_qpolicy.hip", [], False),
-         ("brs_monitor.hip", [], False), ("brs_learner.hip", [], False), ("brs_offpolicy.hip", [], False)]
+         ("brs_monitor.hip", [], False), ("brs_learner.hip", [], False), ("brs_offpolicy.hip", [], False),
+         ("brs_ddpg_learner.hip", [], False)]
 SRC = os.path.join(_CSRC, UNITS[0][0])  # the unit that takes the A/B flags and the build id stamp
 # what the build id hashes next to the sources of its units; brs_host.hpp holds no kernel code and stays out of it
 HEADERS = [os.path.join(_CSRC, h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp")] + \
@@ -55,12 +57,17 @@ class BrsEpisodeStats(C.Structure):
 
 
 LEARNER_NSTAT = 5
+DDPG_NSTAT = 2                                                  # BRS_DDPG_NSTAT
 
 
 class BrsPpoConfig(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("lr", "beta1", "beta2", "eps")] + \
                [(k, C.c_float) for k in ("clip_range", "vf_coef", "ent_coef", "max_grad_norm_pi", "max_grad_norm_vf", "target_kl", "ret_scale")] + \
                [(k, C.c_int32) for k in ("normalize_adv", "actor_on", "joint_norm")]
+
+
+class BrsAdamConfig(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("lr", "beta1", "beta2", "eps")]
 
 
 class BrsLearnerInfo(C.Structure):
@@ -183,6 +190,13 @@ SIGNATURES = {
         "brs_replay_sample": (C.c_int, [_i32, C.POINTER(BrsReplayStorage), _i32, _i32, _i32, _i32, C.c_uint64, C.c_uint32,
                                         C.POINTER(BrsReplayStorage), _vp, _vp]),
         "brs_replay_last_error": (C.c_char_p, []),
+        "brs_ddpg_learner_create": (C.c_int, [_i32, _i32, C.POINTER(_vp)]),
+        "brs_ddpg_learner_destroy": (C.c_int, [_vp]),
+        "brs_ddpg_learner_last_error": (C.c_char_p, [_vp]),
+        "brs_ddpg_learner_scratch": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_int64)]),
+        "brs_ddpg_learner_critic_grad": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+        "brs_ddpg_learner_actor_grad": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+        "brs_ddpg_learner_apply": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(BrsAdamConfig), C.c_int64, _f32, _vp]),
     },
     "brs_render.h": {
         "brs_render_default_camera": (None, [C.POINTER(BrsCamera)]),

@@ -136,7 +136,8 @@ BRS_HD bool kl_stops(float kl, const brs_ppo_config& c) { return c.target_kl > 0
 struct AdamScalars {
   float step_size, bc2_sqrt, w1, beta2, w2, eps;
 };
-BRS_HD AdamScalars adam_scalars(const brs_ppo_config& c, int64_t step) {
+template <class Config>  // brs_ppo_config, brs_adam_config: anything with lr, beta1, beta2, eps in fp64
+BRS_HD AdamScalars adam_scalars(const Config& c, int64_t step) {
   const double bc1 = 1.0 - pow(c.beta1, (double)step), bc2 = 1.0 - pow(c.beta2, (double)step);
   return AdamScalars{(float)(c.lr / bc1), (float)sqrt(bc2), (float)(1.0 - c.beta1), (float)c.beta2, (float)(1.0 - c.beta2), (float)c.eps};
 }

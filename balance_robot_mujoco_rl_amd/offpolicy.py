@@ -5,7 +5,8 @@ net_arch = dict(pi=[300, 200], qf=[200, 150]) and NormalActionNoise(sigma=0.1). 
 deterministic actor, adds the noise, steps the env, stores the transition in a host-side numpy ReplayBuffer (terminal observation
 and time-limit rules per env, in Python), samples a uniform minibatch and evaluates the two target networks.  `DeviceDDPGNets`,
 `DeviceReplayBuffer` and `DeviceOffPolicyCollector` do all of that in HIP kernels of libbrs_hip.so on the simulator's own output
-tensors.  The gradient step is the caller's (tools/train_ddpg_torch.py does it in torch).  PyTorch only owns the buffers and the
+tensors.  The gradient step -- critic and actor gradient, Adam, Polyak update -- is `DeviceDDPGLearner` (brs_ddpg_learner_*;
+DESIGN.md 7.6), or the caller's (tools/train_ddpg_torch.py does it in torch by default).  PyTorch only owns the buffers and the
 stream."""
 import ctypes as C
 
@@ -259,3 +260,119 @@ class DeviceOffPolicyCollector:
             replay.add(self._last_obs, self._action, obs, tobs, rew, term, trunc)
             self._last_obs.copy_(obs)
         return self
+
+
+class DeviceDDPGLearner:
+    """SB3's TD3.train as DDPG uses it (one critic, no delay, no target noise) by the HIP kernels of brs_ddpg_learner_*: the
+    gradient of mse(Q(s, a), y) w.r.t. the critic, the gradient of -mean Q(s, pi(s)) w.r.t. the actor, torch.optim.Adam's step and
+    the Polyak update.  The four networks are the caller's flat float32 device tensors, updated in place; this object owns the two
+    gradient buffers, the four moment vectors and the two step counters.  grad and apply are separate calls: a data-parallel
+    caller all-reduces-and-divides `grad_critic` / `grad_actor` in between."""
+
+    def __init__(self, device=0, max_batch=256, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, tau=0.005):
+        if not torch.cuda.is_available():
+            raise BrsError("no HIP device visible to PyTorch: the on-device DDPG learner has no CPU fallback")
+        self.L = _lib.lib()
+        self.device = _device(device)
+        self.max_batch, self.tau = int(max_batch), float(tau)
+        self.cfg = _lib.BrsAdamConfig(float(lr), float(betas[0]), float(betas[1]), float(eps))
+        h = C.c_void_p()
+        rc = self.L.brs_ddpg_learner_create(self.device.index, self.max_batch, C.byref(h))
+        if rc != 0:
+            raise BrsError(f"brs_ddpg_learner_create failed ({rc}): {self.L.brs_ddpg_learner_last_error(None).decode()}")
+        self.h = h
+        z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.grad_critic, self.grad_actor = z(NCRITIC + _lib.DDPG_NSTAT), z(NACTOR + _lib.DDPG_NSTAT)
+        self.m_critic, self.v_critic, self.m_actor, self.v_actor = z(NCRITIC), z(NCRITIC), z(NACTOR), z(NACTOR)
+        self.steps_critic = self.steps_actor = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.brs_ddpg_learner_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise BrsError(f"{what} failed ({rc}): {self.L.brs_ddpg_learner_last_error(self.h).decode()}")
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def scratch(self):
+        """(device address, bytes) of the handle's one allocation"""
+        ptr, size = C.c_void_p(), C.c_int64()
+        self._check(self.L.brs_ddpg_learner_scratch(self.h, C.byref(ptr), C.byref(size)), "brs_ddpg_learner_scratch")
+        return ptr.value, size.value
+
+    def critic_grad(self, critic, obs, action, y, out=None):
+        """-> [NCRITIC + 2]: the gradient of Lc = mean (Q(s, a) - y)^2 in the critic's flat order, then Lc and mean Q"""
+        d, f32, m = self.device, torch.float32, obs.shape[0]
+        out = self.grad_critic if out is None else out
+        _need(critic, "critic", f32, (NCRITIC,), d); _need(obs, "obs", f32, (m, 6), d); _need(action, "action", f32, (m, 2), d)
+        _need(y, "y", f32, (m,), d); _need(out, "grad", f32, (NCRITIC + _lib.DDPG_NSTAT,), d)
+        self._check(self.L.brs_ddpg_learner_critic_grad(self.h, _p(critic), m, _p(obs), _p(action), _p(y), _p(out), self._stream()),
+                    "brs_ddpg_learner_critic_grad")
+        return out
+
+    def actor_grad(self, actor, critic, obs, out=None):
+        """-> [NACTOR + 2]: the gradient of La = -mean Q(s, pi(s)) in the actor's flat order (through `critic`, which gets none),
+        then La and the mean of pi(s)^2"""
+        d, f32, m = self.device, torch.float32, obs.shape[0]
+        out = self.grad_actor if out is None else out
+        _need(actor, "actor", f32, (NACTOR,), d); _need(critic, "critic", f32, (NCRITIC,), d); _need(obs, "obs", f32, (m, 6), d)
+        _need(out, "grad", f32, (NACTOR + _lib.DDPG_NSTAT,), d)
+        self._check(self.L.brs_ddpg_learner_actor_grad(self.h, _p(actor), _p(critic), m, _p(obs), _p(out), self._stream()),
+                    "brs_ddpg_learner_actor_grad")
+        return out
+
+    def _apply(self, n, params, grad, mom, vel, target, step, name):
+        d, f32 = self.device, torch.float32
+        _need(params, name, f32, (n,), d); _need(grad, "grad", f32, (n + _lib.DDPG_NSTAT,), d)
+        _need(mom, "m_" + name, f32, (n,), d); _need(vel, "v_" + name, f32, (n,), d)
+        if target is not None:
+            _need(target, name + "_target", f32, (n,), d)
+        self._check(self.L.brs_ddpg_learner_apply(self.h, n, _p(params), _p(grad), _p(mom), _p(vel), _p(target), C.byref(self.cfg), step,
+                                                  self.tau, self._stream()), "brs_ddpg_learner_apply")
+
+    def apply_critic(self, critic, critic_target=None, grad=None):
+        """Adam's step on `critic` from grad_critic (or `grad`), then critic_target += tau (critic - critic_target)"""
+        self._apply(NCRITIC, critic, self.grad_critic if grad is None else grad, self.m_critic, self.v_critic, critic_target,
+                    self.steps_critic + 1, "critic")
+        self.steps_critic += 1
+
+    def apply_actor(self, actor, actor_target=None, grad=None):
+        self._apply(NACTOR, actor, self.grad_actor if grad is None else grad, self.m_actor, self.v_actor, actor_target,
+                    self.steps_actor + 1, "actor")
+        self.steps_actor += 1
+
+    def step(self, flat, obs, action, y):
+        """the whole gradient step on a dict of the four flat vectors (actor, critic, actor_target, critic_target) in SB3's order:
+        critic gradient and step, actor gradient WITH THE UPDATED CRITIC and step; each apply moves its own target"""
+        self.critic_grad(flat["critic"], obs, action, y)
+        self.apply_critic(flat["critic"], flat["critic_target"])
+        self.actor_grad(flat["actor"], flat["critic"], obs)
+        self.apply_actor(flat["actor"], flat["actor_target"])
+
+    def stats(self):
+        """the four means of the last two gradient calls, one device-to-host copy: critic_loss, mean_q, actor_loss, mean_action_sq"""
+        s = torch.cat([self.grad_critic[NCRITIC:], self.grad_actor[NACTOR:]]).cpu().tolist()
+        return dict(zip(("critic_loss", "mean_q", "actor_loss", "mean_action_sq"), s))
+
+    def state_dict(self):
+        return {"m_critic": self.m_critic.clone(), "v_critic": self.v_critic.clone(), "m_actor": self.m_actor.clone(),
+                "v_actor": self.v_actor.clone(), "steps_critic": self.steps_critic, "steps_actor": self.steps_actor}
+
+    def load_state_dict(self, sd):
+        for k in ("m_critic", "v_critic", "m_actor", "v_actor"):
+            t = getattr(self, k)
+            src = torch.as_tensor(sd[k])
+            if tuple(src.shape) != tuple(t.shape):
+                raise ValueError(f"{k}: expected shape {tuple(t.shape)}, got {tuple(src.shape)}")
+            t.copy_(src.to(device=self.device, dtype=torch.float32))
+        self.steps_critic, self.steps_actor = int(sd["steps_critic"]), int(sd["steps_actor"])

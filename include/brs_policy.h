@@ -27,6 +27,12 @@
  *   brs_ddpg_td_target    TD3.train's target with target_policy_noise = 0 and one critic: r + (1 - done) gamma Q'(s', pi'(s'))
  *   brs_ddpg_q            the critic forward Q(s, a)
  *
+ * and the gradient step itself (TD3.train as DDPG uses it: one critic, no delay, no target noise):
+ *
+ *   brs_ddpg_learner_critic_grad  the gradient of mse(Q(s, a), y) w.r.t. the critic
+ *   brs_ddpg_learner_actor_grad   the gradient of -mean Q(s, pi(s)) w.r.t. the actor, through the critic to its action inputs
+ *   brs_ddpg_learner_apply        torch.optim.Adam's step on one network and polyak_update of its target
+ *
  * These entry points do the same arithmetic on the GPU, reading the simulator's outputs in place (device pointers),
  * so that a rollout of 65,536 envs needs no per-env Python and no PCIe traffic.  All buffers are DEVICE pointers owned
  * by the caller; every call only enqueues work on `stream`.  Same library (libbrs_hip.so), same status codes as brs.h.
@@ -234,6 +240,38 @@ int brs_replay_add(int32_t device, const brs_replay_storage* storage, int32_t n,
 int brs_replay_sample(int32_t device, const brs_replay_storage* storage, int32_t n, int32_t cap, int32_t size, int32_t m,
                       uint64_t seed, uint32_t draw, const brs_replay_storage* out, int32_t* idx_dev, void* stream);
 const char* brs_replay_last_error(void);
+
+/* ---- DDPG learner: the gradient step between two TD targets.  SB3's order is critic_grad, apply (critic),
+ * actor_grad WITH THE UPDATED CRITIC, apply (actor); the Polyak update of a network is fused into its own apply (the critic
+ * target is read only by the next brs_ddpg_td_target).  grad and apply are separate calls so that a data-parallel caller can
+ * all-reduce-and-divide the buffer in between: all three calls write MEANS over the m rows.  The handle owns the scratch that
+ * max_batch rows need ([unit][sample] images of the activations and their gradients); calls on one handle must be ordered on
+ * one stream.  Every call only enqueues, nothing is allocated after create, no floating-point atomic, no communication between
+ * workgroups: two runs on the same inputs return identical bytes.  Arguments are checked before a device is looked for. */
+#define BRS_DDPG_NSTAT 2
+typedef struct brs_ddpg_learner brs_ddpg_learner;
+typedef struct brs_adam_config { double lr, beta1, beta2, eps; } brs_adam_config; /* fp64, as torch holds them */
+
+int brs_ddpg_learner_create(int32_t device, int32_t max_batch, brs_ddpg_learner** out);
+int brs_ddpg_learner_destroy(brs_ddpg_learner*);
+const char* brs_ddpg_learner_last_error(const brs_ddpg_learner*);
+/* the handle's one device allocation (activation images, then the partial rows) and its size: memory accounting, and the tests
+ * fill it with NaN before a call to show that a call reads nothing it has not written itself.  Enqueues nothing. */
+int brs_ddpg_learner_scratch(brs_ddpg_learner*, void** scratch_dev, int64_t* bytes);
+/* grad_dev[BRS_DDPG_NCRITIC + 2]: gradient of Lc = mean_i (Q(s_i, a_i) - y_i)^2 in the critic's flat order, then Lc and
+ * mean_i Q(s_i, a_i); 1 <= m <= max_batch */
+int brs_ddpg_learner_critic_grad(brs_ddpg_learner*, const float* critic_dev, int32_t m, const float* obs_dev, const float* act_dev,
+                                 const float* y_dev, float* grad_dev, void* stream);
+/* grad_dev[BRS_DDPG_NACTOR + 2]: gradient of La = -mean_i Q(s_i, pi(s_i)) in the actor's flat order, then La and the mean of
+ * pi(s)^2 over rows and both components (how saturated the tanh is).  The critic's weights get no gradient. */
+int brs_ddpg_learner_actor_grad(brs_ddpg_learner*, const float* actor_dev, const float* critic_dev, int32_t m, const float* obs_dev,
+                                float* grad_dev, void* stream);
+/* torch.optim.Adam (no amsgrad, no weight decay) on params / m / v in place from grad_dev[0 .. n_param), step counted from 1 by
+ * the CALLER (bias corrections formed in fp64 on the host); then, if target_dev is not NULL,
+ * target += tau * (params_new - target).  Element-wise: any n_param >= 1.  step >= 1, 0 <= tau <= 1, lr and eps >= 0, betas in
+ * [0, 1). */
+int brs_ddpg_learner_apply(brs_ddpg_learner*, int32_t n_param, float* params_dev, const float* grad_dev, float* m_dev, float* v_dev,
+                           float* target_dev, const brs_adam_config* cfg, int64_t step, float tau, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,13 @@ net_arch = dict(pi=[300, 200], qf=[200, 150]), NormalActionNoise(sigma=0.1)).  T
                   next kernel without a copy.
 
 In both paths torch does the critic loss mse(Q(s, a), y), the actor loss -mean Q(s, pi(s)), the two Adam steps and the Polyak
-update.  Evaluation: evaluate_policy / EpisodeMonitor with sigma = 0."""
+update, unless
+
+  --device-learner  (with --device-data) the gradient step too is HIP kernels: DeviceDDPGLearner.step on the four flat vectors
+                  (DESIGN.md 7.6).  The modules' parameters are views of them, so evaluation and state_dict keep working; the
+                  logged losses are read once at the end.
+
+Evaluation: evaluate_policy / EpisodeMonitor with sigma = 0."""
 import argparse
 import json
 import os
@@ -167,9 +173,11 @@ class DeviceData:
         return self.nets.td_target(self.model.flat["actor_target"], self.model.flat["critic_target"], next_obs, reward, done, gamma)
 
 
-def train(sim, model, data, steps, batch=256, learning_starts=100, gamma=0.99, gradient_steps=1, train_freq=1, monitor=None, log=None):
+def train(sim, model, data, steps, batch=256, learning_starts=100, gamma=0.99, gradient_steps=1, train_freq=1, monitor=None, log=None,
+          learner=None):
     """`steps` env steps of every env: collect train_freq steps, then gradient_steps updates once learning_starts TRANSITIONS are
-    in (SB3 counts num_timesteps over all envs); until then the actions are uniform"""
+    in (SB3 counts num_timesteps over all envs); until then the actions are uniform.  `learner`: a DeviceDDPGLearner that takes
+    the gradient step on model.flat instead of model.gradient_step"""
     losses, t, updates = [], 0, 0
     while t < steps:
         k = min(train_freq, steps - t)
@@ -179,10 +187,16 @@ def train(sim, model, data, steps, batch=256, learning_starts=100, gamma=0.99, g
             for _ in range(gradient_steps):
                 obs, next_obs, action, reward, done = data.sample(batch)
                 y = data.td_target(next_obs, reward, done, gamma)
-                losses.append(model.gradient_step(obs, action, y))
+                if learner is not None:
+                    learner.step(model.flat, obs, action, y)
+                else:
+                    losses.append(model.gradient_step(obs, action, y))
                 updates += 1
     if log is not None and losses:
         log["critic_loss_last"], log["actor_loss_last"] = (float(x) for x in losses[-1])
+    if log is not None and learner is not None and updates:
+        s = learner.stats()   # one read at the end, not one per update
+        log["critic_loss_last"], log["actor_loss_last"] = s["critic_loss"], s["actor_loss"]
     return updates
 
 
@@ -216,9 +230,12 @@ def main():
     ap.add_argument("--train-freq", type=int, default=1, help="env steps between two rounds of updates")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device-data", action="store_true", help="collection, buffer, sampling and TD targets by the HIP kernels")
+    ap.add_argument("--device-learner", action="store_true", help="the gradient step by the HIP kernels too (needs --device-data)")
     ap.add_argument("--eval-episodes", type=int, default=0); ap.add_argument("--eval-envs", type=int, default=256)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.device_learner and not a.device_data:
+        ap.error("--device-learner requires --device-data")
     from balance_robot_mujoco_rl_amd import BatchedSim, EpisodeMonitor, _lib
     sim = BatchedSim(a.env, a.envs, device=0, seed=a.seed, auto_reset=True)
     cap = a.capacity_steps or max(1, 1_000_000 // a.envs)
@@ -227,8 +244,14 @@ def main():
     monitor = EpisodeMonitor(a.envs, device=sim.device, max_len=max(1, int(sim.max_episode_steps)))
     data = DeviceData(sim, model, cap, a.sigma, a.seed) if a.device_data else TorchData(sim, model, cap, a.sigma, a.seed)
     log = {"args": vars(a), "build_id": _lib.build_id(), "data_path": "device" if a.device_data else "torch"}
+    learner = None
+    if a.device_learner:
+        from balance_robot_mujoco_rl_amd.offpolicy import DeviceDDPGLearner
+        learner = DeviceDDPGLearner(device=sim.device, max_batch=a.batch, lr=a.lr, tau=a.tau)
+        log["learner"] = "device"
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    log["updates"] = train(sim, model, data, a.steps, a.batch, a.learning_starts, a.gamma, a.gradient_steps, a.train_freq, monitor, log)
+    log["updates"] = train(sim, model, data, a.steps, a.batch, a.learning_starts, a.gamma, a.gradient_steps, a.train_freq, monitor, log,
+                           learner=learner)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
     s = monitor.stats()
     log.update(seconds=dt, env_steps=a.steps * a.envs, env_steps_per_s=a.steps * a.envs / dt, monitor_steps=s.steps, train_episodes=s.episodes,
@@ -241,6 +264,8 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             json.dump(log, f, indent=1)
+    if learner is not None:
+        learner.close()
     monitor.close(); sim.close()
 
 
