@@ -20,6 +20,10 @@ include/brs.h (libbrs_hip.so).  This package is the host-side mirror of the refe
                                            (include/brs_policy.h: brs_ddpg_*, brs_replay_*): the data path of sb_rl.py:72-83
     offpolicy.DeviceDDPGLearner            SB3's TD3.train as DDPG uses it -- critic and actor gradient, Adam, Polyak update -- as HIP
                                            kernels (include/brs_policy.h: brs_ddpg_learner_*): the learner side of sb_rl.py:72-83
+    offpolicy.DeviceTD3Learner / DeviceDDPGNets.td3_target
+                                           TD3's three changes to that recipe -- smoothed twin-critic target, twin critic gradient,
+                                           delayed actor and target updates -- (include/brs_policy.h: brs_td3_td_target,
+                                           brs_ddpg_learner_twin_critic_grad): sb_rl.py's `-a TD3` with the DDPG net_arch
     quant.quantize_policy / QuantPolicy    int8 post-training quantisation of the actor and the int8 network as a HIP kernel
                                            (include/brs_qpolicy.h): quantize_tflite.py and sb_rl.py:285-364 on the GPU
 
@@ -27,14 +31,14 @@ There is no CPU fallback: creating a sim without a HIP device raises.
 """
 from .registry import ENV_SPECS, make_vec, spec  # noqa: F401
 from .learner import DevicePPOLearner, LearnerStats  # noqa: F401
-from .offpolicy import (DeviceDDPGLearner, DeviceDDPGNets, DeviceOffPolicyCollector, DeviceReplayBuffer, flatten_ddpg_state_dict,  # noqa: F401
-                        unflatten_ddpg_state_dict)
+from .offpolicy import (DeviceDDPGLearner, DeviceDDPGNets, DeviceOffPolicyCollector, DeviceReplayBuffer, DeviceTD3Learner,  # noqa: F401
+                        flatten_ddpg_state_dict, flatten_td3_critics, unflatten_ddpg_state_dict, unflatten_td3_critics)
 from .monitor import EpisodeMonitor, EpisodeStats, episode_count_targets, evaluate_policy  # noqa: F401
 from .quant import REFERENCE_CALIBRATION, QuantModel, QuantPolicy, quantize_policy  # noqa: F401
 from .sim import BatchedSim, BrsError  # noqa: F401
 from .vec_env import BalanceVecEnv  # noqa: F401
 
-__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "DeviceDDPGLearner", "DeviceDDPGNets", "DeviceOffPolicyCollector", "DevicePPOLearner", "DeviceReplayBuffer", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "LearnerStats",
+__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "DeviceDDPGLearner", "DeviceDDPGNets", "DeviceOffPolicyCollector", "DevicePPOLearner", "DeviceReplayBuffer", "DeviceTD3Learner", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "LearnerStats",
            "QuantModel", "QuantPolicy",
-           "REFERENCE_CALIBRATION", "episode_count_targets", "evaluate_policy", "flatten_ddpg_state_dict", "make_vec", "quantize_policy", "spec",
-           "unflatten_ddpg_state_dict"]
+           "REFERENCE_CALIBRATION", "episode_count_targets", "evaluate_policy", "flatten_ddpg_state_dict", "flatten_td3_critics", "make_vec", "quantize_policy", "spec",
+           "unflatten_ddpg_state_dict", "unflatten_td3_critics"]

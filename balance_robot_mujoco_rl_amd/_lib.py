@@ -37,6 +37,7 @@ POLICY_NPARAM = (64 * 6 + 64 + 64 * 64 + 64 + 2 * 64 + 2) + (64 * 6 + 64 + 64 * 
 DDPG_NACTOR = 300 * 6 + 300 + 200 * 300 + 200 + 2 * 200 + 2     # BRS_DDPG_NACTOR
 DDPG_NCRITIC = 200 * 8 + 200 + 150 * 200 + 150 + 1 * 150 + 1    # BRS_DDPG_NCRITIC
 DDPG_TAG_ACT, DDPG_TAG_SAMPLE = 0x44445047, 0x5245504c
+TD3_TAG_NOISE = 0x5444334e                                      # BRS_TD3_TAG_NOISE
 
 
 class BrsConfig(C.Structure):
@@ -58,6 +59,7 @@ class BrsEpisodeStats(C.Structure):
 
 LEARNER_NSTAT = 5
 DDPG_NSTAT = 2                                                  # BRS_DDPG_NSTAT
+TD3_NSTAT = 4                                                   # BRS_TD3_NSTAT
 
 
 class BrsPpoConfig(C.Structure):
@@ -186,6 +188,7 @@ SIGNATURES = {
         "brs_ddpg_act": (C.c_int, [_vp, _vp, _i32, _vp, C.c_uint64, C.c_int64, C.c_uint32, _f32, _i32, _vp, _vp, _vp, _vp]),
         "brs_ddpg_q": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
         "brs_ddpg_td_target": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
+        "brs_td3_td_target": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _f32, _f32, _f32, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]),
         "brs_replay_add": (C.c_int, [_i32, C.POINTER(BrsReplayStorage), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "brs_replay_sample": (C.c_int, [_i32, C.POINTER(BrsReplayStorage), _i32, _i32, _i32, _i32, C.c_uint64, C.c_uint32,
                                         C.POINTER(BrsReplayStorage), _vp, _vp]),
@@ -197,6 +200,8 @@ SIGNATURES = {
         "brs_ddpg_learner_critic_grad": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
         "brs_ddpg_learner_actor_grad": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
         "brs_ddpg_learner_apply": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(BrsAdamConfig), C.c_int64, _f32, _vp]),
+        "brs_ddpg_learner_create_twin": (C.c_int, [_i32, _i32, C.POINTER(_vp)]),
+        "brs_ddpg_learner_twin_critic_grad": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     },
     "brs_render.h": {
         "brs_render_default_camera": (None, [C.POINTER(BrsCamera)]),

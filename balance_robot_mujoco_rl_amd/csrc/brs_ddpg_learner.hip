@@ -19,6 +19,10 @@
 //                                column c of the partials is summed in ascending order in fp64.  Below that the two kernels
 //                                write the gradient buffer themselves.
 //   ddpg_apply_kernel            element-wise: Adam, then target += tau (param - target).
+// TD3's twin critics are the same kernels with the critic's index on a free grid axis: blockIdx.y of the backward
+// kernel, blockIdx.z of the two sample-contracting ones.  Critic k reads critics + k NCRITIC, keeps its activations in the k-th
+// critic-sized scratch image and writes block k of the buffer (or of a partial row); one combine covers both.  What one critic
+// computes does not depend on the other's presence: block k is brs_ddpg_learner_critic_grad's result byte for byte.
 // Padding: a row past m runs on zero inputs; its dq / dz3 is zero, so every product it enters is zero, and it is left out of the
 // statistics and of the 1 / m.  Padded units are zeros in the LDS image, their scratch rows are written (as zeros) by every call
 // and their gradient is never stored.  No floating-point atomic, no communication between workgroups.
@@ -40,15 +44,25 @@ using brs::learner::AdamScalars;
 
 constexpr int MAX_SPLIT = 8, SPLIT_ROWS = 256;
 constexpr int pad128(int x) { return (x + 127) / 128 * 128; }
-// rows of the scratch (each `ld` floats, ld = max_batch padded to the workgroup's 128 rows): sized for the actor, the wider net
-constexpr int S_H1 = 0, S_H2 = S_H1 + Tile<Actor>::H1P, S_DZ1 = S_H2 + Tile<Actor>::H2P, S_DZ2 = S_DZ1 + Tile<Actor>::H1P,
-              S_Z3 = S_DZ2 + Tile<Actor>::H2P, S_ROWS = S_Z3 + Z3_ROWS;
+// rows of a scratch image (each `ld` floats, ld = max_batch padded to the workgroup's 128 rows) sized for network N.  The single
+// calls use the actor's, the wider net, for both networks; the twin call keeps two images of the critic's back to back.
+template <class N> struct Layout {
+  static constexpr int H1 = 0, H2 = H1 + Tile<N>::H1P, DZ1 = H2 + Tile<N>::H2P, DZ2 = DZ1 + Tile<N>::H1P, Z3 = DZ2 + Tile<N>::H2P, ROWS = Z3 + Z3_ROWS;
+};
+using Wide = Layout<Actor>;
+using Narrow = Layout<Critic>;
 static_assert(Tile<Critic>::H1P <= Tile<Actor>::H1P && Tile<Critic>::H2P <= Tile<Actor>::H2P, "the critic fits in the actor's scratch");
+constexpr int TWIN_LEN = 2 * nparam<Critic>() + BRS_TD3_NSTAT;  // the twin gradient buffer / a twin partial row
+static_assert(BRS_TD3_NSTAT == 2 * NSTAT, "two statistics per critic");
+constexpr int SCRATCH_ROWS = Wide::ROWS, TWIN_SCRATCH_ROWS = 2 * Narrow::ROWS > Wide::ROWS ? 2 * Narrow::ROWS : Wide::ROWS;
+constexpr int PARTIAL_LEN = row_len<Actor>(), TWIN_PARTIAL_LEN = TWIN_LEN > row_len<Actor>() ? TWIN_LEN : row_len<Actor>();
 
 struct Scratch {
   float* base;
   int ld;
   __device__ __forceinline__ float* row(int r) const { return base + (size_t)r * ld; }
+  // the k-th image of `rows` rows
+  __device__ __forceinline__ Scratch image(int k, int rows) const { return Scratch{base + (size_t)k * rows * ld, ld}; }
 };
 
 // Scratch element (unit 32 mt + BRS_UNIT(r), sample i) = column(...)[UNIFORM_UNIT(mt, r) * ld]: the lane's share of the address
@@ -60,13 +74,13 @@ __device__ __forceinline__ bool bit(const uint32_t* g, int mt, int r) { return (
 
 // what the forward leaves for the backward: the gates as bit masks (tile mt, register r -> bit 16 (mt % 2) + r of word mt / 2), the
 // outputs before the tanh, and, with STORE, the activations in the scratch column of this lane's row
-template <class N, bool STORE> struct Tape {
+template <class N, bool STORE, class Lay = Wide> struct Tape {
   uint32_t g1[(Tile<N>::MT1 + 1) / 2], g2[(Tile<N>::MT2 + 1) / 2];
   float pre[N::OUT];
   float *h1col, *h2col;  // null without STORE
   int ld;
   __device__ __forceinline__ Tape(const Scratch& s, int i)
-      : h1col(STORE ? column(s, S_H1, i) : nullptr), h2col(STORE ? column(s, S_H2, i) : nullptr), ld(s.ld) {
+      : h1col(STORE ? column(s, Lay::H1, i) : nullptr), h2col(STORE ? column(s, Lay::H2, i) : nullptr), ld(s.ld) {
 #pragma unroll
     for (int k = 0; k < (Tile<N>::MT1 + 1) / 2; k++) g1[k] = 0u;
 #pragma unroll
@@ -84,10 +98,10 @@ template <class N, bool STORE> struct Tape {
 };
 
 // dz2 and dz1 of this lane's row into its scratch column
-struct StoreSink {
+template <class Lay = Wide> struct StoreSink {
   float *dz1col, *dz2col;
   int ld;
-  __device__ __forceinline__ StoreSink(const Scratch& s, int i) : dz1col(column(s, S_DZ1, i)), dz2col(column(s, S_DZ2, i)), ld(s.ld) {}
+  __device__ __forceinline__ StoreSink(const Scratch& s, int i) : dz1col(column(s, Lay::DZ1, i)), dz2col(column(s, Lay::DZ2, i)), ld(s.ld) {}
   __device__ __forceinline__ void dz2(int mt, int r, float v) { dz2col[UNIFORM_UNIT(mt, r) * ld] = v; }
   __device__ __forceinline__ void dz1(int mt, int r, float v) { dz1col[UNIFORM_UNIT(mt, r) * ld] = v; }
 };
@@ -153,24 +167,28 @@ __device__ __forceinline__ void backward_tile(const float* __restrict__ w, float
   }
 }
 
-__global__ void __launch_bounds__(THREADS) ddpg_critic_backward_kernel(const float* __restrict__ critic, const int m, const float* __restrict__ obs,
-                                                                       const float* __restrict__ act, const float* __restrict__ y, const Scratch S) {
+// blockIdx.y: which of the critics laid back to back in `critics` (and which scratch image); one critic, one image in the single call
+template <class Lay> __global__ void __launch_bounds__(THREADS) ddpg_critic_backward_kernel(const float* __restrict__ critics, const int m,
+                                                                                            const float* __restrict__ obs, const float* __restrict__ act,
+                                                                                            const float* __restrict__ y, const Scratch all) {
   __shared__ float L[Tile<Critic>::L_SIZE];
+  const float* __restrict__ critic = critics + (size_t)blockIdx.y * nparam<Critic>();
+  const Scratch S = all.image(blockIdx.y, Lay::ROWS);
   const int i = tile_row();  // < gridDim.x * 128 <= S.ld
   float xb[(OBS + ACT) / 2], v[1];
   load_obs_operands(obs, m, i, xb);
   xb[OBS / 2] = i < m ? act[(size_t)ACT * i + wave_half()] : 0.0f;
-  Tape<Critic, true> tape(S, i);
+  Tape<Critic, true, Lay> tape(S, i);
   forward_tile<Critic>(critic, L, xb, v, tape);
   CriticHead hd = {0.0f, 0.0f, 0.0f};
   if (i < m) hd = critic_head(v[0], y[i], 1.0f / (float)m);
   if (finishes_row()) {
-    S.row(S_Z3)[i] = hd.dq;
-    S.row(S_Z3 + 1)[i] = hd.loss;
-    S.row(S_Z3 + 2)[i] = hd.q;
+    S.row(Lay::Z3)[i] = hd.dq;
+    S.row(Lay::Z3 + 1)[i] = hd.loss;
+    S.row(Lay::Z3 + 2)[i] = hd.q;
   }
   const float dz3[1] = {hd.dq};
-  backward_tile<Critic, false>(critic, L, dz3, tape.g1, tape.g2, StoreSink(S, i));
+  backward_tile<Critic, false>(critic, L, dz3, tape.g1, tape.g2, StoreSink<Lay>(S, i));
 }
 
 __global__ void __launch_bounds__(THREADS) ddpg_actor_backward_kernel(const float* __restrict__ actor, const float* __restrict__ critic, const int m,
@@ -194,33 +212,38 @@ __global__ void __launch_bounds__(THREADS) ddpg_actor_backward_kernel(const floa
 #pragma unroll
   for (int k = 0; k < ACT; k++) dz3[k] = (to_action.da[k] + __shfl_xor(to_action.da[k], 32, 64)) * ga[k];  // zero past m: dq is
   if (finishes_row()) {
-    S.row(S_Z3)[i] = dz3[0];
-    S.row(S_Z3 + 1)[i] = dz3[1];
-    S.row(S_Z3 + 2)[i] = i < m ? actor_loss_share(v[0], inv_m) : 0.0f;
-    S.row(S_Z3 + 3)[i] = i < m ? actor_sat_share(a, inv_m) : 0.0f;
+    S.row(Wide::Z3)[i] = dz3[0];
+    S.row(Wide::Z3 + 1)[i] = dz3[1];
+    S.row(Wide::Z3 + 2)[i] = i < m ? actor_loss_share(v[0], inv_m) : 0.0f;
+    S.row(Wide::Z3 + 3)[i] = i < m ? actor_sat_share(a, inv_m) : 0.0f;
   }
-  backward_tile<Actor, true>(actor, L, dz3, ta.g1, ta.g2, StoreSink(S, i));
+  backward_tile<Actor, true>(actor, L, dz3, ta.g1, ta.g2, StoreSink<Wide>(S, i));
 }
 
-// where a workgroup row (blockIdx.y) of the two sample-contracting kernels reads and writes
+// where a workgroup row (blockIdx.y) of the two sample-contracting kernels reads and writes, for the network of its plane
+// (blockIdx.z: 0 in the single calls, the critic's index in the twin call)
 struct Split {
   int mp, span;        // samples padded to 128; samples per split (a multiple of 128)
   float* dst;          // the gradient buffer, or the first partial row
   int stride;          // floats between partial rows
+  int net_stride;      // floats between the parameter blocks of two networks in a row
+  int stat_at;         // where the statistics of network 0 begin in a row; network k's NSTAT follow at + k NSTAT
   __device__ __forceinline__ int begin() const { return blockIdx.y * span; }
   __device__ __forceinline__ int end() const { const int e = begin() + span; return e < mp ? e : mp; }
-  __device__ __forceinline__ float* out() const { return dst + (size_t)blockIdx.y * stride; }
+  __device__ __forceinline__ float* out() const { return dst + (size_t)blockIdx.y * stride + (size_t)blockIdx.z * net_stride; }
+  __device__ __forceinline__ float* stat() const { return dst + (size_t)blockIdx.y * stride + stat_at + blockIdx.z * NSTAT; }
 };
 
 // dW2[u][k] = sum_s dz2[u][s] h1[k][s].  One wave per 32 x 32 tile; lane (c, h) supplies A[u = c][.] and B[.][k = c] for the
 // samples s + 4 h .. s + 4 h + 3 of every group of eight (one 16-byte load per operand), four matrix instructions per group.
-template <class N> __global__ void __launch_bounds__(256) ddpg_dw2_kernel(const Scratch S, const Split sp) {
+template <class N, class Lay> __global__ void __launch_bounds__(256) ddpg_dw2_kernel(const Scratch all, const Split sp) {
   using T = Tile<N>;
+  const Scratch S = all.image(blockIdx.z, Lay::ROWS);
   const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (tile >= T::MT2 * T::MT1) return;  // the whole wave
   const int tu = tile / T::MT1, tk = tile % T::MT1, lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
-  const float* __restrict__ A = S.row(S_DZ2 + 32 * tu + c) + 4 * h;
-  const float* __restrict__ B = S.row(S_H1 + 32 * tk + c) + 4 * h;
+  const float* __restrict__ A = S.row(Lay::DZ2 + 32 * tu + c) + 4 * h;
+  const float* __restrict__ B = S.row(Lay::H1 + 32 * tk + c) + 4 * h;
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; r++) acc[r] = 0.0f;
@@ -249,14 +272,15 @@ __device__ __forceinline__ float wave_sum(float v) {  // a butterfly: every lane
 
 // One wave per row.  Rows [0, H1): dz1[u] -> dW1[u][:] and db1[u]; rows [H1, H1 + H2): dz2[u] -> db2[u], h2[u] -> dW3[:][u];
 // then the OUT + NSTAT per-sample rows -> db3 and the statistics.  Lane l takes samples l, l + 64, ... of the split.
-template <class N> __global__ void __launch_bounds__(256) ddpg_rows_kernel(const Scratch S, const Split sp, const int m, const float* __restrict__ obs,
-                                                                           const float* __restrict__ act) {
+template <class N, class Lay> __global__ void __launch_bounds__(256) ddpg_rows_kernel(const Scratch all, const Split sp, const int m,
+                                                                                      const float* __restrict__ obs, const float* __restrict__ act) {
   using O = Offsets<N>;
+  const Scratch S = all.image(blockIdx.z, Lay::ROWS);
   const int wv = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int s0 = sp.begin() + lane, s1 = sp.end();
   float* __restrict__ out = sp.out();
   if (wv < N::H1) {
-    const float* __restrict__ d1 = S.row(S_DZ1 + wv);
+    const float* __restrict__ d1 = S.row(Lay::DZ1 + wv);
     float acc[N::IN + 1];
 #pragma unroll
     for (int k = 0; k <= N::IN; k++) acc[k] = 0.0f;
@@ -279,15 +303,15 @@ template <class N> __global__ void __launch_bounds__(256) ddpg_rows_kernel(const
     }
   } else if (wv < N::H1 + N::H2) {
     const int u = wv - N::H1;
-    const float* __restrict__ d2 = S.row(S_DZ2 + u);
-    const float* __restrict__ a2 = S.row(S_H2 + u);
+    const float* __restrict__ d2 = S.row(Lay::DZ2 + u);
+    const float* __restrict__ a2 = S.row(Lay::H2 + u);
     float acc[N::OUT + 1];
 #pragma unroll
     for (int k = 0; k <= N::OUT; k++) acc[k] = 0.0f;
     for (int s = s0; s < s1; s += 64) {
       const float t = a2[s];
 #pragma unroll
-      for (int k = 0; k < N::OUT; k++) acc[k] = fmaf(S.row(S_Z3 + k)[s], t, acc[k]);
+      for (int k = 0; k < N::OUT; k++) acc[k] = fmaf(S.row(Lay::Z3 + k)[s], t, acc[k]);
       acc[N::OUT] += d2[s];
     }
 #pragma unroll
@@ -299,11 +323,14 @@ template <class N> __global__ void __launch_bounds__(256) ddpg_rows_kernel(const
     }
   } else if (wv < N::H1 + N::H2 + N::OUT + NSTAT) {
     const int j = wv - N::H1 - N::H2;
-    const float* __restrict__ z = S.row(S_Z3 + j);
+    const float* __restrict__ z = S.row(Lay::Z3 + j);
     float acc = 0.0f;
     for (int s = s0; s < s1; s += 64) acc += z[s];
     acc = wave_sum(acc);
-    if (lane == 0) out[O::B3 + j] = acc;  // b3 is the last block: the statistics follow it in the buffer
+    if (lane == 0) {
+      if (j < N::OUT) out[O::B3 + j] = acc;
+      else sp.stat()[j - N::OUT] = acc;  // single calls: right behind b3, the last block; the twin call: behind both networks
+    }
   }
 }
 
@@ -329,6 +356,7 @@ struct brs_ddpg_learner {
   float* block = nullptr;    // the scratch rows, then MAX_SPLIT partial rows: one allocation
   float* partial = nullptr;
   size_t bytes = 0;
+  bool twin = false;         // from brs_ddpg_learner_create_twin: two critic images fit the rows, a twin row fits a partial row
   std::string err;
 };
 
@@ -337,17 +365,46 @@ using brs::host::DeviceGuard, brs::host::fail;
 namespace {
 
 // the scratch view, the split of m rows and the launches after a backward kernel
-template <class N> void launch_weight_kernels(brs_ddpg_learner* l, int m, const float* obs, const float* act, float* grad, hipStream_t s) {
+template <class N, class Lay = Wide, int NETS = 1> void launch_weight_kernels(brs_ddpg_learner* l, int m, const float* obs, const float* act, float* grad, hipStream_t s) {
   const int mp = pad128(m);
   int nsplit = mp / SPLIT_ROWS;
   nsplit = nsplit < 1 ? 1 : (nsplit > MAX_SPLIT ? MAX_SPLIT : nsplit);
   const int span = pad128((mp + nsplit - 1) / nsplit);
   nsplit = (mp + span - 1) / span;
   const Scratch S{l->block, l->ld};
-  const Split sp{mp, span, nsplit == 1 ? grad : l->partial, row_len<N>()};
-  hipLaunchKernelGGL(ddpg_dw2_kernel<N>, dim3((Tile<N>::MT1 * Tile<N>::MT2 + 3) / 4, nsplit), dim3(256), 0, s, S, sp);
-  hipLaunchKernelGGL(ddpg_rows_kernel<N>, dim3((N::H1 + N::H2 + N::OUT + NSTAT + 3) / 4, nsplit), dim3(256), 0, s, S, sp, m, obs, act);
-  if (nsplit > 1) hipLaunchKernelGGL(ddpg_combine_kernel, dim3((row_len<N>() + 255) / 256), dim3(256), 0, s, l->partial, nsplit, row_len<N>(), grad);
+  // NETS networks side by side in a row of `len` floats: their parameter blocks, then their statistics
+  const int len = NETS * nparam<N>() + NETS * NSTAT;
+  const Split sp{mp, span, nsplit == 1 ? grad : l->partial, len, nparam<N>(), NETS * nparam<N>()};
+  hipLaunchKernelGGL((ddpg_dw2_kernel<N, Lay>), dim3((Tile<N>::MT1 * Tile<N>::MT2 + 3) / 4, nsplit, NETS), dim3(256), 0, s, S, sp);
+  hipLaunchKernelGGL((ddpg_rows_kernel<N, Lay>), dim3((N::H1 + N::H2 + N::OUT + NSTAT + 3) / 4, nsplit, NETS), dim3(256), 0, s, S, sp, m, obs, act);
+  if (nsplit > 1) hipLaunchKernelGGL(ddpg_combine_kernel, dim3((len + 255) / 256), dim3(256), 0, s, l->partial, nsplit, len, grad);
+}
+
+int create(const char* who, bool twin, int32_t device, int32_t max_batch, brs_ddpg_learner** out) {
+  const std::string w(who);
+  if (!out) return fail<brs_ddpg_learner>(nullptr, BRS_ERR_ARG, w + ": null argument");
+  *out = nullptr;
+  if (max_batch < 1 || max_batch > (1 << 22)) return fail<brs_ddpg_learner>(nullptr, BRS_ERR_ARG, w + ": max_batch must be in [1, 2^22]");
+  std::string why;
+  if (const int rc = brs::host::check_device(device, who, &why)) return fail<brs_ddpg_learner>(nullptr, rc, why);
+  DeviceGuard g(device);
+  if (!g.ok) return fail<brs_ddpg_learner>(nullptr, BRS_ERR_HIP, w + ": hipSetDevice failed");
+  brs_ddpg_learner* l = new brs_ddpg_learner();
+  l->device = device;
+  l->max_batch = max_batch;
+  l->ld = pad128(max_batch);
+  l->twin = twin;
+  const size_t scratch = (size_t)(twin ? TWIN_SCRATCH_ROWS : SCRATCH_ROWS) * l->ld,
+               bytes = (scratch + (size_t)MAX_SPLIT * (twin ? TWIN_PARTIAL_LEN : PARTIAL_LEN)) * sizeof(float);
+  if (hipMalloc((void**)&l->block, bytes) != hipSuccess || hipMemset(l->block, 0, bytes) != hipSuccess) {
+    if (l->block) (void)hipFree(l->block);
+    delete l;
+    return fail<brs_ddpg_learner>(nullptr, BRS_ERR_HIP, w + ": device allocation failed");
+  }
+  l->partial = l->block + scratch;
+  l->bytes = bytes;
+  *out = l;
+  return BRS_OK;
 }
 
 }  // namespace
@@ -355,28 +412,11 @@ template <class N> void launch_weight_kernels(brs_ddpg_learner* l, int m, const 
 extern "C" {
 
 int brs_ddpg_learner_create(int32_t device, int32_t max_batch, brs_ddpg_learner** out) {
-  if (!out) return fail<brs_ddpg_learner>(nullptr, BRS_ERR_ARG, "brs_ddpg_learner_create: null argument");
-  *out = nullptr;
-  if (max_batch < 1 || max_batch > (1 << 22))
-    return fail<brs_ddpg_learner>(nullptr, BRS_ERR_ARG, "brs_ddpg_learner_create: max_batch must be in [1, 2^22]");
-  std::string why;
-  if (const int rc = brs::host::check_device(device, "brs_ddpg_learner_create", &why)) return fail<brs_ddpg_learner>(nullptr, rc, why);
-  DeviceGuard g(device);
-  if (!g.ok) return fail<brs_ddpg_learner>(nullptr, BRS_ERR_HIP, "brs_ddpg_learner_create: hipSetDevice failed");
-  brs_ddpg_learner* l = new brs_ddpg_learner();
-  l->device = device;
-  l->max_batch = max_batch;
-  l->ld = pad128(max_batch);
-  const size_t scratch = (size_t)S_ROWS * l->ld, bytes = (scratch + (size_t)MAX_SPLIT * row_len<Actor>()) * sizeof(float);
-  if (hipMalloc((void**)&l->block, bytes) != hipSuccess || hipMemset(l->block, 0, bytes) != hipSuccess) {
-    if (l->block) (void)hipFree(l->block);
-    delete l;
-    return fail<brs_ddpg_learner>(nullptr, BRS_ERR_HIP, "brs_ddpg_learner_create: device allocation failed");
-  }
-  l->partial = l->block + scratch;
-  l->bytes = bytes;
-  *out = l;
-  return BRS_OK;
+  return create("brs_ddpg_learner_create", false, device, max_batch, out);
+}
+
+int brs_ddpg_learner_create_twin(int32_t device, int32_t max_batch, brs_ddpg_learner** out) {
+  return create("brs_ddpg_learner_create_twin", true, device, max_batch, out);
 }
 
 int brs_ddpg_learner_destroy(brs_ddpg_learner* l) {
@@ -409,9 +449,28 @@ int brs_ddpg_learner_critic_grad(brs_ddpg_learner* l, const float* critic_dev, i
   DeviceGuard g(l->device);
   if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_ddpg_learner_critic_grad: hipSetDevice failed");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ddpg_critic_backward_kernel, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, critic_dev, m, obs_dev, act_dev, y_dev,
+  hipLaunchKernelGGL(ddpg_critic_backward_kernel<Wide>, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, critic_dev, m, obs_dev, act_dev, y_dev,
                      Scratch{l->block, l->ld});
   launch_weight_kernels<Critic>(l, m, obs_dev, act_dev, grad_dev, s);
+  BRS_HIP_TRY(l, hipGetLastError());
+  return BRS_OK;
+}
+
+int brs_ddpg_learner_twin_critic_grad(brs_ddpg_learner* l, const float* critics_dev, int32_t m, const float* obs_dev, const float* act_dev,
+                                      const float* y_dev, float* grad_dev, void* stream) {
+  if (!critics_dev || !obs_dev || !act_dev || !y_dev || !grad_dev)
+    return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: null argument");
+  if (m < 1) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: m must be at least 1");
+  if (!l) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: null handle");
+  if (!l->twin)
+    return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: the handle was not created with brs_ddpg_learner_create_twin");
+  if (m > l->max_batch) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: m exceeds the handle's max_batch");
+  DeviceGuard g(l->device);
+  if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_ddpg_learner_twin_critic_grad: hipSetDevice failed");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ddpg_critic_backward_kernel<Narrow>, dim3(pad128(m) / WG_ROWS, 2), dim3(THREADS), 0, s, critics_dev, m, obs_dev, act_dev,
+                     y_dev, Scratch{l->block, l->ld});
+  launch_weight_kernels<Critic, Narrow, 2>(l, m, obs_dev, act_dev, grad_dev, s);
   BRS_HIP_TRY(l, hipGetLastError());
   return BRS_OK;
 }

@@ -1,5 +1,6 @@
 // brs_offpolicy.hip -- the DDPG data path of include/brs_policy.h: actor with exploration noise, critic, TD
-// target from the two target networks, replay buffer add and fused sample, as HIP kernels for gfx950.
+// target from the two target networks, replay buffer add and fused sample, as HIP kernels for gfx950; and TD3's target with
+// smoothing noise and two target critics.
 //
 // One forward routine (forward_tile, brs_ddpg_tile.hpp, shared with brs_ddpg_learner.hip) serves brs_ddpg_act, brs_ddpg_q and brs_ddpg_td_target.  It is brs_policy.hip's scheme for
 // wider layers: fp32 on the MATRIX cores (v_mfma_f32_32x32x2_f32: exact fp32 products, a k-ordered fma chain), the product
@@ -89,6 +90,32 @@ __global__ void __launch_bounds__(THREADS) ddpg_td_target_kernel(const float* __
   const float xb[(OBS + ACT) / 2] = {sb[0], sb[1], sb[2], a_mine};
   forward_tile<Critic>(critic_t, L, xb, v);
   if (i < m && finishes_row()) y[i] = td_combine(reward[i], done[i], gamma, v[0]);
+}
+
+// TD3's target: actor' -> smoothing noise, two clamps -> critic 0' -> critic 1' -> minimum -> combine in one launch;
+// the three forwards share the LDS image one after the other.  Both halves of a wave compute the row's Philox block: the action
+// is the B operand of both.
+__global__ void __launch_bounds__(THREADS) td3_td_target_kernel(const float* __restrict__ actor_t, const float* __restrict__ critics_t, const int m,
+                                                                const float* __restrict__ next_obs, const float* __restrict__ reward,
+                                                                const uint8_t* __restrict__ done, const float gamma, const float policy_noise,
+                                                                const float noise_clip, const uint64_t seed, const uint32_t draw,
+                                                                float* __restrict__ y, float* __restrict__ next_action, float* __restrict__ noise) {
+  __shared__ float L[LDS_FLOATS];
+  const int i = tile_row();
+  float sb[OBS / 2], mu[ACT], a[ACT], z[ACT], q1[1], q2[1];
+  load_obs_operands(next_obs, m, i, sb);
+  forward_tile<Actor>(actor_t, L, sb, mu);
+  td3_action_tail(seed, draw, (uint32_t)i, policy_noise, noise_clip, mu, a, z);
+  const float xb[(OBS + ACT) / 2] = {sb[0], sb[1], sb[2], wave_half() ? a[1] : a[0]};
+  forward_tile<Critic>(critics_t, L, xb, q1);
+  forward_tile<Critic>(critics_t + nparam<Critic>(), L, xb, q2);
+  if (i >= m || !finishes_row()) return;
+  y[i] = td3_combine(reward[i], done[i], gamma, q1[0], q2[0]);
+#pragma unroll
+  for (int k = 0; k < ACT; k++) {
+    if (next_action) next_action[(size_t)ACT * i + k] = a[k];
+    if (noise) noise[(size_t)ACT * i + k] = z[k];
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ replay buffer
@@ -233,6 +260,22 @@ int brs_ddpg_td_target(brs_ddpg* d, const float* actor_target_dev, const float* 
   if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_ddpg_td_target: hipSetDevice failed");
   hipLaunchKernelGGL(ddpg_td_target_kernel, dim3((m + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_target_dev,
                      critic_target_dev, m, next_obs_dev, reward_dev, done_dev, gamma, y_dev);
+  BRS_HIP_TRY(d, hipGetLastError());
+  return BRS_OK;
+}
+
+int brs_td3_td_target(brs_ddpg* d, const float* actor_target_dev, const float* critics_target_dev, int32_t m, const float* next_obs_dev,
+                      const float* reward_dev, const uint8_t* done_dev, float gamma, float policy_noise, float noise_clip, uint64_t seed,
+                      uint32_t draw, float* y_dev, float* next_action_dev, float* noise_dev, void* stream) {
+  if (const char* why = td3_target_argument_error(actor_target_dev, critics_target_dev, m, next_obs_dev, reward_dev, done_dev, policy_noise,
+                                                  noise_clip, y_dev))
+    return fail(d, BRS_ERR_ARG, std::string("brs_td3_td_target: ") + why);
+  if (!d) return fail(d, BRS_ERR_ARG, "brs_td3_td_target: null handle");
+  DeviceGuard g(d->device);
+  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_td3_td_target: hipSetDevice failed");
+  hipLaunchKernelGGL(td3_td_target_kernel, dim3((m + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_target_dev,
+                     critics_target_dev, m, next_obs_dev, reward_dev, done_dev, gamma, policy_noise, noise_clip, seed, draw, y_dev,
+                     next_action_dev, noise_dev);
   BRS_HIP_TRY(d, hipGetLastError());
   return BRS_OK;
 }

@@ -24,7 +24,7 @@ template <class N> struct Offsets {
   static constexpr int W1 = 0, B1 = W1 + N::H1 * N::IN, W2 = B1 + N::H1, B2 = W2 + N::H2 * N::H1, W3 = B2 + N::H2, B3 = W3 + N::OUT * N::H2;
 };
 
-constexpr uint32_t TAG_ACT = BRS_DDPG_TAG_ACT, TAG_SAMPLE = BRS_DDPG_TAG_SAMPLE;
+constexpr uint32_t TAG_ACT = BRS_DDPG_TAG_ACT, TAG_SAMPLE = BRS_DDPG_TAG_SAMPLE, TAG_TD3_NOISE = BRS_TD3_TAG_NOISE;
 
 // the Philox block of env gid at `step` (brs_ddpg_act) and of sample j of `draw` (brs_replay_sample)
 BRS_HD void act_block(uint64_t seed, int64_t gid, uint32_t step, uint32_t* o) {
@@ -33,6 +33,11 @@ BRS_HD void act_block(uint64_t seed, int64_t gid, uint32_t step, uint32_t* o) {
 }
 BRS_HD void sample_block(uint64_t seed, uint32_t draw, uint32_t j, uint32_t* o) {
   philox4x32_10(draw, TAG_SAMPLE, j, 0u, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), o);
+}
+
+// ... and of row j of `draw` of brs_td3_td_target's smoothing noise
+BRS_HD void td3_noise_block(uint64_t seed, uint32_t draw, uint32_t j, uint32_t* o) {
+  philox4x32_10(draw, TAG_TD3_NOISE, j, 0u, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), o);
 }
 
 // Box-Muller on two 24-bit uniforms in (0, 1): the arithmetic of brs_policy_act, on words 0 and 1
@@ -76,6 +81,37 @@ BRS_HD float td_combine(float reward, uint8_t done, float gamma, float q_next) {
   if (done) return reward;
   const float g = gamma * q_next;
   return reward + g;
+}
+
+// TD3's target policy smoothing: a' = clamp(mean + clamp(policy_noise z, -clip, clip), -1, 1); with
+// policy_noise == 0 the target actor's output comes back as it is (it lies in [-1, 1]; -0 + mean is mean)
+BRS_HD float smoothed_action(float mean, float policy_noise, float clip, float z) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  float p = policy_noise * z;
+  p = fminf(clip, fmaxf(-clip, p));
+  const float a = mean + p;
+  return fminf(1.0f, fmaxf(-1.0f, a));
+}
+// the per-row tail of brs_td3_td_target before the two critics: z[2] from the row's Philox block, next_action[2] from mean[2]
+BRS_HD void td3_action_tail(uint64_t seed, uint32_t draw, uint32_t row, float policy_noise, float clip, const float* mean, float* next_action,
+                            float* z) {
+  uint32_t o[4];
+  td3_noise_block(seed, draw, row, o);
+  normal_pair(o[0], o[1], z);
+  for (int k = 0; k < ACT; k++) next_action[k] = smoothed_action(mean[k], policy_noise, clip, z[k]);
+}
+// ... and after them: clipped double-Q, then td_combine
+BRS_HD float td3_combine(float reward, uint8_t done, float gamma, float q1, float q2) { return td_combine(reward, done, gamma, fminf(q1, q2)); }
+// the argument rules of brs_td3_td_target that need no device: 0 or the text after "brs_td3_td_target: "
+inline const char* td3_target_argument_error(const void* actor_t, const void* critics_t, int32_t m, const void* next_obs, const void* reward,
+                                             const void* done, float policy_noise, float noise_clip, const void* y) {
+  if (!actor_t || !critics_t || !next_obs || !reward || !done || !y) return "null argument";
+  if (m < 1) return "m must be at least 1";
+  if (!(policy_noise >= 0.0f) || isinf(policy_noise)) return "policy_noise must be finite and >= 0";
+  if (!(noise_clip >= 0.0f) || isinf(noise_clip)) return "noise_clip must be finite and >= 0";
+  return nullptr;
 }
 
 // replay buffer, one env of one added step: which observation is the transition's successor, and its done flag

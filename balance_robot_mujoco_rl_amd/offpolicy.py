@@ -74,6 +74,61 @@ def unflatten_ddpg_state_dict(flat, net="actor", naming="sb3"):
     return out
 
 
+# the two critics of TD3 inside one state_dict: SB3's ContinuousCritic (critic.qf0.0.weight, critic.qf1.0.weight) and
+# tools/train_td3_torch.py, which holds them as an nn.ModuleList of two nn.Sequential (critic.0.0.weight, critic.1.0.weight)
+TD3_CRITIC_NAMINGS = {"sb3": "{net}.qf{k}.{i}.", "tool": "{net}.{k}.{i}."}
+
+
+def _td3_layout(net, naming):
+    if net not in ("critic", "critic_target"):
+        raise ValueError(f"net must be 'critic' or 'critic_target', got {net!r}")
+    if naming not in TD3_CRITIC_NAMINGS:
+        raise ValueError(f"naming must be 'sb3' or 'tool', got {naming!r}")
+    return [(TD3_CRITIC_NAMINGS[naming].format(net=net, k=k, i=i) + kind, shape) for k in (0, 1) for i, pair in zip(_LAYER_INDEX, CRITIC_SHAPES)
+            for kind, shape in zip(("weight", "bias"), pair)]
+
+
+def _td3_naming_of(sd, net):
+    keys = [k.split(".") for k in sd if isinstance(k, str)]
+    if any(len(k) == 4 and k[0] == net and k[1] in ("qf0", "qf1") for k in keys):
+        return "sb3"
+    if any(len(k) == 4 and k[0] == net and k[1] in ("0", "1") and k[2].isdigit() for k in keys):
+        return "tool"
+    raise ValueError(f"neither SB3's naming ({net}.qf0.0.weight, {net}.qf1.0.weight) nor the TD3 tool's ({net}.0.0.weight, {net}.1.0.weight)")
+
+
+def flatten_td3_critics(sd, net="critic"):
+    """state_dict -> the flat float32 vector [2 NCRITIC] of TD3's two critics, critic 0 then critic 1, each in the critic's flat
+    order.  `net`: 'critic' or 'critic_target'.  Two namings are understood: SB3's TD3Policy (critic.qf0.{0,2,4}.{weight,bias} and
+    critic.qf1.*) and tools/train_td3_torch.py's, an nn.ModuleList of two nn.Sequential (critic.0.{0,2,4}.{weight,bias} and
+    critic.1.*)."""
+    parts = []
+    for name, shape in _td3_layout(net, _td3_naming_of(sd, net)):
+        if name not in sd:
+            raise ValueError(f"{name}: missing")
+        a = sd[name]
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        if tuple(a.shape) != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
+        parts.append(a.astype(np.float32).ravel())
+    flat = np.concatenate(parts)
+    assert flat.size == 2 * NCRITIC
+    return flat
+
+
+def unflatten_td3_critics(flat, net="critic", naming="sb3"):
+    """the flat vector [2 NCRITIC] of the two critics -> {name: tensor} in `naming` ('sb3' or 'tool', as flatten_td3_critics)"""
+    flat = np.ascontiguousarray(flat.detach().cpu().numpy() if hasattr(flat, "detach") else flat, dtype=np.float32)
+    if flat.shape != (2 * NCRITIC,):
+        raise ValueError(f"{net}: expected {2 * NCRITIC} parameters, got shape {flat.shape}")
+    out, at = {}, 0
+    for name, shape in _td3_layout(net, naming):
+        k = int(np.prod(shape))
+        out[name] = torch.from_numpy(flat[at:at + k].reshape(shape).copy())
+        at += k
+    return out
+
+
 def _device(device):
     return torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
 
@@ -150,6 +205,26 @@ class DeviceDDPGNets:
         _need(out, "y", f32, (m,), d)
         self._check(self.L.brs_ddpg_td_target(self.h, _p(actor_target_params), _p(critic_target_params), m, _p(next_obs), _p(reward), _p(done),
                                               float(gamma), _p(out), self._stream()), "brs_ddpg_td_target")
+        return out
+
+
+    def td3_target(self, actor_target, critics_target, next_obs, reward, done, gamma, policy_noise, noise_clip, draw, out=None, next_action=None,
+                   noise=None):
+        """TD3's target from the three target networks, one launch: y = reward + (1 - done) gamma min(Q1', Q2')(next_obs, a') with
+        a' = clamp(pi'(next_obs) + clamp(policy_noise z, -noise_clip, noise_clip), -1, 1); critics_target [2 NCRITIC]; `draw`: the
+        counter of this call's noise (with the object's seed); next_action / noise: optional [m,2] outputs (a' and z) -> y [m]"""
+        d, f32, m = self.device, torch.float32, next_obs.shape[0]
+        _need(actor_target, "actor_target", f32, (NACTOR,), d); _need(critics_target, "critics_target", f32, (2 * NCRITIC,), d)
+        _need(next_obs, "next_obs", f32, (m, 6), d); _need(reward, "reward", f32, (m,), d); _need(done, "done", torch.uint8, (m,), d)
+        if out is None:
+            out = torch.empty(m, dtype=f32, device=d)
+        _need(out, "y", f32, (m,), d)
+        for t, name in ((next_action, "next_action"), (noise, "noise")):
+            if t is not None:
+                _need(t, name, f32, (m, 2), d)
+        self._check(self.L.brs_td3_td_target(self.h, _p(actor_target), _p(critics_target), m, _p(next_obs), _p(reward), _p(done), float(gamma),
+                                             float(policy_noise), float(noise_clip), self.seed, int(draw) & 0xffffffff, _p(out), _p(next_action),
+                                             _p(noise), self._stream()), "brs_td3_td_target")
         return out
 
 
@@ -376,3 +451,113 @@ class DeviceDDPGLearner:
                 raise ValueError(f"{k}: expected shape {tuple(t.shape)}, got {tuple(src.shape)}")
             t.copy_(src.to(device=self.device, dtype=torch.float32))
         self.steps_critic, self.steps_actor = int(sd["steps_critic"]), int(sd["steps_actor"])
+
+
+class DeviceTD3Learner:
+    """SB3's TD3.train by the HIP kernels, on the reference's DDPG widths (pi=[300, 200], qf=[200, 150]): the gradient of
+    mse(Q1(s, a), y) + mse(Q2(s, a), y) w.r.t. both critics in one set of launches (brs_ddpg_learner_twin_critic_grad), one Adam
+    over the [2 NCRITIC] vector, and every `policy_delay`-th update the actor's gradient through the first, updated critic, its
+    Adam step and the Polyak update of all three targets.  The networks are the caller's flat float32 device tensors (actor
+    [NACTOR], critics [2 NCRITIC] and their targets), updated in place; this object owns the twin gradient buffer, the actor's, the
+    moment vectors, the step counters and n_updates."""
+
+    def __init__(self, device=0, max_batch=256, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, tau=0.005, policy_delay=2):
+        if not torch.cuda.is_available():
+            raise BrsError("no HIP device visible to PyTorch: the on-device TD3 learner has no CPU fallback")
+        if int(policy_delay) < 1:
+            raise ValueError(f"policy_delay must be at least 1, got {policy_delay}")
+        self.L = _lib.lib()
+        self.device = _device(device)
+        self.max_batch, self.tau, self.policy_delay = int(max_batch), float(tau), int(policy_delay)
+        self.cfg = _lib.BrsAdamConfig(float(lr), float(betas[0]), float(betas[1]), float(eps))
+        h = C.c_void_p()
+        rc = self.L.brs_ddpg_learner_create_twin(self.device.index, self.max_batch, C.byref(h))
+        if rc != 0:
+            raise BrsError(f"brs_ddpg_learner_create_twin failed ({rc}): {self.L.brs_ddpg_learner_last_error(None).decode()}")
+        self.h = h
+        z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.grad_critics, self.grad_actor = z(2 * NCRITIC + _lib.TD3_NSTAT), z(NACTOR + _lib.DDPG_NSTAT)
+        self.m_critics, self.v_critics, self.m_actor, self.v_actor = z(2 * NCRITIC), z(2 * NCRITIC), z(NACTOR), z(NACTOR)
+        self.steps_critics = self.steps_actor = self.n_updates = 0
+
+    close, __del__, _check, _stream, scratch = (DeviceDDPGLearner.close, DeviceDDPGLearner.__del__, DeviceDDPGLearner._check,
+                                                DeviceDDPGLearner._stream, DeviceDDPGLearner.scratch)
+
+    def twin_critic_grad(self, critics, obs, action, y, out=None):
+        """-> [2 NCRITIC + 4]: the gradient of mse(Q1(s, a), y) w.r.t. critic 0, of mse(Q2(s, a), y) w.r.t. critic 1, then the loss
+        and the mean Q of critic 0 and of critic 1"""
+        d, f32, m = self.device, torch.float32, obs.shape[0]
+        out = self.grad_critics if out is None else out
+        _need(critics, "critics", f32, (2 * NCRITIC,), d); _need(obs, "obs", f32, (m, 6), d); _need(action, "action", f32, (m, 2), d)
+        _need(y, "y", f32, (m,), d); _need(out, "grad", f32, (2 * NCRITIC + _lib.TD3_NSTAT,), d)
+        self._check(self.L.brs_ddpg_learner_twin_critic_grad(self.h, _p(critics), m, _p(obs), _p(action), _p(y), _p(out), self._stream()),
+                    "brs_ddpg_learner_twin_critic_grad")
+        return out
+
+    def actor_grad(self, actor, critics, obs, out=None):
+        """-> [NACTOR + 2]: the gradient of La = -mean Q1(s, pi(s)) through the FIRST critic of `critics` [2 NCRITIC], then La and
+        the mean of pi(s)^2"""
+        d, f32, m = self.device, torch.float32, obs.shape[0]
+        out = self.grad_actor if out is None else out
+        _need(actor, "actor", f32, (NACTOR,), d); _need(critics, "critics", f32, (2 * NCRITIC,), d); _need(obs, "obs", f32, (m, 6), d)
+        _need(out, "grad", f32, (NACTOR + _lib.DDPG_NSTAT,), d)
+        self._check(self.L.brs_ddpg_learner_actor_grad(self.h, _p(actor), _p(critics), m, _p(obs), _p(out), self._stream()),
+                    "brs_ddpg_learner_actor_grad")
+        return out
+
+    def _apply(self, n, nstat, params, grad, mom, vel, target, step, name):
+        d, f32 = self.device, torch.float32
+        _need(params, name, f32, (n,), d); _need(grad, "grad", f32, (n + nstat,), d)
+        _need(mom, "m_" + name, f32, (n,), d); _need(vel, "v_" + name, f32, (n,), d)
+        if target is not None:
+            _need(target, name + "_target", f32, (n,), d)
+        self._check(self.L.brs_ddpg_learner_apply(self.h, n, _p(params), _p(grad), _p(mom), _p(vel), _p(target), C.byref(self.cfg), step,
+                                                  self.tau, self._stream()), "brs_ddpg_learner_apply")
+
+    def apply_critics(self, critics, critics_target=None, grad=None):
+        """one Adam step over both critics from grad_critics (or `grad`); with critics_target, also its Polyak update (the delayed
+        steps: the critics do not change between their Adam step and the end of the update)"""
+        self._apply(2 * NCRITIC, _lib.TD3_NSTAT, critics, self.grad_critics if grad is None else grad, self.m_critics, self.v_critics,
+                    critics_target, self.steps_critics + 1, "critics")
+        self.steps_critics += 1
+
+    def apply_actor(self, actor, actor_target=None, grad=None):
+        self._apply(NACTOR, _lib.DDPG_NSTAT, actor, self.grad_actor if grad is None else grad, self.m_actor, self.v_actor, actor_target,
+                    self.steps_actor + 1, "actor")
+        self.steps_actor += 1
+
+    def step(self, flat, obs, action, y):
+        """one update of SB3's TD3.train on a dict of the four flat vectors actor, critics, actor_target, critics_target: the twin
+        critic gradient and one Adam step; if n_updates (counted from 1) is a multiple of policy_delay, the actor's gradient through
+        the updated first critic, its Adam step and the Polyak update of all targets; on the other updates no target moves.
+        -> whether the actor was updated"""
+        self.n_updates += 1
+        delayed = self.n_updates % self.policy_delay == 0
+        self.twin_critic_grad(flat["critics"], obs, action, y)
+        self.apply_critics(flat["critics"], flat["critics_target"] if delayed else None)
+        if delayed:
+            self.actor_grad(flat["actor"], flat["critics"], obs)
+            self.apply_actor(flat["actor"], flat["actor_target"])
+        return delayed
+
+    def stats(self):
+        """one device-to-host copy: critic_loss (the sum of the two), mean_q1, mean_q2 of the last update, actor_loss and
+        mean_action_sq of the last delayed one"""
+        c0, q0, c1, q1, la, sq = torch.cat([self.grad_critics[2 * NCRITIC:], self.grad_actor[NACTOR:]]).cpu().tolist()
+        return {"critic_loss": c0 + c1, "mean_q1": q0, "mean_q2": q1, "actor_loss": la, "mean_action_sq": sq}
+
+    _TENSORS = ("m_critics", "v_critics", "m_actor", "v_actor")
+    _COUNTERS = ("steps_critics", "steps_actor", "n_updates")
+
+    def state_dict(self):
+        return {**{k: getattr(self, k).clone() for k in self._TENSORS}, **{k: getattr(self, k) for k in self._COUNTERS}}
+
+    def load_state_dict(self, sd):
+        for k in self._TENSORS:
+            t = getattr(self, k)
+            src = torch.as_tensor(sd[k])
+            if tuple(src.shape) != tuple(t.shape):
+                raise ValueError(f"{k}: expected shape {tuple(t.shape)}, got {tuple(src.shape)}")
+            t.copy_(src.to(device=self.device, dtype=torch.float32))
+        for k in self._COUNTERS:
+            setattr(self, k, int(sd[k]))

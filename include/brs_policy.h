@@ -33,6 +33,12 @@
  *   brs_ddpg_learner_actor_grad   the gradient of -mean Q(s, pi(s)) w.r.t. the actor, through the critic to its action inputs
  *   brs_ddpg_learner_apply        torch.optim.Adam's step on one network and polyak_update of its target
  *
+ * and TD3's three changes to that recipe (the CLI's `-a TD3`, src/sb_rl.py:73-83, with the DDPG net_arch):
+ *
+ *   brs_td3_td_target                  TD3.train's target: clipped Gaussian noise on the target action, the minimum of two critics
+ *   brs_ddpg_learner_twin_critic_grad  the gradient of mse(Q1(s, a), y) + mse(Q2(s, a), y) w.r.t. both critics in one set of launches
+ *                                      (the delay is the caller's: it skips actor_grad and passes target_dev = NULL on the other steps)
+ *
  * These entry points do the same arithmetic on the GPU, reading the simulator's outputs in place (device pointers),
  * so that a rollout of 65,536 envs needs no per-env Python and no PCIe traffic.  All buffers are DEVICE pointers owned
  * by the caller; every call only enqueues work on `stream`.  Same library (libbrs_hip.so), same status codes as brs.h.
@@ -241,6 +247,17 @@ int brs_replay_sample(int32_t device, const brs_replay_storage* storage, int32_t
                       uint64_t seed, uint32_t draw, const brs_replay_storage* out, int32_t* idx_dev, void* stream);
 const char* brs_replay_last_error(void);
 
+/* ---- TD3's target: y[m] = reward + (1 - done) gamma min(Q1'(s', a'), Q2'(s', a')) with
+ * a' = clamp(pi'(s') + clamp(policy_noise z, -noise_clip, noise_clip), -1, 1), all from the three TARGET networks, one launch;
+ * critics_target_dev holds the two critics back to back.  A row with done != 0 gets y == reward exactly.  Row j takes
+ * Philox4x32-10(counter = (draw, BRS_TD3_TAG_NOISE, j, 0), key = seed); words 0 and 1 -> z[0], z[1] by brs_ddpg_act's Box-Muller.
+ * next_action_dev [m][2] (a') and noise_dev [m][2] (z, before the scale and the clip) may be NULL.  policy_noise and noise_clip
+ * are finite and >= 0; policy_noise == 0 with two equal critics is brs_ddpg_td_target byte for byte. */
+#define BRS_TD3_TAG_NOISE 0x5444334eu /* "TD3N": second Philox counter word of brs_td3_td_target */
+int brs_td3_td_target(brs_ddpg*, const float* actor_target_dev, const float* critics_target_dev, int32_t m, const float* next_obs_dev,
+                      const float* reward_dev, const uint8_t* done_dev, float gamma, float policy_noise, float noise_clip, uint64_t seed,
+                      uint32_t draw, float* y_dev, float* next_action_dev, float* noise_dev, void* stream);
+
 /* ---- DDPG learner: the gradient step between two TD targets.  SB3's order is critic_grad, apply (critic),
  * actor_grad WITH THE UPDATED CRITIC, apply (actor); the Polyak update of a network is fused into its own apply (the critic
  * target is read only by the next brs_ddpg_td_target).  grad and apply are separate calls so that a data-parallel caller can
@@ -272,6 +289,17 @@ int brs_ddpg_learner_actor_grad(brs_ddpg_learner*, const float* actor_dev, const
  * [0, 1). */
 int brs_ddpg_learner_apply(brs_ddpg_learner*, int32_t n_param, float* params_dev, const float* grad_dev, float* m_dev, float* v_dev,
                            float* target_dev, const brs_adam_config* cfg, int64_t step, float tau, void* stream);
+
+/* ---- TD3's twin critics.  A handle from brs_ddpg_learner_create_twin serves every call above unchanged and has
+ * the scratch and the partial rows for two critics at once; brs_ddpg_learner_create's handles stay as they are.
+ * grad_dev[2 * BRS_DDPG_NCRITIC + BRS_TD3_NSTAT]: critic 0's gradient of mse(Q1(s, a), y) in its flat order, then critic 1's of
+ * mse(Q2(s, a), y) -- the gradient of the summed loss w.r.t. one critic is that of its own term -- then Lc and mean Q of critic 0,
+ * Lc and mean Q of critic 1.  Block k and its two statistics are byte for byte what brs_ddpg_learner_critic_grad returns for
+ * critic k alone.  One brs_ddpg_learner_apply with n_param = 2 * BRS_DDPG_NCRITIC is the Adam (and Polyak) step of both. */
+#define BRS_TD3_NSTAT 4
+int brs_ddpg_learner_create_twin(int32_t device, int32_t max_batch, brs_ddpg_learner** out);
+int brs_ddpg_learner_twin_critic_grad(brs_ddpg_learner*, const float* critics_dev, int32_t m, const float* obs_dev, const float* act_dev,
+                                      const float* y_dev, float* grad_dev, void* stream);
 
 #ifdef __cplusplus
 }
