@@ -42,8 +42,6 @@ using namespace brs::ddpg_learner;
 using namespace brs::ddpg_tile;
 using brs::learner::AdamScalars;
 
-constexpr int MAX_SPLIT = 8, SPLIT_ROWS = 256;
-constexpr int pad128(int x) { return (x + 127) / 128 * 128; }
 // rows of a scratch image (each `ld` floats, ld = max_batch padded to the workgroup's 128 rows) sized for network N.  The single
 // calls use the actor's, the wider net, for both networks; the twin call keeps two images of the critic's back to back.
 template <class N> struct Layout {
@@ -52,10 +50,7 @@ template <class N> struct Layout {
 using Wide = Layout<Actor>;
 using Narrow = Layout<Critic>;
 static_assert(Tile<Critic>::H1P <= Tile<Actor>::H1P && Tile<Critic>::H2P <= Tile<Actor>::H2P, "the critic fits in the actor's scratch");
-constexpr int TWIN_LEN = 2 * nparam<Critic>() + BRS_TD3_NSTAT;  // the twin gradient buffer / a twin partial row
-static_assert(BRS_TD3_NSTAT == 2 * NSTAT, "two statistics per critic");
 constexpr int SCRATCH_ROWS = Wide::ROWS, TWIN_SCRATCH_ROWS = 2 * Narrow::ROWS > Wide::ROWS ? 2 * Narrow::ROWS : Wide::ROWS;
-constexpr int PARTIAL_LEN = row_len<Actor>(), TWIN_PARTIAL_LEN = TWIN_LEN > row_len<Actor>() ? TWIN_LEN : row_len<Actor>();
 
 struct Scratch {
   float* base;
@@ -366,11 +361,8 @@ namespace {
 
 // the scratch view, the split of m rows and the launches after a backward kernel
 template <class N, class Lay = Wide, int NETS = 1> void launch_weight_kernels(brs_ddpg_learner* l, int m, const float* obs, const float* act, float* grad, hipStream_t s) {
-  const int mp = pad128(m);
-  int nsplit = mp / SPLIT_ROWS;
-  nsplit = nsplit < 1 ? 1 : (nsplit > MAX_SPLIT ? MAX_SPLIT : nsplit);
-  const int span = pad128((mp + nsplit - 1) / nsplit);
-  nsplit = (mp + span - 1) / span;
+  const SampleSplit ss = sample_split(m);  // brs_ddpg_learner.hpp
+  const int mp = ss.mp, span = ss.span, nsplit = ss.nsplit;
   const Scratch S{l->block, l->ld};
   // NETS networks side by side in a row of `len` floats: their parameter blocks, then their statistics
   const int len = NETS * nparam<N>() + NETS * NSTAT;
@@ -395,7 +387,7 @@ int create(const char* who, bool twin, int32_t device, int32_t max_batch, brs_dd
   l->ld = pad128(max_batch);
   l->twin = twin;
   const size_t scratch = (size_t)(twin ? TWIN_SCRATCH_ROWS : SCRATCH_ROWS) * l->ld,
-               bytes = (scratch + (size_t)MAX_SPLIT * (twin ? TWIN_PARTIAL_LEN : PARTIAL_LEN)) * sizeof(float);
+               bytes = (scratch + partial_floats(twin)) * sizeof(float);
   if (hipMalloc((void**)&l->block, bytes) != hipSuccess || hipMemset(l->block, 0, bytes) != hipSuccess) {
     if (l->block) (void)hipFree(l->block);
     delete l;

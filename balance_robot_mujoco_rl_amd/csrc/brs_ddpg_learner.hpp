@@ -21,6 +21,29 @@ constexpr int Z3_ROWS = 4;  // per-sample rows next to the hidden ones: dz3[OUT]
 static_assert(Actor::OUT + NSTAT <= Z3_ROWS && Critic::OUT + NSTAT <= Z3_ROWS, "rows");
 template <class N> constexpr int row_len() { return nparam<N>() + NSTAT; }  // a gradient buffer / a partial row
 
+// ---- how the weight-gradient kernels of brs_ddpg_learner.hip split the sample axis: at 512 padded rows and more, over up to
+// MAX_SPLIT workgroup rows of `span` samples each, every one writing a partial row of the handle.  Host code, here so that the
+// CPU tests reach it (tests/ddpglearnerhost: dh_split_sweep).
+constexpr int MAX_SPLIT = 8, SPLIT_ROWS = 256;
+constexpr int pad128(int x) { return (x + 127) / 128 * 128; }
+constexpr int TWIN_LEN = 2 * nparam<Critic>() + BRS_TD3_NSTAT;  // the twin gradient buffer / a twin partial row
+static_assert(BRS_TD3_NSTAT == 2 * NSTAT, "two statistics per critic");
+// a partial row holds the longest row a call writes: the actor's in the single calls, two critics side by side in the twin call
+constexpr int PARTIAL_LEN = row_len<Actor>(), TWIN_PARTIAL_LEN = TWIN_LEN > row_len<Actor>() ? TWIN_LEN : row_len<Actor>();
+static_assert(row_len<Critic>() <= PARTIAL_LEN, "the critic's row fits a partial row");
+// floats the handle keeps for partial rows, behind its scratch rows
+constexpr size_t partial_floats(bool twin) { return (size_t)MAX_SPLIT * (twin ? TWIN_PARTIAL_LEN : PARTIAL_LEN); }
+
+struct SampleSplit { int mp, span, nsplit; };  // samples padded to 128; samples per split (a multiple of 128); splits launched
+inline SampleSplit sample_split(int m) {
+  const int mp = pad128(m);
+  int nsplit = mp / SPLIT_ROWS;
+  nsplit = nsplit < 1 ? 1 : (nsplit > MAX_SPLIT ? MAX_SPLIT : nsplit);
+  const int span = pad128((mp + nsplit - 1) / nsplit);
+  nsplit = (mp + span - 1) / span;
+  return SampleSplit{mp, span, nsplit};
+}
+
 // ReLU's backward gate, as torch's: the pre-activation is positive (equivalently: the ReLU's output is)
 BRS_HD bool relu_gate(float pre) { return pre > 0.0f; }
 

@@ -24,6 +24,28 @@ MARGIN = {"init": 1e-5, "x3": 1e-4}
 WEIGHT_SETS = ("init", "x3")
 CPU_ROWS = (1, 33, 257, 1000)
 GPU_ROWS = (1, 31, 32, 33, 127, 128, 129, 257, 1000)   # the wave edge, the workgroup edge, eight row-workgroups (and four splits)
+# Where the weight-gradient kernels split the sample axis (brs_ddpg_learner.hpp: sample_split; mp = m padded to 128,
+# nsplit = clamp(mp / 256, 1, 8), span = pad128(ceil(mp / nsplit)), nsplit recomputed as ceil(mp / span)):
+#
+#      m     mp   splits (rows each)   real rows in the last split   what it reaches
+#  <= 384  <= 384  1                    -                             no split (GPU_ROWS up to 257)
+#     385    512   256, 256             129                           first split size, two partial rows
+#     513    640   384, 256             129                           uneven: the last split is shorter than span
+#     769    896   384, 384, 128          1                           the last split is 127 padding rows and one real row
+#    1000   1024   4 x 256              232                           the one split case of GPU_ROWS
+#    1025   1152   3 x 384              257                           recomputed nsplit (3) below the requested 4
+#    2049   2176   5 x 384, 256         129                           clamp at 8 requested, 6 launched, uneven
+#    8192   8192   8 x 1024            1024                           MAX_SPLIT, the size DESIGN.md 7.6 / 7.7 quote timings for
+#    8193   8320   7 x 1152, 256        129                           MAX_SPLIT and uneven
+SPLIT_ROWS = (385, 513, 769, 1025, 2049, 8192, 8193)
+SPLIT_X3_ROWS = (513, 2049, 8193)                      # the x3 weight set at the uneven geometries, at three depths
+SPLIT_CASES = [(n, "init") for n in SPLIT_ROWS] + [(n, "x3") for n in SPLIT_X3_ROWS]
+SPLIT_SEQUENCE = (8193, 513, 33, 2049, 769)            # 8 partial rows, then 2, none, 6, 3: what one handle is taken through
+SPLIT_BIG = 8448                                       # max_batch of the large handle: ld != mp at every row of SPLIT_ROWS
+HOST_ROWS_MAX = 2049                                   # the host build's plain loops are compared up to here (see the GPU tests)
+SPLIT_TABLE = {384: (384, 384, 1), 385: (512, 256, 2), 513: (640, 384, 2), 769: (896, 384, 3), 1000: (1024, 256, 4),   # m: (mp, span, nsplit)
+               1025: (1152, 384, 3), 2049: (2176, 384, 6), 8192: (8192, 1024, 8), 8193: (8320, 1152, 8)}
+SPLIT_LAST_REAL = {385: 129, 513: 129, 769: 1, 1000: 232, 1025: 257, 2049: 129, 8192: 1024, 8193: 129}
 GRAD_GATE = 1e-5            # per parameter block, ||g - g64|| / ||g64||: the project's learner tolerance
 ADAM = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, tau=0.005)
 _LAYERS = np.cumsum([0, 300, 200, 200, 150, 200, 150])   # the six hidden layers inside RL.preactivations' rows
@@ -205,6 +227,8 @@ def build_host(directory):
     L.dh_critic_grad.restype, L.dh_critic_grad.argtypes = i, [vp, i, vp, vp, vp, vp]
     L.dh_actor_grad.restype, L.dh_actor_grad.argtypes = i, [vp, vp, i, vp, vp]
     L.dh_apply.restype, L.dh_apply.argtypes = i, [i, vp, vp, vp, vp, vp, C.POINTER(_lib.BrsAdamConfig), C.c_int64, C.c_float]
+    L.dh_sample_split.restype, L.dh_sample_split.argtypes = None, [i, C.POINTER(i * 3)]
+    L.dh_split_sweep.restype, L.dh_split_sweep.argtypes = C.c_longlong, [i, i, C.POINTER(i), C.POINTER(C.c_uint)]
     L.dh_adam_pair.restype, L.dh_adam_pair.argtypes = None, [i, vp, C.POINTER(_lib.BrsAdamConfig), C.c_int64] + [vp] * 6
     return L
 

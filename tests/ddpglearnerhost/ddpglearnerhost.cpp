@@ -13,6 +13,11 @@ int dh_apply(int n_param, float* params, const float* grad, float* m, float* v, 
   return ddpglearnerhost::apply(n_param, params, grad, m, v, target, cfg, step, tau);
 }
 
+void dh_sample_split(int m, int* out) { ddpglearnerhost::split_of(m, out); }
+long long dh_split_sweep(int m_lo, int m_hi, int* first_bad, unsigned* first_mask) {
+  return ddpglearnerhost::split_sweep(m_lo, m_hi, first_bad, first_mask);
+}
+
 // the two statements of Adam's element update side by side: brs_learner.hpp's adam_update (the PPO learner's) and apply_element
 // (this learner's, contraction off).  Under g++ neither fuses, so the test holds them to the same bytes: the copies cannot drift.
 void dh_adam_pair(int n, const float* grad, const brs_adam_config* cfg, int64_t step, float* p_a, float* m_a, float* v_a, float* p_b, float* m_b,

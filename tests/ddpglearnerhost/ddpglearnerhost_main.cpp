@@ -4,11 +4,15 @@
 //
 //   ddpglearnerhost_main CASE...   each CASE a file written by the test: int32 m, steps; float tau; double lr, beta1, beta2, eps;
 //                                  actor f32[NACTOR]; critic f32[NCRITIC]; then per step obs f32[m][6], act f32[m][2], y f32[m]
+//   ddpglearnerhost_main --split-sweep LO HI M...   sample_split checked over every m of [LO, HI] (one line: how many m break a
+//                                  rule, the first of them and its bits), then one line "m mp span nsplit" per M
 // For every case: the targets start as copies, the moments at zero; per step critic_grad, apply (critic), actor_grad with the
 // updated critic, apply (actor).  One line with FNV-1a digests of the four networks and of the two last gradient buffers.  Every
 // array has exactly its size, so an index past an end is seen.
 #include <inttypes.h>
 #include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
 
 #include <vector>
 
@@ -33,6 +37,18 @@ bool read(FILE* f, std::vector<float>& v, size_t n) {
 int main(int argc, char** argv) {
   using namespace ddpglearnerhost;
   constexpr size_t NA = BRS_DDPG_NACTOR, NC = BRS_DDPG_NCRITIC;
+  if (argc >= 4 && !strcmp(argv[1], "--split-sweep")) {
+    int first_bad;
+    unsigned first_mask;
+    const long long bad = split_sweep(atoi(argv[2]), atoi(argv[3]), &first_bad, &first_mask);
+    printf("sweep %d..%d bad=%lld first=%d mask=%u\n", atoi(argv[2]), atoi(argv[3]), bad, first_bad, first_mask);
+    for (int a = 4; a < argc; a++) {
+      int out[3];
+      split_of(atoi(argv[a]), out);
+      printf("%d %d %d %d\n", atoi(argv[a]), out[0], out[1], out[2]);
+    }
+    return bad ? 1 : 0;
+  }
   for (int a = 1; a < argc; a++) {
     FILE* f = fopen(argv[a], "rb");
     int32_t head[2];

@@ -14,7 +14,7 @@ import torch
 import ref_ddpg_learner as RL
 import ref_offpolicy as R
 from balance_robot_mujoco_rl_amd import _lib, offpolicy
-from ddpg_learner_cases import (ADAM, CPU_ROWS, HOST_DIR, STEP_ROWS, STEPS, WEIGHT_SETS, HostDDPG, adam_config, block_distances, build_host,
+from ddpg_learner_cases import (ADAM, CPU_ROWS, HOST_DIR, SPLIT_LAST_REAL, SPLIT_ROWS, SPLIT_TABLE, STEP_ROWS, STEPS, WEIGHT_SETS, HostDDPG, adam_config, block_distances, build_host,
                                 check_gradient, check_trajectory, host_actor_grad, host_critic_grad, learner_case, references, trajectory_case)
 from offpolicy_cases import GXX, ROOT, gate
 
@@ -170,6 +170,49 @@ def test_stand_alone_program_is_clean_under_asan_and_ubsan(host, tmp_path):
     assert out["plain"] == (f"m={m} steps={steps} actor={_fnv(h.flat['actor']):016x} critic={_fnv(h.flat['critic']):016x} "
                             f"actor_target={_fnv(h.flat['actor_target']):016x} critic_target={_fnv(h.flat['critic_target']):016x} "
                             f"ga={_fnv(ga):016x} gc={_fnv(gc):016x}\n")
+
+
+# --------------------------------------------------------------------------------------- 3b. the split of the sample axis
+MAX_BATCH = 1 << 22   # the ABI's range of max_batch (brs_ddpg_learner_create)
+SPLIT_RULES = ("span is no multiple of 128", "nsplit is outside [1, 8]", "nsplit * span < mp", "(nsplit - 1) * span >= m: a split without a real row",
+               "nsplit == 1 is not the same as mp < 512", "the partial rows do not fit the allocation", "mp is not m padded to 128")
+
+
+def _split(host, m):
+    out = (C.c_int * 3)()
+    host.dh_sample_split(m, C.byref(out))
+    return tuple(out)
+
+
+def test_sample_split_over_every_batch_size_of_the_abi(host):
+    """brs_ddpg_learner.hpp's sample_split, the function launch_weight_kernels calls, for every m in [1, 2^22], the loop run inside
+    the host library: span a multiple of 128, 1 <= nsplit <= 8, the splits cover mp, every launched split holds a real row,
+    one split exactly below 512 padded rows, and nsplit partial rows fit what the handle allocates (single and twin).  Then the
+    nine geometries of ddpg_learner_cases' table as known answers."""
+    first, mask = C.c_int(), C.c_uint()
+    bad = host.dh_split_sweep(1, MAX_BATCH, C.byref(first), C.byref(mask))
+    assert bad == 0, (bad, first.value, [r for k, r in enumerate(SPLIT_RULES) if mask.value >> k & 1], _split(host, first.value))
+    for m, want in SPLIT_TABLE.items():
+        assert _split(host, m) == want, (m, _split(host, m), want)
+    for m in (1, 128, 383, 384):
+        assert _split(host, m)[2] == 1
+    assert set(SPLIT_ROWS) | {384, 1000} == set(SPLIT_TABLE)
+    for m, real in SPLIT_LAST_REAL.items():
+        mp, span, nsplit = _split(host, m)
+        assert m - (nsplit - 1) * span == real and min(span, mp - (nsplit - 1) * span) >= real
+
+
+def test_split_sweep_in_the_stand_alone_program_under_asan_and_ubsan(tmp_path):
+    """the same sweep in ddpglearnerhost_main.cpp built with -fsanitize=address,undefined: no overflow in the split's integer
+    arithmetic anywhere in the ABI's range, and the table's rows as the program prints them"""
+    exe = str(tmp_path / "ddpglearnerhost_san")
+    subprocess.check_call(GXX + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
+                                 os.path.join(HOST_DIR, "ddpglearnerhost_main.cpp")])
+    r = subprocess.run([exe, "--split-sweep", "1", str(MAX_BATCH)] + [str(m) for m in SPLIT_TABLE], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-2000:])
+    lines = r.stdout.splitlines()
+    assert lines[0] == f"sweep 1..{MAX_BATCH} bad=0 first=0 mask=0"
+    assert lines[1:] == [f"{m} {mp} {span} {nsplit}" for m, (mp, span, nsplit) in SPLIT_TABLE.items()]
 
 
 # --------------------------------------------------------------------------------------- 4. C ABI without a device

@@ -11,8 +11,9 @@ import pytest
 
 import ref_ddpg_learner as RL
 import ref_offpolicy as R
-from ddpg_learner_cases import (ADAM, GAMMA, GPU_ROWS, GRAD_GATE, STEP_ROWS, STEPS, WEIGHT_SETS, HostDDPG, block_distances, build_host,
-                                check_gradient, check_trajectory, host_actor_grad, host_critic_grad, learner_case, references, trajectory_case)
+from ddpg_learner_cases import (ADAM, GAMMA, GPU_ROWS, GRAD_GATE, HOST_ROWS_MAX, SPLIT_BIG, SPLIT_CASES, SPLIT_SEQUENCE, STEP_ROWS, STEPS, WEIGHT_SETS,
+                                HostDDPG, block_distances, build_host, check_gradient, check_trajectory, host_actor_grad, host_critic_grad, learner_case,
+                                references, trajectory_case)
 from offpolicy_cases import ROOT, gate
 from test_offpolicy_gpu import Guarded, _cuda
 
@@ -33,6 +34,14 @@ def _learner(max_batch):
 @pytest.fixture(scope="module")
 def big():
     lrn = _learner(1024)
+    yield lrn
+    lrn.close()
+
+
+@pytest.fixture(scope="module")
+def huge():
+    """max_batch = 8,448: its rows are longer than the padded batch (ld != mp) at every row of ddpg_learner_cases.SPLIT_ROWS"""
+    lrn = _learner(SPLIT_BIG)
     yield lrn
     lrn.close()
 
@@ -68,26 +77,41 @@ def _grads(lrn, c, dev):
 
 
 # --------------------------------------------------------------------------------------- 1. the two gradients
-@pytest.mark.parametrize("kind", WEIGHT_SETS)
-@pytest.mark.parametrize("n", GPU_ROWS)
-def test_gradients_against_fp64_and_the_host_build(host, big, n, kind):
+def _check_gradients(host, big, n, kind, with_host=True):
     c = learner_case(n, kind)
     c64, a64, c32, a32 = references(n, kind)
     dev = {k: _cuda(c[k]) for k in ("obs", "act", "y", "actor", "critic")}
     own = _learner(n)                       # max_batch == m, fresh
     gc, ga = _grads(own, c, dev)
     own.close()
-    _poison(big)                            # max_batch = 1,024, every word of its allocation NaN
+    _poison(big)                            # a larger max_batch, every word of its allocation NaN
     gc_big, ga_big = _grads(big, c, dev)
     assert np.isfinite(gc).all() and np.isfinite(ga).all()
     assert gc.tobytes() == gc_big.tobytes() and ga.tobytes() == ga_big.tobytes()   # nothing stale read, the handle's size does not matter
     check_gradient(f"n={n} {kind} critic", gc, c64, c32, R.CRITIC_SIZES, gate)
     check_gradient(f"n={n} {kind} actor", ga, a64, a32, R.ACTOR_SIZES, gate)
+    if not with_host:
+        return
     hc, ha = host_critic_grad(host, c["critic"], c["obs"], c["act"], c["y"]), host_actor_grad(host, c["actor"], c["critic"], c["obs"])
     dc, da = block_distances(gc[:NC], hc[:NC], R.CRITIC_SIZES), block_distances(ga[:NA], ha[:NA], R.ACTOR_SIZES)
     print(f"n={n} {kind}: largest block distance from the host build {max(dc.values()):.3g} (critic), {max(da.values()):.3g} (actor)")
     assert max(dc.values()) <= GRAD_GATE and max(da.values()) <= GRAD_GATE
     gate(gc[NC:], hc[NC:], "critic statistics against the host build"); gate(ga[NA:], ha[NA:], "actor statistics against the host build")
+
+
+@pytest.mark.parametrize("kind", WEIGHT_SETS)
+@pytest.mark.parametrize("n", GPU_ROWS)
+def test_gradients_against_fp64_and_the_host_build(host, big, n, kind):
+    _check_gradients(host, big, n, kind)    # big: max_batch = 1,024
+
+
+@pytest.mark.parametrize("n,kind", SPLIT_CASES)
+def test_gradients_at_every_split_geometry(host, huge, n, kind):
+    """the assertions of test_gradients_against_fp64_and_the_host_build at the rows of ddpg_learner_cases.SPLIT_ROWS: two to eight
+    partial rows, even and uneven splits, a last split with one real row, on a handle of max_batch = 8,448 (ld != mp everywhere).
+    The host build's plain loops take 2 s (critic) and 5 s (actor) per gradient at 8,192 rows on a CPU, so the comparison with the
+    host build is made up to 2,049 rows; the fp64 gate and every other assertion hold at all rows."""
+    _check_gradients(host, huge, n, kind, with_host=n <= HOST_ROWS_MAX)
 
 
 def test_identical_bytes_and_no_leftover_scratch(big):
@@ -102,6 +126,24 @@ def test_identical_bytes_and_no_leftover_scratch(big):
     fresh = _grads(fresh_handle, c33, d33)
     fresh_handle.close()
     assert after[0].tobytes() == fresh[0].tobytes() and after[1].tobytes() == fresh[1].tobytes()
+
+
+def test_no_leftover_between_split_geometries_on_one_handle(huge):
+    """8,193 -> 513 -> 33 -> 2,049 -> 769 rows on the NaN-filled large handle (8 partial rows, then 2, none, 6 and 3): every result
+    is what a fresh handle of exactly that size returns, byte for byte, and the sequence a second time returns the same bytes"""
+    cases = {n: learner_case(n, "init") for n in SPLIT_SEQUENCE}
+    devs = {n: {k: _cuda(c[k]) for k in ("obs", "act", "y", "actor", "critic")} for n, c in cases.items()}
+    fresh = {}
+    for n in SPLIT_SEQUENCE:
+        own = _learner(n)
+        fresh[n] = _grads(own, cases[n], devs[n])
+        own.close()
+        assert np.isfinite(fresh[n][0]).all() and np.isfinite(fresh[n][1]).all()
+    _poison(huge)
+    for run in range(2):
+        for n in SPLIT_SEQUENCE:
+            gc, ga = _grads(huge, cases[n], devs[n])
+            assert gc.tobytes() == fresh[n][0].tobytes() and ga.tobytes() == fresh[n][1].tobytes(), (run, n)
 
 
 def test_calls_are_refused_past_max_batch():

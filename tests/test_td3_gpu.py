@@ -11,7 +11,8 @@ import pytest
 
 import ref_offpolicy as R
 import td3_cases as TC
-from ddpg_learner_cases import ADAM, GPU_ROWS, GRAD_GATE, WEIGHT_SETS, block_distances, check_gradient
+from ddpg_learner_cases import (ADAM, GPU_ROWS, GRAD_GATE, HOST_ROWS_MAX, SPLIT_BIG, SPLIT_CASES, SPLIT_SEQUENCE, WEIGHT_SETS, block_distances,
+                                check_gradient)
 from offpolicy_cases import GAMMA, ROOT, SEED, gate
 from test_ddpg_learner_gpu import _poison
 from test_offpolicy_gpu import Guarded, _cuda
@@ -46,6 +47,14 @@ def _single(max_batch):
 @pytest.fixture(scope="module")
 def big():
     lrn = _twin(1024)
+    yield lrn
+    lrn.close()
+
+
+@pytest.fixture(scope="module")
+def huge():
+    """a twin handle of max_batch = 8,448: ld != mp at every row of ddpg_learner_cases.SPLIT_ROWS"""
+    lrn = _twin(SPLIT_BIG)
     yield lrn
     lrn.close()
 
@@ -112,30 +121,46 @@ def _dev(c):
     return {k: _cuda(c[k]) for k in ("obs", "act", "y", "actor", "critics")}
 
 
-@pytest.mark.parametrize("kind", WEIGHT_SETS)
-@pytest.mark.parametrize("n", GPU_ROWS)
-def test_twin_gradient_against_fp64_the_host_build_and_the_single_call(host, big, n, kind):
+def _check_twin_gradient(host, big, n, kind, with_host=True):
     c = TC.twin_case(n, kind)
     g64, g32 = TC.twin_references(n, kind)
     dev = _dev(c)
     own = _twin(n)                          # max_batch == m, fresh
     g = _twin_grad(own, dev)
     own.close()
-    _poison(big)                            # max_batch = 1,024, every word of its allocation NaN
+    _poison(big)                            # a larger max_batch, every word of its allocation NaN
     g_big = _twin_grad(big, dev)
     assert np.isfinite(g).all() and g.tobytes() == g_big.tobytes()   # nothing stale read, the handle's size does not matter
-    hg = TC.host_twin_critic_grad(host, c["critics"], c["obs"], c["act"], c["y"])
+    hg = TC.host_twin_critic_grad(host, c["critics"], c["obs"], c["act"], c["y"]) if with_host else g
     single = _single(n)
     for k, (mine, r64, r32, h) in enumerate(zip(TC.split_twin(g), TC.split_twin(g64), TC.split_twin(g32), TC.split_twin(hg))):
         alone = Guarded((NC + 2,))
         single.critic_grad(_cuda(np.ascontiguousarray(c["critics"][k * NC:(k + 1) * NC])), dev["obs"], dev["act"], dev["y"], out=alone.t)
         assert mine.tobytes() == alone.np().tobytes(), f"block {k} is not the single-critic call's result"
         check_gradient(f"n={n} {kind} critic {k}", mine, r64, r32, R.CRITIC_SIZES, gate)
+        if not with_host:
+            continue
         d = block_distances(mine[:NC], h[:NC], R.CRITIC_SIZES)
         print(f"n={n} {kind} critic {k}: largest block distance from the host build {max(d.values()):.3g}")
         assert max(d.values()) <= GRAD_GATE
         gate(mine[NC:], h[NC:], f"critic {k} statistics against the host build")
     single.close()
+
+
+@pytest.mark.parametrize("kind", WEIGHT_SETS)
+@pytest.mark.parametrize("n", GPU_ROWS)
+def test_twin_gradient_against_fp64_the_host_build_and_the_single_call(host, big, n, kind):
+    _check_twin_gradient(host, big, n, kind)   # big: max_batch = 1,024
+
+
+@pytest.mark.parametrize("n,kind", SPLIT_CASES)
+def test_twin_gradient_at_every_split_geometry(host, huge, n, kind):
+    """the assertions of test_twin_gradient_against_fp64_the_host_build_and_the_single_call at the rows of
+    ddpg_learner_cases.SPLIT_ROWS: two to eight partial rows of the twin length, even and uneven splits, a last split with one real row,
+    on a twin handle of max_batch = 8,448 (ld != mp everywhere).  One host gradient of one critic takes 2 s at 8,192 rows on a CPU
+    (the actor's, in the DDPG file, 5 s), so the comparison with the host build is made up to 2,049 rows in both files; the fp64 gate,
+    the identity with the single-critic call and every other assertion hold at all rows."""
+    _check_twin_gradient(host, huge, n, kind, with_host=n <= HOST_ROWS_MAX)
 
 
 def test_no_leftover_scratch_between_sizes(big):
@@ -149,6 +174,22 @@ def test_no_leftover_scratch_between_sizes(big):
     fresh = _twin_grad(fresh_handle, d33)
     fresh_handle.close()
     assert after.tobytes() == fresh.tobytes()
+
+
+def test_no_leftover_between_split_geometries_on_one_twin_handle(huge):
+    """8,193 -> 513 -> 33 -> 2,049 -> 769 rows on the NaN-filled large twin handle (8 partial rows, then 2, none, 6 and 3): every
+    result is what a fresh twin handle of exactly that size returns, byte for byte, and the sequence a second time returns the same"""
+    devs = {n: _dev(TC.twin_case(n, "init")) for n in SPLIT_SEQUENCE}
+    fresh = {}
+    for n in SPLIT_SEQUENCE:
+        own = _twin(n)
+        fresh[n] = _twin_grad(own, devs[n])
+        own.close()
+        assert np.isfinite(fresh[n]).all()
+    _poison(huge)
+    for run in range(2):
+        for n in SPLIT_SEQUENCE:
+            assert _twin_grad(huge, devs[n]).tobytes() == fresh[n].tobytes(), (run, n)
 
 
 # --------------------------------------------------------------------------------------- 3. handles
