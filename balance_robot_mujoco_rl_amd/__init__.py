@@ -24,6 +24,10 @@ include/brs.h (libbrs_hip.so).  This package is the host-side mirror of the refe
                                            TD3's three changes to that recipe -- smoothed twin-critic target, twin critic gradient,
                                            delayed actor and target updates -- (include/brs_policy.h: brs_td3_td_target,
                                            brs_ddpg_learner_twin_critic_grad): sb_rl.py's `-a TD3` with the DDPG net_arch
+    offpolicy.DeviceSACNets / DeviceSACLearner
+                                           SAC on the same widths -- squashed-Gaussian actor, entropy target, the actor's chain through
+                                           both critics, the learned temperature -- (include/brs_policy.h: brs_sac_*,
+                                           brs_ddpg_learner_create_sac): sb_rl.py's `-a SAC` with the DDPG net_arch
     quant.quantize_policy / QuantPolicy    int8 post-training quantisation of the actor and the int8 network as a HIP kernel
                                            (include/brs_qpolicy.h): quantize_tflite.py and sb_rl.py:285-364 on the GPU
 
@@ -31,14 +35,15 @@ There is no CPU fallback: creating a sim without a HIP device raises.
 """
 from .registry import ENV_SPECS, make_vec, spec  # noqa: F401
 from .learner import DevicePPOLearner, LearnerStats  # noqa: F401
-from .offpolicy import (DeviceDDPGLearner, DeviceDDPGNets, DeviceOffPolicyCollector, DeviceReplayBuffer, DeviceTD3Learner,  # noqa: F401
-                        flatten_ddpg_state_dict, flatten_td3_critics, unflatten_ddpg_state_dict, unflatten_td3_critics)
+from .offpolicy import (DeviceDDPGLearner, DeviceDDPGNets, DeviceOffPolicyCollector, DeviceReplayBuffer, DeviceSACLearner,  # noqa: F401
+                        DeviceSACNets, DeviceTD3Learner, flatten_ddpg_state_dict, flatten_sac_actor, flatten_td3_critics,
+                        unflatten_ddpg_state_dict, unflatten_sac_actor, unflatten_td3_critics)
 from .monitor import EpisodeMonitor, EpisodeStats, episode_count_targets, evaluate_policy  # noqa: F401
 from .quant import REFERENCE_CALIBRATION, QuantModel, QuantPolicy, quantize_policy  # noqa: F401
 from .sim import BatchedSim, BrsError  # noqa: F401
 from .vec_env import BalanceVecEnv  # noqa: F401
 
-__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "DeviceDDPGLearner", "DeviceDDPGNets", "DeviceOffPolicyCollector", "DevicePPOLearner", "DeviceReplayBuffer", "DeviceTD3Learner", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "LearnerStats",
+__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "DeviceDDPGLearner", "DeviceDDPGNets", "DeviceOffPolicyCollector", "DevicePPOLearner", "DeviceReplayBuffer", "DeviceSACLearner", "DeviceSACNets", "DeviceTD3Learner", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "LearnerStats",
            "QuantModel", "QuantPolicy",
-           "REFERENCE_CALIBRATION", "episode_count_targets", "evaluate_policy", "flatten_ddpg_state_dict", "flatten_td3_critics", "make_vec", "quantize_policy", "spec",
-           "unflatten_ddpg_state_dict", "unflatten_td3_critics"]
+           "REFERENCE_CALIBRATION", "episode_count_targets", "evaluate_policy", "flatten_ddpg_state_dict", "flatten_sac_actor", "flatten_td3_critics", "make_vec", "quantize_policy", "spec",
+           "unflatten_ddpg_state_dict", "unflatten_sac_actor", "unflatten_td3_critics"]

@@ -38,6 +38,8 @@ DDPG_NACTOR = 300 * 6 + 300 + 200 * 300 + 200 + 2 * 200 + 2     # BRS_DDPG_NACTO
 DDPG_NCRITIC = 200 * 8 + 200 + 150 * 200 + 150 + 1 * 150 + 1    # BRS_DDPG_NCRITIC
 DDPG_TAG_ACT, DDPG_TAG_SAMPLE = 0x44445047, 0x5245504c
 TD3_TAG_NOISE = 0x5444334e                                      # BRS_TD3_TAG_NOISE
+SAC_NACTOR = 300 * 6 + 300 + 200 * 300 + 200 + 4 * 200 + 4      # BRS_SAC_NACTOR; the actor vector holds one more, log_ent_coef
+SAC_TAG_ACT, SAC_TAG_TARGET, SAC_TAG_PI = 0x53414341, 0x53414354, 0x53414350
 
 
 class BrsConfig(C.Structure):
@@ -60,6 +62,7 @@ class BrsEpisodeStats(C.Structure):
 LEARNER_NSTAT = 5
 DDPG_NSTAT = 2                                                  # BRS_DDPG_NSTAT
 TD3_NSTAT = 4                                                   # BRS_TD3_NSTAT
+SAC_NSTAT = 4                                                   # BRS_SAC_NSTAT
 
 
 class BrsPpoConfig(C.Structure):
@@ -202,6 +205,11 @@ SIGNATURES = {
         "brs_ddpg_learner_apply": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(BrsAdamConfig), C.c_int64, _f32, _vp]),
         "brs_ddpg_learner_create_twin": (C.c_int, [_i32, _i32, C.POINTER(_vp)]),
         "brs_ddpg_learner_twin_critic_grad": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+        "brs_sac_act": (C.c_int, [_vp, _vp, _i32, _vp, C.c_uint64, C.c_int64, C.c_uint32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+        "brs_sac_td_target": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _f32, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+        "brs_ddpg_learner_create_sac": (C.c_int, [_i32, _i32, C.POINTER(_vp)]),
+        "brs_sac_twin_critic_grad": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+        "brs_sac_actor_grad": (C.c_int, [_vp, _vp, _vp, _i32, _vp, C.c_uint64, C.c_uint32, _i32, _f32, _vp, _vp]),
     },
     "brs_render.h": {
         "brs_render_default_camera": (None, [C.POINTER(BrsCamera)]),

@@ -23,6 +23,14 @@
 // kernel, blockIdx.z of the two sample-contracting ones.  Critic k reads critics + k NCRITIC, keeps its activations in the k-th
 // critic-sized scratch image and writes block k of the buffer (or of a partial row); one combine covers both.  What one critic
 // computes does not depend on the other's presence: block k is brs_ddpg_learner_critic_grad's result byte for byte.
+// SAC adds the actor's chain in two launches.  sac_actor_backward_kernel: the squashed-Gaussian actor's forward with
+// the activations stored, the sample and logp (brs_sac.hpp), BOTH critics' forwards (gates only) and backwards -- per row the smaller
+// Q takes dq = -1 / m, the other 0 -- into one d q / d action, the two dz3 formulas, dz3 and the row's shares into the per-sample
+// rows.  sac_actor_tail_kernel: the actor's backward with four outputs from those rows, the gates re-read as the signs of the stored
+// activations.  (In one kernel the compiler spills 352 registers per lane, 1,256 bytes of private memory; split, 22 and none.)  The
+// weight kernels are instantiated for the SAC actor with five per-sample sums behind b3 (the temperature's gradient and four
+// statistics).  SB3's 0.5
+// in front of the critic loss is a `loss_scale` at the head of ddpg_critic_backward_kernel; the DDPG / TD3 calls pass 1.
 // Padding: a row past m runs on zero inputs; its dq / dz3 is zero, so every product it enters is zero, and it is left out of the
 // statistics and of the 1 / m.  Padded units are zeros in the LDS image, their scratch rows are written (as zeros) by every call
 // and their gradient is never stored.  No floating-point atomic, no communication between workgroups.
@@ -35,22 +43,31 @@
 #include "brs_ddpg_learner.hpp"
 #include "brs_ddpg_tile.hpp"
 #include "brs_host.hpp"
+#include "brs_sac.hpp"
 
 namespace {
 
 using namespace brs::ddpg_learner;
 using namespace brs::ddpg_tile;
 using brs::learner::AdamScalars;
+using brs::sac::SacActor, brs::sac::SAC_TAIL, brs::sac::SAC_Z3_ROWS, brs::sac::SAC_ROW_LEN, brs::sac::SAC_NACTOR;
 
 // rows of a scratch image (each `ld` floats, ld = max_batch padded to the workgroup's 128 rows) sized for network N.  The single
 // calls use the actor's, the wider net, for both networks; the twin call keeps two images of the critic's back to back.
-template <class N> struct Layout {
-  static constexpr int H1 = 0, H2 = H1 + Tile<N>::H1P, DZ1 = H2 + Tile<N>::H2P, DZ2 = DZ1 + Tile<N>::H1P, Z3 = DZ2 + Tile<N>::H2P, ROWS = Z3 + Z3_ROWS;
+template <class N, int ZR = Z3_ROWS> struct Layout {
+  static constexpr int H1 = 0, H2 = H1 + Tile<N>::H1P, DZ1 = H2 + Tile<N>::H2P, DZ2 = DZ1 + Tile<N>::H1P, Z3 = DZ2 + Tile<N>::H2P, ROWS = Z3 + ZR;
 };
 using Wide = Layout<Actor>;
 using Narrow = Layout<Critic>;
 static_assert(Tile<Critic>::H1P <= Tile<Actor>::H1P && Tile<Critic>::H2P <= Tile<Actor>::H2P, "the critic fits in the actor's scratch");
 constexpr int SCRATCH_ROWS = Wide::ROWS, TWIN_SCRATCH_ROWS = 2 * Narrow::ROWS > Wide::ROWS ? 2 * Narrow::ROWS : Wide::ROWS;
+// a SAC handle: the SAC actor's image with its nine per-sample rows (Z3_ROWS = 4 holds dz3[OUT <= 2] and two statistics only), and
+// whatever the calls above need, so that all of them run on it; its partial rows hold the longest row of any call
+using SacLay = Layout<SacActor, SAC_Z3_ROWS>;
+static_assert(SacActor::OUT + SAC_TAIL <= SAC_Z3_ROWS && Tile<SacActor>::H1P == Tile<Actor>::H1P && Tile<SacActor>::H2P == Tile<Actor>::H2P, "rows");
+constexpr int SAC_SCRATCH_ROWS = SacLay::ROWS > TWIN_SCRATCH_ROWS ? SacLay::ROWS : TWIN_SCRATCH_ROWS;
+constexpr int SAC_PARTIAL_LEN = SAC_ROW_LEN > TWIN_PARTIAL_LEN ? SAC_ROW_LEN : TWIN_PARTIAL_LEN;
+constexpr int SAC_LDS_FLOATS = Tile<SacActor>::L_SIZE > LDS_FLOATS ? Tile<SacActor>::L_SIZE : LDS_FLOATS;
 
 struct Scratch {
   float* base;
@@ -165,7 +182,8 @@ __device__ __forceinline__ void backward_tile(const float* __restrict__ w, float
 // blockIdx.y: which of the critics laid back to back in `critics` (and which scratch image); one critic, one image in the single call
 template <class Lay> __global__ void __launch_bounds__(THREADS) ddpg_critic_backward_kernel(const float* __restrict__ critics, const int m,
                                                                                             const float* __restrict__ obs, const float* __restrict__ act,
-                                                                                            const float* __restrict__ y, const Scratch all) {
+                                                                                            const float* __restrict__ y, const Scratch all,
+                                                                                            const float loss_scale) {
   __shared__ float L[Tile<Critic>::L_SIZE];
   const float* __restrict__ critic = critics + (size_t)blockIdx.y * nparam<Critic>();
   const Scratch S = all.image(blockIdx.y, Lay::ROWS);
@@ -176,7 +194,7 @@ template <class Lay> __global__ void __launch_bounds__(THREADS) ddpg_critic_back
   Tape<Critic, true, Lay> tape(S, i);
   forward_tile<Critic>(critic, L, xb, v, tape);
   CriticHead hd = {0.0f, 0.0f, 0.0f};
-  if (i < m) hd = critic_head(v[0], y[i], 1.0f / (float)m);
+  if (i < m) hd = brs::sac::scale_head(critic_head(v[0], y[i], 1.0f / (float)m), loss_scale);  // 1 (exact) but for SAC's 0.5
   if (finishes_row()) {
     S.row(Lay::Z3)[i] = hd.dq;
     S.row(Lay::Z3 + 1)[i] = hd.loss;
@@ -213,6 +231,78 @@ __global__ void __launch_bounds__(THREADS) ddpg_actor_backward_kernel(const floa
     S.row(Wide::Z3 + 3)[i] = i < m ? actor_sat_share(a, inv_m) : 0.0f;
   }
   backward_tile<Actor, true>(actor, L, dz3, ta.g1, ta.g2, StoreSink<Wide>(S, i));
+}
+
+// SAC's actor chain up to dz3.  Both halves of a wave compute the row's Philox block and its sample: the action is the B operand of
+// both.  The critics are walked 0, 1 forward and 1, 0 backward, so that critic 1's resident image serves its own backward; the sink
+// adds both critics' d q / d action (the unselected one's is an exact zero: its dq is).
+__global__ void __launch_bounds__(THREADS) sac_actor_backward_kernel(const float* __restrict__ actor, const float* __restrict__ critics, const int m,
+                                                                     const float* __restrict__ obs, const uint64_t seed, const uint32_t draw,
+                                                                     const int learn_alpha, const float target_entropy, const Scratch S) {
+  __shared__ float L[SAC_LDS_FLOATS];
+  const int i = tile_row();
+  const float* __restrict__ critic1 = critics + nparam<Critic>();
+  float sb[OBS / 2], out[SacActor::OUT], z[ACT], q0[1], q1[1];
+  load_obs_operands(obs, m, i, sb);
+  Tape<SacActor, true, SacLay> ta(S, i);
+  forward_tile<SacActor>(actor, L, sb, out, ta);
+  uint32_t o[4];
+  brs::sac::sac_row_block(BRS_SAC_TAG_PI, seed, draw, (uint32_t)i, o);
+  normal_pair(o[0], o[1], z);
+  brs::sac::Sample sm;
+  brs::sac::sample(out, z, sm);
+  const float xb[(OBS + ACT) / 2] = {sb[0], sb[1], sb[2], wave_half() ? sm.a[1] : sm.a[0]};
+  Tape<Critic, false> tc0(S, i), tc1(S, i);
+  forward_tile<Critic>(critics, L, xb, q0, tc0);
+  forward_tile<Critic>(critic1, L, xb, q1, tc1);
+  const bool live = i < m;
+  const float inv_m = 1.0f / (float)m, alpha = brs::sac::ent_coef(actor);
+  const int sel = brs::sac::min_select(q0[0], q1[0]);
+  const float dq0[1] = {live && sel == 0 ? actor_dq(inv_m) : 0.0f}, dq1[1] = {live && sel == 1 ? actor_dq(inv_m) : 0.0f};
+  ActionSink to_action(L);
+  backward_tile<Critic, false>(critic1, L, dq1, tc1.g1, tc1.g2, to_action);
+  backward_tile<Critic, true>(critics, L, dq0, tc0.g1, tc0.g2, to_action);
+  float dz3[SacActor::OUT];
+#pragma unroll
+  for (int k = 0; k < ACT; k++) {
+    const float da = to_action.da[k] + __shfl_xor(to_action.da[k], 32, 64);
+    const float du = brs::sac::sac_du(da, sm.a[k], sm.g[k], alpha * inv_m);
+    dz3[k] = live ? du : 0.0f;   // a row past m contributes exact zeros
+    dz3[ACT + k] = live ? brs::sac::sac_dlog_std(du, sm.sigma[k], z[k], alpha * inv_m, out[ACT + k]) : 0.0f;
+  }
+  if (finishes_row()) {
+    float share[SAC_TAIL];
+    brs::sac::sac_shares(learn_alpha, target_entropy, alpha, sm.logp, sel ? q1[0] : q0[0], inv_m, share);
+#pragma unroll
+    for (int k = 0; k < SacActor::OUT; k++) S.row(SacLay::Z3 + k)[i] = dz3[k];
+#pragma unroll
+    for (int k = 0; k < SAC_TAIL; k++) S.row(SacLay::Z3 + SacActor::OUT + k)[i] = live ? share[k] : 0.0f;
+  }
+}
+
+// ... and the second launch: the actor's backward from what the first left in the scratch -- dz3 in its four per-sample rows, the
+// ReLU gates as the signs of the stored activations (relu_gate of the output is relu_gate of the pre-activation)
+__global__ void __launch_bounds__(THREADS) sac_actor_tail_kernel(const float* __restrict__ actor, const Scratch S) {
+  __shared__ float L[Tile<SacActor>::L_SIZE];
+  using T = Tile<SacActor>;
+  const int i = tile_row();  // < gridDim.x * 128 <= S.ld: every row of the padded batch was written by the first launch
+  Tape<SacActor, false> ta(S, i);
+  const float* __restrict__ h1col = column(S, SacLay::H1, i);
+  const float* __restrict__ h2col = column(S, SacLay::H2, i);
+#pragma unroll
+  for (int mt = 0; mt < T::MT1; mt++)
+#pragma unroll
+    for (int r = 0; r < 16; r++)
+      if (relu_gate(h1col[UNIFORM_UNIT(mt, r) * S.ld])) ta.g1[mt >> 1] |= 1u << (16 * (mt & 1) + r);
+#pragma unroll
+  for (int mt = 0; mt < T::MT2; mt++)
+#pragma unroll
+    for (int r = 0; r < 16; r++)
+      if (relu_gate(h2col[UNIFORM_UNIT(mt, r) * S.ld])) ta.g2[mt >> 1] |= 1u << (16 * (mt & 1) + r);
+  float dz3[SacActor::OUT];
+#pragma unroll
+  for (int k = 0; k < SacActor::OUT; k++) dz3[k] = S.row(SacLay::Z3 + k)[i];
+  backward_tile<SacActor, true>(actor, L, dz3, ta.g1, ta.g2, StoreSink<SacLay>(S, i));
 }
 
 // where a workgroup row (blockIdx.y) of the two sample-contracting kernels reads and writes, for the network of its plane
@@ -266,8 +356,9 @@ __device__ __forceinline__ float wave_sum(float v) {  // a butterfly: every lane
 }
 
 // One wave per row.  Rows [0, H1): dz1[u] -> dW1[u][:] and db1[u]; rows [H1, H1 + H2): dz2[u] -> db2[u], h2[u] -> dW3[:][u];
-// then the OUT + NSTAT per-sample rows -> db3 and the statistics.  Lane l takes samples l, l + 64, ... of the split.
-template <class N, class Lay> __global__ void __launch_bounds__(256) ddpg_rows_kernel(const Scratch all, const Split sp, const int m,
+// then the OUT + NS per-sample rows -> db3 and the statistics (NS = NSTAT but for SAC's actor, whose five sums follow b3 in the
+// buffer).  Lane l takes samples l, l + 64, ... of the split.
+template <class N, class Lay, int NS = NSTAT> __global__ void __launch_bounds__(256) ddpg_rows_kernel(const Scratch all, const Split sp, const int m,
                                                                                       const float* __restrict__ obs, const float* __restrict__ act) {
   using O = Offsets<N>;
   const Scratch S = all.image(blockIdx.z, Lay::ROWS);
@@ -316,7 +407,7 @@ template <class N, class Lay> __global__ void __launch_bounds__(256) ddpg_rows_k
       for (int k = 0; k < N::OUT; k++) out[O::W3 + k * N::H2 + u] = acc[k];
       out[O::B2 + u] = acc[N::OUT];
     }
-  } else if (wv < N::H1 + N::H2 + N::OUT + NSTAT) {
+  } else if (wv < N::H1 + N::H2 + N::OUT + NS) {
     const int j = wv - N::H1 - N::H2;
     const float* __restrict__ z = S.row(Lay::Z3 + j);
     float acc = 0.0f;
@@ -352,6 +443,7 @@ struct brs_ddpg_learner {
   float* partial = nullptr;
   size_t bytes = 0;
   bool twin = false;         // from brs_ddpg_learner_create_twin: two critic images fit the rows, a twin row fits a partial row
+  bool sac = false;          // from brs_ddpg_learner_create_sac: a twin handle that also fits the SAC actor's image and row
   std::string err;
 };
 
@@ -360,19 +452,19 @@ using brs::host::DeviceGuard, brs::host::fail;
 namespace {
 
 // the scratch view, the split of m rows and the launches after a backward kernel
-template <class N, class Lay = Wide, int NETS = 1> void launch_weight_kernels(brs_ddpg_learner* l, int m, const float* obs, const float* act, float* grad, hipStream_t s) {
+template <class N, class Lay = Wide, int NETS = 1, int NS = NSTAT> void launch_weight_kernels(brs_ddpg_learner* l, int m, const float* obs, const float* act, float* grad, hipStream_t s) {
   const SampleSplit ss = sample_split(m);  // brs_ddpg_learner.hpp
   const int mp = ss.mp, span = ss.span, nsplit = ss.nsplit;
   const Scratch S{l->block, l->ld};
   // NETS networks side by side in a row of `len` floats: their parameter blocks, then their statistics
-  const int len = NETS * nparam<N>() + NETS * NSTAT;
+  const int len = NETS * nparam<N>() + NETS * NS;
   const Split sp{mp, span, nsplit == 1 ? grad : l->partial, len, nparam<N>(), NETS * nparam<N>()};
   hipLaunchKernelGGL((ddpg_dw2_kernel<N, Lay>), dim3((Tile<N>::MT1 * Tile<N>::MT2 + 3) / 4, nsplit, NETS), dim3(256), 0, s, S, sp);
-  hipLaunchKernelGGL((ddpg_rows_kernel<N, Lay>), dim3((N::H1 + N::H2 + N::OUT + NSTAT + 3) / 4, nsplit, NETS), dim3(256), 0, s, S, sp, m, obs, act);
+  hipLaunchKernelGGL((ddpg_rows_kernel<N, Lay, NS>), dim3((N::H1 + N::H2 + N::OUT + NS + 3) / 4, nsplit, NETS), dim3(256), 0, s, S, sp, m, obs, act);
   if (nsplit > 1) hipLaunchKernelGGL(ddpg_combine_kernel, dim3((len + 255) / 256), dim3(256), 0, s, l->partial, nsplit, len, grad);
 }
 
-int create(const char* who, bool twin, int32_t device, int32_t max_batch, brs_ddpg_learner** out) {
+int create(const char* who, bool twin, bool sac, int32_t device, int32_t max_batch, brs_ddpg_learner** out) {
   const std::string w(who);
   if (!out) return fail<brs_ddpg_learner>(nullptr, BRS_ERR_ARG, w + ": null argument");
   *out = nullptr;
@@ -386,8 +478,9 @@ int create(const char* who, bool twin, int32_t device, int32_t max_batch, brs_dd
   l->max_batch = max_batch;
   l->ld = pad128(max_batch);
   l->twin = twin;
-  const size_t scratch = (size_t)(twin ? TWIN_SCRATCH_ROWS : SCRATCH_ROWS) * l->ld,
-               bytes = (scratch + partial_floats(twin)) * sizeof(float);
+  l->sac = sac;
+  const size_t scratch = (size_t)(sac ? SAC_SCRATCH_ROWS : twin ? TWIN_SCRATCH_ROWS : SCRATCH_ROWS) * l->ld,
+               bytes = (scratch + (sac ? (size_t)MAX_SPLIT * SAC_PARTIAL_LEN : partial_floats(twin))) * sizeof(float);
   if (hipMalloc((void**)&l->block, bytes) != hipSuccess || hipMemset(l->block, 0, bytes) != hipSuccess) {
     if (l->block) (void)hipFree(l->block);
     delete l;
@@ -404,11 +497,15 @@ int create(const char* who, bool twin, int32_t device, int32_t max_batch, brs_dd
 extern "C" {
 
 int brs_ddpg_learner_create(int32_t device, int32_t max_batch, brs_ddpg_learner** out) {
-  return create("brs_ddpg_learner_create", false, device, max_batch, out);
+  return create("brs_ddpg_learner_create", false, false, device, max_batch, out);
 }
 
 int brs_ddpg_learner_create_twin(int32_t device, int32_t max_batch, brs_ddpg_learner** out) {
-  return create("brs_ddpg_learner_create_twin", true, device, max_batch, out);
+  return create("brs_ddpg_learner_create_twin", true, false, device, max_batch, out);
+}
+
+int brs_ddpg_learner_create_sac(int32_t device, int32_t max_batch, brs_ddpg_learner** out) {
+  return create("brs_ddpg_learner_create_sac", true, true, device, max_batch, out);
 }
 
 int brs_ddpg_learner_destroy(brs_ddpg_learner* l) {
@@ -442,7 +539,7 @@ int brs_ddpg_learner_critic_grad(brs_ddpg_learner* l, const float* critic_dev, i
   if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_ddpg_learner_critic_grad: hipSetDevice failed");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ddpg_critic_backward_kernel<Wide>, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, critic_dev, m, obs_dev, act_dev, y_dev,
-                     Scratch{l->block, l->ld});
+                     Scratch{l->block, l->ld}, 1.0f);
   launch_weight_kernels<Critic>(l, m, obs_dev, act_dev, grad_dev, s);
   BRS_HIP_TRY(l, hipGetLastError());
   return BRS_OK;
@@ -461,8 +558,43 @@ int brs_ddpg_learner_twin_critic_grad(brs_ddpg_learner* l, const float* critics_
   if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_ddpg_learner_twin_critic_grad: hipSetDevice failed");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ddpg_critic_backward_kernel<Narrow>, dim3(pad128(m) / WG_ROWS, 2), dim3(THREADS), 0, s, critics_dev, m, obs_dev, act_dev,
-                     y_dev, Scratch{l->block, l->ld});
+                     y_dev, Scratch{l->block, l->ld}, 1.0f);
   launch_weight_kernels<Critic, Narrow, 2>(l, m, obs_dev, act_dev, grad_dev, s);
+  BRS_HIP_TRY(l, hipGetLastError());
+  return BRS_OK;
+}
+
+int brs_sac_twin_critic_grad(brs_ddpg_learner* l, const float* critics_dev, int32_t m, const float* obs_dev, const float* act_dev, const float* y_dev,
+                             float* grad_dev, void* stream) {
+  if (const char* why = brs::sac::sac_critic_grad_argument_error(critics_dev, m, obs_dev, act_dev, y_dev, grad_dev))
+    return fail(l, BRS_ERR_ARG, std::string("brs_sac_twin_critic_grad: ") + why);
+  if (!l) return fail(l, BRS_ERR_ARG, "brs_sac_twin_critic_grad: null handle");
+  if (!l->sac) return fail(l, BRS_ERR_ARG, "brs_sac_twin_critic_grad: the handle was not created with brs_ddpg_learner_create_sac");
+  if (m > l->max_batch) return fail(l, BRS_ERR_ARG, "brs_sac_twin_critic_grad: m exceeds the handle's max_batch");
+  DeviceGuard g(l->device);
+  if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_sac_twin_critic_grad: hipSetDevice failed");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ddpg_critic_backward_kernel<Narrow>, dim3(pad128(m) / WG_ROWS, 2), dim3(THREADS), 0, s, critics_dev, m, obs_dev, act_dev,
+                     y_dev, Scratch{l->block, l->ld}, 0.5f);
+  launch_weight_kernels<Critic, Narrow, 2>(l, m, obs_dev, act_dev, grad_dev, s);
+  BRS_HIP_TRY(l, hipGetLastError());
+  return BRS_OK;
+}
+
+int brs_sac_actor_grad(brs_ddpg_learner* l, const float* actor_dev, const float* critics_dev, int32_t m, const float* obs_dev, uint64_t seed,
+                       uint32_t draw, int32_t learn_alpha, float target_entropy, float* grad_dev, void* stream) {
+  if (const char* why = brs::sac::sac_actor_grad_argument_error(actor_dev, critics_dev, m, obs_dev, target_entropy, grad_dev))
+    return fail(l, BRS_ERR_ARG, std::string("brs_sac_actor_grad: ") + why);
+  if (!l) return fail(l, BRS_ERR_ARG, "brs_sac_actor_grad: null handle");
+  if (!l->sac) return fail(l, BRS_ERR_ARG, "brs_sac_actor_grad: the handle was not created with brs_ddpg_learner_create_sac");
+  if (m > l->max_batch) return fail(l, BRS_ERR_ARG, "brs_sac_actor_grad: m exceeds the handle's max_batch");
+  DeviceGuard g(l->device);
+  if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_sac_actor_grad: hipSetDevice failed");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sac_actor_backward_kernel, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, actor_dev, critics_dev, m, obs_dev, seed, draw,
+                     learn_alpha != 0, target_entropy, Scratch{l->block, l->ld});
+  hipLaunchKernelGGL(sac_actor_tail_kernel, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, actor_dev, Scratch{l->block, l->ld});
+  launch_weight_kernels<SacActor, SacLay, 1, SAC_TAIL>(l, m, obs_dev, nullptr, grad_dev, s);
   BRS_HIP_TRY(l, hipGetLastError());
   return BRS_OK;
 }

@@ -35,6 +35,7 @@ template <class N> struct Tile {
                        CH_SIZE = H2P * CH_LD, L_SIZE = L_CH + 2 * CH_SIZE;
   static constexpr int CH_PER_THREAD = H2P * 32 / THREADS;  // words of a chunk each thread moves
   static_assert(N::IN % 2 == 0 && (H2P * 32) % THREADS == 0, "tiling");
+  static_assert(N::OUT >= 1 && N::OUT <= 4, "the image reserves 4 words for b3 (the SAC actor of brs_sac.hpp uses all of them)");
 };
 constexpr int LDS_FLOATS = Tile<Actor>::L_SIZE > Tile<Critic>::L_SIZE ? Tile<Actor>::L_SIZE : Tile<Critic>::L_SIZE;
 

@@ -1,6 +1,6 @@
 // brs_offpolicy.hip -- the DDPG data path of include/brs_policy.h: actor with exploration noise, critic, TD
 // target from the two target networks, replay buffer add and fused sample, as HIP kernels for gfx950; and TD3's target with
-// smoothing noise and two target critics.
+// smoothing noise and two target critics; and SAC's squashed-Gaussian actor and its entropy target.
 //
 // One forward routine (forward_tile, brs_ddpg_tile.hpp, shared with brs_ddpg_learner.hip) serves brs_ddpg_act, brs_ddpg_q and brs_ddpg_td_target.  It is brs_policy.hip's scheme for
 // wider layers: fp32 on the MATRIX cores (v_mfma_f32_32x32x2_f32: exact fp32 products, a k-ordered fma chain), the product
@@ -24,11 +24,15 @@
 #include "brs_host.hpp"
 #include "brs_ddpg_tile.hpp"
 #include "brs_offpolicy.hpp"
+#include "brs_sac.hpp"
 
 namespace {
 
 using namespace brs::offpolicy;
 using namespace brs::ddpg_tile;
+using brs::sac::SacActor;
+constexpr int SAC_LDS_FLOATS = Tile<SacActor>::L_SIZE > LDS_FLOATS ? Tile<SacActor>::L_SIZE : LDS_FLOATS;
+static_assert(Tile<SacActor>::L_SIZE == Tile<Actor>::L_SIZE + 2 * Tile<Actor>::H2P && SAC_LDS_FLOATS * sizeof(float) <= 160 * 1024, "LDS");
 
 __global__ void __launch_bounds__(THREADS) ddpg_act_kernel(const float* __restrict__ actor, const int n, const float* __restrict__ obs,
                                                            const uint64_t seed, const int64_t gid_base, const uint32_t step, const float sigma,
@@ -114,6 +118,75 @@ __global__ void __launch_bounds__(THREADS) td3_td_target_kernel(const float* __r
 #pragma unroll
   for (int k = 0; k < ACT; k++) {
     if (next_action) next_action[(size_t)ACT * i + k] = a[k];
+    if (noise) noise[(size_t)ACT * i + k] = z[k];
+  }
+}
+
+// SAC's actor: the forward with four outputs, then the per-row tail of brs_sac.hpp
+__global__ void __launch_bounds__(THREADS) sac_act_kernel(const float* __restrict__ actor, const int n, const float* __restrict__ obs,
+                                                          const uint64_t seed, const int64_t gid_base, const uint32_t step, const int deterministic,
+                                                          float* __restrict__ action, float* __restrict__ mu, float* __restrict__ log_std,
+                                                          float* __restrict__ noise) {
+  __shared__ float L[Tile<SacActor>::L_SIZE];
+  const int i = tile_row();
+  float xb[OBS / 2], out[SacActor::OUT];
+  load_obs_operands(obs, n, i, xb);
+  forward_tile<SacActor>(actor, L, xb, out);
+  if (i >= n || !finishes_row()) return;
+  float a[ACT], m[ACT], ls[ACT], z[ACT];
+  brs::sac::sac_act_tail(seed, gid_base + (int64_t)i, step, deterministic, 0, out, a, m, ls, z);
+#pragma unroll
+  for (int k = 0; k < ACT; k++) {
+    action[(size_t)ACT * i + k] = a[k];
+    if (mu) mu[(size_t)ACT * i + k] = m[k];
+    if (log_std) log_std[(size_t)ACT * i + k] = ls[k];
+    if (noise) noise[(size_t)ACT * i + k] = z[k];
+  }
+}
+
+__global__ void __launch_bounds__(256) sac_random_kernel(const int n, const uint64_t seed, const int64_t gid_base, const uint32_t step,
+                                                         float* __restrict__ action, float* __restrict__ mu, float* __restrict__ log_std,
+                                                         float* __restrict__ noise) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float none[SacActor::OUT] = {0.0f, 0.0f, 0.0f, 0.0f};
+  float a[ACT], m[ACT], ls[ACT], z[ACT];
+  brs::sac::sac_act_tail(seed, gid_base + (int64_t)i, step, 0, 1, none, a, m, ls, z);
+#pragma unroll
+  for (int k = 0; k < ACT; k++) {
+    action[(size_t)ACT * i + k] = a[k];
+    if (mu) mu[(size_t)ACT * i + k] = m[k];
+    if (log_std) log_std[(size_t)ACT * i + k] = ls[k];
+    if (noise) noise[(size_t)ACT * i + k] = z[k];
+  }
+}
+
+// SAC's target: the CURRENT actor -> sample and logp -> target critic 0 -> target critic 1 -> minimum, entropy term, combine in one
+// launch; the three forwards share the LDS image one after the other.  alpha = exp(actor[BRS_SAC_NACTOR]) is read here.
+__global__ void __launch_bounds__(THREADS) sac_td_target_kernel(const float* __restrict__ actor, const float* __restrict__ critics_t, const int m,
+                                                                const float* __restrict__ next_obs, const float* __restrict__ reward,
+                                                                const uint8_t* __restrict__ done, const float gamma, const uint64_t seed,
+                                                                const uint32_t draw, float* __restrict__ y, float* __restrict__ next_action,
+                                                                float* __restrict__ logp, float* __restrict__ noise) {
+  __shared__ float L[SAC_LDS_FLOATS];
+  const int i = tile_row();
+  float sb[OBS / 2], out[SacActor::OUT], z[ACT], q1[1], q2[1];
+  load_obs_operands(next_obs, m, i, sb);
+  forward_tile<SacActor>(actor, L, sb, out);
+  uint32_t o[4];
+  brs::sac::sac_row_block(BRS_SAC_TAG_TARGET, seed, draw, (uint32_t)i, o);
+  normal_pair(o[0], o[1], z);
+  brs::sac::Sample sm;
+  brs::sac::sample(out, z, sm);
+  const float xb[(OBS + ACT) / 2] = {sb[0], sb[1], sb[2], wave_half() ? sm.a[1] : sm.a[0]};
+  forward_tile<Critic>(critics_t, L, xb, q1);
+  forward_tile<Critic>(critics_t + nparam<Critic>(), L, xb, q2);
+  if (i >= m || !finishes_row()) return;
+  y[i] = brs::sac::sac_combine(reward[i], done[i], gamma, q1[0], q2[0], brs::sac::ent_coef(actor), sm.logp);
+  if (logp) logp[i] = sm.logp;
+#pragma unroll
+  for (int k = 0; k < ACT; k++) {
+    if (next_action) next_action[(size_t)ACT * i + k] = sm.a[k];
     if (noise) noise[(size_t)ACT * i + k] = z[k];
   }
 }
@@ -276,6 +349,37 @@ int brs_td3_td_target(brs_ddpg* d, const float* actor_target_dev, const float* c
   hipLaunchKernelGGL(td3_td_target_kernel, dim3((m + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_target_dev,
                      critics_target_dev, m, next_obs_dev, reward_dev, done_dev, gamma, policy_noise, noise_clip, seed, draw, y_dev,
                      next_action_dev, noise_dev);
+  BRS_HIP_TRY(d, hipGetLastError());
+  return BRS_OK;
+}
+
+int brs_sac_act(brs_ddpg* d, const float* actor_dev, int32_t n, const float* obs_dev, uint64_t seed, int64_t env_index_base, uint32_t step,
+                int32_t deterministic, int32_t random, float* action_dev, float* mu_dev, float* log_std_dev, float* z_dev, void* stream) {
+  if (const char* why = brs::sac::sac_act_argument_error(actor_dev, n, obs_dev, random, action_dev))
+    return fail(d, BRS_ERR_ARG, std::string("brs_sac_act: ") + why);
+  if (!d) return fail(d, BRS_ERR_ARG, "brs_sac_act: null handle");
+  DeviceGuard g(d->device);
+  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_sac_act: hipSetDevice failed");
+  if (random)
+    hipLaunchKernelGGL(sac_random_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, env_index_base, step, action_dev,
+                       mu_dev, log_std_dev, z_dev);
+  else
+    hipLaunchKernelGGL(sac_act_kernel, dim3((n + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_dev, n, obs_dev, seed,
+                       env_index_base, step, deterministic != 0, action_dev, mu_dev, log_std_dev, z_dev);
+  BRS_HIP_TRY(d, hipGetLastError());
+  return BRS_OK;
+}
+
+int brs_sac_td_target(brs_ddpg* d, const float* actor_dev, const float* critics_target_dev, int32_t m, const float* next_obs_dev,
+                      const float* reward_dev, const uint8_t* done_dev, float gamma, uint64_t seed, uint32_t draw, float* y_dev,
+                      float* next_action_dev, float* logp_dev, float* z_dev, void* stream) {
+  if (const char* why = brs::sac::sac_target_argument_error(actor_dev, critics_target_dev, m, next_obs_dev, reward_dev, done_dev, gamma, y_dev))
+    return fail(d, BRS_ERR_ARG, std::string("brs_sac_td_target: ") + why);
+  if (!d) return fail(d, BRS_ERR_ARG, "brs_sac_td_target: null handle");
+  DeviceGuard g(d->device);
+  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_sac_td_target: hipSetDevice failed");
+  hipLaunchKernelGGL(sac_td_target_kernel, dim3((m + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_dev,
+                     critics_target_dev, m, next_obs_dev, reward_dev, done_dev, gamma, seed, draw, y_dev, next_action_dev, logp_dev, z_dev);
   BRS_HIP_TRY(d, hipGetLastError());
   return BRS_OK;
 }

@@ -561,3 +561,208 @@ class DeviceTD3Learner:
             t.copy_(src.to(device=self.device, dtype=torch.float32))
         for k in self._COUNTERS:
             setattr(self, k, int(sd[k]))
+
+
+# ------------------------------------------------------------------------------------------------ SAC
+SAC_NACTOR = _lib.SAC_NACTOR
+SAC_GRAD_LEN = SAC_NACTOR + 1 + _lib.SAC_NSTAT
+# the SAC actor VECTOR [SAC_NACTOR + 1]: latent_pi's two layers, the mu and log_std heads stacked into one [4][200] layer, then
+# log_ent_coef.  SB3's SACPolicy (actor.latent_pi.{0,2}, actor.mu, actor.log_std; log_ent_coef is the algorithm's, not the policy's,
+# and is looked up under that name) and tools/train_sac_torch.py (actor.body.{0,2}, actor.mu, actor.log_std, log_ent_coef)
+SAC_ACTOR_NAMINGS = {"sb3": ("actor.latent_pi.0.", "actor.latent_pi.2.", "actor.mu.", "actor.log_std."),
+                     "tool": ("actor.body.0.", "actor.body.2.", "actor.mu.", "actor.log_std.")}
+_SAC_LAYER_SHAPES = (((300, 6), (300,)), ((200, 300), (200,)), ((2, 200), (2,)), ((2, 200), (2,)))
+
+
+def _sac_naming_of(sd):
+    for naming, prefixes in SAC_ACTOR_NAMINGS.items():
+        if prefixes[0] + "weight" in sd:
+            return naming
+    raise ValueError("neither SB3's SACPolicy naming (actor.latent_pi.0.weight) nor the SAC tool's (actor.body.0.weight)")
+
+
+def flatten_sac_actor(sd):
+    """state_dict in either naming, with a scalar `log_ent_coef` in it -> the flat float32 actor vector [SAC_NACTOR + 1]"""
+    prefixes = SAC_ACTOR_NAMINGS[_sac_naming_of(sd)]
+    got = {}
+    for prefix, (wshape, bshape) in zip(prefixes, _SAC_LAYER_SHAPES):
+        for kind, shape in (("weight", wshape), ("bias", bshape)):
+            name = prefix + kind
+            if name not in sd:
+                raise ValueError(f"{name}: missing")
+            a = sd[name]
+            a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+            if tuple(a.shape) != shape:
+                raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
+            got[name] = a.astype(np.float32)
+    if "log_ent_coef" not in sd:
+        raise ValueError("log_ent_coef: missing")
+    t = sd["log_ent_coef"]
+    t = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+    if t.size != 1:
+        raise ValueError(f"log_ent_coef: expected one element, got shape {tuple(t.shape)}")
+    p = prefixes
+    flat = np.concatenate([got[p[0] + "weight"].ravel(), got[p[0] + "bias"], got[p[1] + "weight"].ravel(), got[p[1] + "bias"],
+                           got[p[2] + "weight"].ravel(), got[p[3] + "weight"].ravel(), got[p[2] + "bias"], got[p[3] + "bias"],
+                           t.astype(np.float32).ravel()])
+    assert flat.size == SAC_NACTOR + 1
+    return flat
+
+
+def unflatten_sac_actor(flat, naming="sb3"):
+    """the actor vector [SAC_NACTOR + 1] -> {name: tensor} in `naming` ('sb3' or 'tool'), log_ent_coef as a tensor of shape (1,)"""
+    flat = np.ascontiguousarray(flat.detach().cpu().numpy() if hasattr(flat, "detach") else flat, dtype=np.float32)
+    if flat.shape != (SAC_NACTOR + 1,):
+        raise ValueError(f"expected {SAC_NACTOR + 1} elements, got shape {flat.shape}")
+    if naming not in SAC_ACTOR_NAMINGS:
+        raise ValueError(f"naming must be 'sb3' or 'tool', got {naming!r}")
+    p, out, at = SAC_ACTOR_NAMINGS[naming], {}, 0
+
+    def take(shape):
+        nonlocal at
+        k = int(np.prod(shape))
+        t = torch.from_numpy(flat[at:at + k].reshape(shape).copy())
+        at += k
+        return t
+    for prefix, (wshape, bshape) in zip(p[:2], _SAC_LAYER_SHAPES[:2]):
+        out[prefix + "weight"], out[prefix + "bias"] = take(wshape), take(bshape)
+    out[p[2] + "weight"], out[p[3] + "weight"] = take((2, 200)), take((2, 200))
+    out[p[2] + "bias"], out[p[3] + "bias"] = take((2,)), take((2,))
+    out["log_ent_coef"] = take((1,))
+    return out
+
+
+class DeviceSACNets(DeviceDDPGNets):
+    """SB3's SACPolicy on the reference's DDPG widths, evaluated by the HIP kernels (brs_sac_act, brs_sac_td_target): the
+    squashed-Gaussian actor [SAC_NACTOR + 1] (the last element is log_ent_coef) and the two target critics [2 NCRITIC].  act() has
+    DeviceDDPGNets.act's surface, so DeviceOffPolicyCollector drives it unchanged; q() is inherited."""
+
+    def act(self, actor_params, obs, step, sigma=None, random=False, deterministic=False, out=None, mean=None, log_std=None, noise=None):
+        """obs [n,6] -> action [n,2] = tanh(mu + exp(clamp(log_std, -20, 2)) z); deterministic: tanh(mu); `random`: the learning_starts
+        phase (uniform; actor_params and obs may be None, n is then taken from `out`); `sigma` is ignored (SAC has no action noise: the
+        collector passes its own); mean / log_std / noise: optional [n,2] outputs (mu, the clamped log_std, z)"""
+        d, f32 = self.device, torch.float32
+        n = out.shape[0] if random and obs is None else obs.shape[0]
+        if not random:
+            _need(actor_params, "actor_params", f32, (SAC_NACTOR + 1,), d); _need(obs, "obs", f32, (n, 6), d)
+        if out is None:
+            out = torch.empty((n, 2), dtype=f32, device=d)
+        _need(out, "action", f32, (n, 2), d)
+        for t, name in ((mean, "mean"), (log_std, "log_std"), (noise, "noise")):
+            if t is not None:
+                _need(t, name, f32, (n, 2), d)
+        self._check(self.L.brs_sac_act(self.h, None if random else _p(actor_params), n, None if random else _p(obs), self.seed,
+                                       self.env_index_base, int(step) & 0xffffffff, int(bool(deterministic)), int(bool(random)), _p(out),
+                                       _p(mean), _p(log_std), _p(noise), self._stream()), "brs_sac_act")
+        return out
+
+    def sac_target(self, actor, critics_target, next_obs, reward, done, gamma, draw, out=None, next_action=None, logp=None, noise=None):
+        """SAC's target, one launch: y = reward + (1 - done) gamma (min(Q1', Q2')(next_obs, a') - alpha logp') with a', logp' sampled
+        from the CURRENT actor and alpha = exp(actor[-1]); `draw`: the counter of this call's noise (with the object's seed);
+        next_action [m,2], logp [m], noise [m,2]: optional outputs -> y [m]"""
+        d, f32, m = self.device, torch.float32, next_obs.shape[0]
+        _need(actor, "actor", f32, (SAC_NACTOR + 1,), d); _need(critics_target, "critics_target", f32, (2 * NCRITIC,), d)
+        _need(next_obs, "next_obs", f32, (m, 6), d); _need(reward, "reward", f32, (m,), d); _need(done, "done", torch.uint8, (m,), d)
+        if out is None:
+            out = torch.empty(m, dtype=f32, device=d)
+        _need(out, "y", f32, (m,), d)
+        for t, name, shape in ((next_action, "next_action", (m, 2)), (logp, "logp", (m,)), (noise, "noise", (m, 2))):
+            if t is not None:
+                _need(t, name, f32, shape, d)
+        self._check(self.L.brs_sac_td_target(self.h, _p(actor), _p(critics_target), m, _p(next_obs), _p(reward), _p(done), float(gamma), self.seed,
+                                             int(draw) & 0xffffffff, _p(out), _p(next_action), _p(logp), _p(noise), self._stream()),
+                    "brs_sac_td_target")
+        return out
+
+
+class DeviceSACLearner:
+    """SB3's SAC.train by the HIP kernels, on the reference's DDPG widths: the gradient of 0.5 (mse(Q1, y) + mse(Q2, y)) w.r.t. both
+    critics (brs_sac_twin_critic_grad), one Adam with the Polyak update over the [2 NCRITIC] vector, the actor's gradient through
+    both UPDATED critics with the temperature's in the same buffer (brs_sac_actor_grad), and one Adam over the [SAC_NACTOR + 1]
+    vector, actor and log_ent_coef together (SB3 gives both the same learning rate, and Adam is element-wise).  The vectors are the
+    caller's flat float32 device tensors, updated in place; this object owns the two gradient buffers, the moment vectors and the
+    step counter.  With learn_alpha=False the temperature's gradient is written as 0 and Adam leaves the element as it is."""
+
+    def __init__(self, device=0, max_batch=256, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, tau=0.005, target_entropy=-2.0, learn_alpha=True, seed=0):
+        if not torch.cuda.is_available():
+            raise BrsError("no HIP device visible to PyTorch: the on-device SAC learner has no CPU fallback")
+        self.L = _lib.lib()
+        self.device = _device(device)
+        self.max_batch, self.tau, self.target_entropy, self.learn_alpha, self.seed = int(max_batch), float(tau), float(target_entropy), bool(learn_alpha), int(seed)
+        self.cfg = _lib.BrsAdamConfig(float(lr), float(betas[0]), float(betas[1]), float(eps))
+        h = C.c_void_p()
+        rc = self.L.brs_ddpg_learner_create_sac(self.device.index, self.max_batch, C.byref(h))
+        if rc != 0:
+            raise BrsError(f"brs_ddpg_learner_create_sac failed ({rc}): {self.L.brs_ddpg_learner_last_error(None).decode()}")
+        self.h = h
+        z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.grad_critics, self.grad_actor = z(2 * NCRITIC + _lib.TD3_NSTAT), z(SAC_GRAD_LEN)
+        self.m_critics, self.v_critics, self.m_actor, self.v_actor = z(2 * NCRITIC), z(2 * NCRITIC), z(SAC_NACTOR + 1), z(SAC_NACTOR + 1)
+        self.steps_critics = self.steps_actor = 0
+
+    close, __del__, _check, _stream, scratch = (DeviceDDPGLearner.close, DeviceDDPGLearner.__del__, DeviceDDPGLearner._check,
+                                                DeviceDDPGLearner._stream, DeviceDDPGLearner.scratch)
+
+    def twin_critic_grad(self, critics, obs, action, y, out=None):
+        """-> [2 NCRITIC + 4]: the gradient of 0.5 (mse(Q1(s, a), y) + mse(Q2(s, a), y)) w.r.t. critic 0 and critic 1, then 0.5 mse and
+        the mean Q of critic 0 and of critic 1"""
+        d, f32, m = self.device, torch.float32, obs.shape[0]
+        out = self.grad_critics if out is None else out
+        _need(critics, "critics", f32, (2 * NCRITIC,), d); _need(obs, "obs", f32, (m, 6), d); _need(action, "action", f32, (m, 2), d)
+        _need(y, "y", f32, (m,), d); _need(out, "grad", f32, (2 * NCRITIC + _lib.TD3_NSTAT,), d)
+        self._check(self.L.brs_sac_twin_critic_grad(self.h, _p(critics), m, _p(obs), _p(action), _p(y), _p(out), self._stream()),
+                    "brs_sac_twin_critic_grad")
+        return out
+
+    def actor_grad(self, actor, critics, obs, draw, out=None):
+        """-> [SAC_NACTOR + 1 + 4]: the gradient of La = mean(alpha logp - min(Q1, Q2)(s, a)) in the actor's flat order, the
+        temperature's -(mean logp + target_entropy) (0 with learn_alpha=False), then La, mean logp, mean min Q and alpha; `draw`: the
+        counter of this call's noise (with the object's seed)"""
+        d, f32, m = self.device, torch.float32, obs.shape[0]
+        out = self.grad_actor if out is None else out
+        _need(actor, "actor", f32, (SAC_NACTOR + 1,), d); _need(critics, "critics", f32, (2 * NCRITIC,), d); _need(obs, "obs", f32, (m, 6), d)
+        _need(out, "grad", f32, (SAC_GRAD_LEN,), d)
+        self._check(self.L.brs_sac_actor_grad(self.h, _p(actor), _p(critics), m, _p(obs), self.seed, int(draw) & 0xffffffff, int(self.learn_alpha),
+                                              self.target_entropy, _p(out), self._stream()), "brs_sac_actor_grad")
+        return out
+
+    def _apply(self, n, params, grad, glen, mom, vel, target, step, name):
+        d, f32 = self.device, torch.float32
+        _need(params, name, f32, (n,), d); _need(grad, "grad", f32, (glen,), d)
+        _need(mom, "m_" + name, f32, (n,), d); _need(vel, "v_" + name, f32, (n,), d)
+        if target is not None:
+            _need(target, name + "_target", f32, (n,), d)
+        self._check(self.L.brs_ddpg_learner_apply(self.h, n, _p(params), _p(grad), _p(mom), _p(vel), _p(target), C.byref(self.cfg), step,
+                                                  self.tau, self._stream()), "brs_ddpg_learner_apply")
+
+    def apply_critics(self, critics, critics_target=None, grad=None):
+        """one Adam step over both critics from grad_critics (or `grad`), then the Polyak update of critics_target"""
+        self._apply(2 * NCRITIC, critics, self.grad_critics if grad is None else grad, 2 * NCRITIC + _lib.TD3_NSTAT, self.m_critics, self.v_critics,
+                    critics_target, self.steps_critics + 1, "critics")
+        self.steps_critics += 1
+
+    def apply_actor(self, actor, grad=None):
+        """one Adam step over the actor and log_ent_coef from grad_actor (or `grad`); SAC has no target actor"""
+        self._apply(SAC_NACTOR + 1, actor, self.grad_actor if grad is None else grad, SAC_GRAD_LEN, self.m_actor, self.v_actor, None,
+                    self.steps_actor + 1, "actor")
+        self.steps_actor += 1
+
+    def step(self, flat, obs, action, y, draw):
+        """one update of SB3's SAC.train on a dict of the three flat vectors actor [SAC_NACTOR + 1], critics, critics_target, for a y
+        computed from them BEFORE this call (DeviceSACNets.sac_target): critic gradient, critics' Adam and Polyak, the actor's
+        gradient through the updated critics with the temperature of before the update, one Adam over actor and temperature"""
+        self.twin_critic_grad(flat["critics"], obs, action, y)
+        self.apply_critics(flat["critics"], flat["critics_target"])
+        self.actor_grad(flat["actor"], flat["critics"], obs, draw)
+        self.apply_actor(flat["actor"])
+
+    def stats(self):
+        """one device-to-host copy: critic_loss (SB3's 0.5 (mse1 + mse2)), mean_q1, mean_q2, actor_loss, mean_logp, mean_qmin and
+        ent_coef (the alpha the last actor gradient used), ent_coef_grad"""
+        c0, q0, c1, q1, ge, la, lp, qm, al = torch.cat([self.grad_critics[2 * NCRITIC:], self.grad_actor[SAC_NACTOR:]]).cpu().tolist()
+        return {"critic_loss": c0 + c1, "mean_q1": q0, "mean_q2": q1, "actor_loss": la, "mean_logp": lp, "mean_qmin": qm, "ent_coef": al,
+                "ent_coef_grad": ge}
+
+    _TENSORS = ("m_critics", "v_critics", "m_actor", "v_actor")
+    _COUNTERS = ("steps_critics", "steps_actor")
+    state_dict, load_state_dict = DeviceTD3Learner.state_dict, DeviceTD3Learner.load_state_dict

@@ -301,6 +301,50 @@ int brs_ddpg_learner_create_twin(int32_t device, int32_t max_batch, brs_ddpg_lea
 int brs_ddpg_learner_twin_critic_grad(brs_ddpg_learner*, const float* critics_dev, int32_t m, const float* obs_dev, const float* act_dev,
                                       const float* y_dev, float* grad_dev, void* stream);
 
+/* ---- SAC on the same widths: SB3's SACPolicy / SAC.train with pi=[300, 200], qf=[200, 150].
+ *   SAC actor: W1[300][6] b1[300] W2[200][300] b2[200] W3[4][200] b3[4], ReLU ReLU linear; output rows 0-1 are actor.mu, rows 2-3
+ *              actor.log_std (two Linear(200, 2) stacked).  The actor VECTOR has BRS_SAC_NACTOR + 1 elements: the last one is
+ *              log_ent_coef, and every SAC kernel that needs the temperature reads alpha = exp(actor[BRS_SAC_NACTOR]) from device
+ *              memory.  brs_sac_act does not read that element.
+ *   critics  : two DDPG critics back to back [2 BRS_DDPG_NCRITIC], as TD3's; only the critics have targets.
+ * With sigma = exp(clamp(log_std, -20, 2)), u = mu + sigma z and a = tanh(u):
+ *   logp = sum_k (-z_k^2 / 2 - log_std_k - log(2 pi) / 2) - sum_k log(1 - a_k^2 + 1e-6)     (log_std clamped; 1 - a^2 from the
+ *   exponential of the tanh, so that it does not cancel where the tanh saturates) */
+#define BRS_SAC_NACTOR (300 * 6 + 300 + 200 * 300 + 200 + 4 * 200 + 4) /* 63,104 */
+#define BRS_SAC_NSTAT 4
+#define BRS_SAC_TAG_ACT 0x53414341u    /* "SACA": second Philox counter word of brs_sac_act */
+#define BRS_SAC_TAG_TARGET 0x53414354u /* "SACT": ... of brs_sac_td_target */
+#define BRS_SAC_TAG_PI 0x53414350u     /* "SACP": ... of brs_sac_actor_grad */
+
+/* SB3's SAC actor for n envs, brs_ddpg_act's contract: action = tanh(mu + sigma z) with z[0], z[1] from words 0 and 1 of
+ * Philox4x32-10(counter = (step, BRS_SAC_TAG_ACT, gid_lo, gid_hi), key = seed), gid = env_index_base + i, by brs_ddpg_act's
+ * Box-Muller; deterministic != 0: action = tanh(mu); random != 0 (the learning_starts phase; actor_dev and obs_dev may be NULL):
+ * the uniform components of words 2 and 3, and then mu = action, log_std = 0.  mu_dev, log_std_dev (clamped) and z_dev [n][2] may
+ * be NULL. */
+int brs_sac_act(brs_ddpg*, const float* actor_dev, int32_t n, const float* obs_dev, uint64_t seed, int64_t env_index_base, uint32_t step,
+                int32_t deterministic, int32_t random, float* action_dev, float* mu_dev, float* log_std_dev, float* z_dev, void* stream);
+/* y[m] = reward + (1 - done) gamma (min(Q1', Q2')(s', a') - alpha logp') in one launch: the CURRENT actor on next_obs (SAC has
+ * no target actor), row j's z from Philox4x32-10(counter = (draw, BRS_SAC_TAG_TARGET, j, 0), key = seed), the two TARGET critics.
+ * A row with done != 0 gets y == reward exactly.  next_action_dev [m][2] (a'), logp_dev [m] (logp') and z_dev [m][2] may be NULL. */
+int brs_sac_td_target(brs_ddpg*, const float* actor_dev, const float* critics_target_dev, int32_t m, const float* next_obs_dev,
+                      const float* reward_dev, const uint8_t* done_dev, float gamma, uint64_t seed, uint32_t draw, float* y_dev,
+                      float* next_action_dev, float* logp_dev, float* z_dev, void* stream);
+/* A handle of the brs_ddpg_learner family with room for the SAC calls below: every brs_ddpg_learner_* call works on it, and the
+ * handles of brs_ddpg_learner_create / _create_twin stay as they are.  The SAC calls refuse any other handle. */
+int brs_ddpg_learner_create_sac(int32_t device, int32_t max_batch, brs_ddpg_learner** out);
+/* SB3's critic_loss = 0.5 (mse(Q1, y) + mse(Q2, y)): brs_ddpg_learner_twin_critic_grad's buffer with every parameter block and the
+ * two loss statistics multiplied by 0.5 (exactly: a power of two at the loss head); the two mean Q stay. */
+int brs_sac_twin_critic_grad(brs_ddpg_learner*, const float* critics_dev, int32_t m, const float* obs_dev, const float* act_dev,
+                             const float* y_dev, float* grad_dev, void* stream);
+/* grad_dev[BRS_SAC_NACTOR + 1 + BRS_SAC_NSTAT]: the gradient of La = mean_i (alpha logp_i - min(Q1, Q2)(s_i, a_i)) in the SAC
+ * actor's flat order, a_i sampled with row i's z from Philox4x32-10(counter = (draw, BRS_SAC_TAG_PI, i, 0), key = seed), through
+ * both critics (which get no gradient; per row the smaller Q takes it, critic 0 on a tie); element BRS_SAC_NACTOR:
+ * learn_alpha != 0 ? -(mean logp + target_entropy) : 0, SB3's ent_coef_loss differentiated by log_ent_coef, so that one
+ * brs_ddpg_learner_apply with n_param = BRS_SAC_NACTOR + 1 steps the actor and the temperature (a zero gradient leaves an element
+ * of Adam at zero moments unchanged); then La, mean logp, mean min Q and alpha. */
+int brs_sac_actor_grad(brs_ddpg_learner*, const float* actor_dev, const float* critics_dev, int32_t m, const float* obs_dev, uint64_t seed,
+                       uint32_t draw, int32_t learn_alpha, float target_entropy, float* grad_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""What SAC costs on the device, the measurements that end up in profiles/sac_kernel_stats.json (each mode adds its
+section to --out), the profiler off.  The method is tools/td3_kernel_time.py's: a warm-up of 10, three repeats of --calls, the sides
+alternating in the same process, medians and all repeats written down, the build id in the file, m = 256 and m = 8,192.
+
+  --kernels  (a) brs_sac_td_target against torch's target of tools/train_sac_torch.py, next to brs_td3_td_target;
+             (b) brs_sac_actor_grad against brs_ddpg_learner_actor_grad (the expected extra: one critic forward and backward);
+             (c) the whole update against torch's gradient_step on the same tensors
+  --wall     (d) DESIGN.md 7.5's run with the SAC tool: Env01-v1, --envs envs, --steps env steps, one update of batch 256 per step,
+             torch, then --device-data, then --device-data --device-learner, after a 20-step warm-up run
+  --train    (e) one run as found: --train-envs envs x --train-steps steps on the device path, then 64 evaluation episodes,
+             deterministic
+      python3 tools/sac_kernel_time.py --kernels --wall --train --out profiles/sac_kernel_stats.json
+"""
+import argparse, os, statistics, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from ddpg_learner_kernel_time import _alternate, _emit  # noqa: E402
+from td3_kernel_time import _sides  # noqa: E402
+GAMMA = 0.99
+
+
+def kernels(calls):
+    import torch
+    import train_sac_torch as T
+    import train_td3_torch as T3
+    from balance_robot_mujoco_rl_amd import DeviceDDPGLearner, DeviceSACLearner, DeviceSACNets
+    from balance_robot_mujoco_rl_amd.offpolicy import NCRITIC
+    dev = torch.device("cuda", 0)
+    res = {"calls_per_repeat": calls, "repeats": 3, "warmup": 10, "units": "microseconds per call", "sizes": {}}
+    nets = DeviceSACNets(device=0, seed=0)
+    for m in (256, 8192):
+        gen = torch.Generator(device=dev); gen.manual_seed(m)
+        scale = torch.tensor([1.5, 4.0, 0.5, 0.5, 0.5, 0.5], device=dev)
+        obs, next_obs = (torch.randn((m, 6), generator=gen, device=dev) * scale for _ in range(2))
+        act = torch.rand((m, 2), generator=gen, device=dev) * 2 - 1
+        y, reward = torch.randn(m, generator=gen, device=dev), torch.randn(m, generator=gen, device=dev)
+        done = (torch.arange(m, device=dev) % 3 == 1).to(torch.uint8)
+        t_model, d_model, td3 = T.SAC(dev, seed=0), T.SAC(dev, seed=0), T3.TD3(dev, seed=0)   # the same initial weights, one set per side
+        f, f3 = d_model.flat, td3.flat
+        sac, single = DeviceSACLearner(device=0, max_batch=m), DeviceDDPGLearner(device=0, max_batch=m)
+        y_out, draw = torch.empty(m, device=dev), [0]
+
+        def sac_target():
+            nets.sac_target(f["actor"], f["critics_target"], next_obs, reward, done, GAMMA, draw[0], out=y_out)
+            draw[0] += 1
+
+        def td3_target():
+            nets.td3_target(f3["actor_target"], f3["critics_target"], next_obs, reward, done, GAMMA, 0.2, 0.5, draw[0], out=y_out)
+            draw[0] += 1
+
+        def sac_actor_grad():
+            sac.actor_grad(f["actor"], f["critics"], obs, draw[0])
+            draw[0] += 1
+
+        def device_step():
+            sac.step(f, obs, act, y, draw[0])
+            draw[0] += 1
+        a = _alternate(torch, {"torch_target": lambda: t_model.td_target_torch(next_obs, reward, done, GAMMA), "sac_target": sac_target,
+                               "td3_target": td3_target}, calls)
+        b = _alternate(torch, {"sac_actor_grad": sac_actor_grad,
+                               "ddpg_actor_grad": lambda: single.actor_grad(f3["actor"], f3["critics"][:NCRITIC], obs)}, calls)
+        c = _alternate(torch, {"torch_update": lambda: t_model.gradient_step(obs, act, y), "device_update": device_step}, calls)
+        ma, mb, mc = ({k: statistics.median(v) for k, v in t.items()} for t in (a, b, c))
+        res["sizes"][f"m{m}"] = dict(
+            target=dict(**_sides(a), torch_over_sac=round(ma["torch_target"] / ma["sac_target"], 2), sac_minus_td3_us=round(ma["sac_target"] - ma["td3_target"], 2)),
+            actor_grad=dict(**_sides(b), sac_minus_ddpg_us=round(mb["sac_actor_grad"] - mb["ddpg_actor_grad"], 2)),
+            update=dict(**_sides(c), torch_over_device=round(mc["torch_update"] / mc["device_update"], 2)),
+            finite=bool(all(torch.isfinite(v).all() for v in list(f.values()) + list(t_model.flat.values()))))
+        sac.close(); single.close()
+    nets.close()
+    return res
+
+
+def _run(mode, envs, steps, seed=0, eval_episodes=0):
+    import torch
+    import train_sac_torch as T
+    from balance_robot_mujoco_rl_amd import BatchedSim, DeviceSACLearner, EpisodeMonitor
+    sim = BatchedSim("Env01-v1", envs, device=0, seed=seed, auto_reset=True)
+    model = T.SAC(sim.device, seed=seed)
+    mon = EpisodeMonitor(envs, device=0, max_len=int(sim.max_episode_steps))
+    cap = max(1, 1_000_000 // envs)
+    data = T.SACTorchData(sim, model, cap, 0.0, seed) if mode == "torch" else T.SACDeviceData(sim, model, cap, seed)
+    learner = DeviceSACLearner(device=0, max_batch=256, seed=seed) if mode == "device_data_device_learner" else None
+    log = {}
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    updates = T.train(sim, model, data, steps, batch=256, learning_starts=100, gamma=GAMMA, gradient_steps=1, train_freq=1, monitor=mon, log=log,
+                      learner=learner)
+    torch.cuda.synchronize(); wall = time.perf_counter() - t0
+    s = mon.stats()
+    out = dict(mode=mode, envs=envs, steps=steps, updates=updates, wall_s=round(wall, 3), env_steps_per_s=round(steps * envs / wall),
+               train_episodes=s.episodes, train_mean_len=s.mean_len, **log, finite=bool(all(torch.isfinite(v).all() for v in model.flat.values())))
+    if eval_episodes:
+        out["eval_episodes"] = eval_episodes
+        out["eval_mean_return"], out["eval_std_return"], out["eval_mean_len"] = T.evaluate("Env01-v1", model, eval_episodes, 64, mode != "torch")
+    if learner is not None:
+        learner.close()
+    mon.close(); sim.close()
+    return out
+
+
+def wall(envs, steps):
+    res = {"recipe": f"Env01-v1, {envs} envs, {steps} env steps, one SAC update of batch 256 per env step (ent_coef auto, target_entropy -2), "
+                     "SB3's defaults otherwise", "runs": []}
+    _run("device_data_device_learner", envs, 20)   # warm-up: library load, first launches, allocator
+    for mode in ("torch", "device_data", "device_data_device_learner"):
+        res["runs"].append(_run(mode, envs, steps))
+    base = res["runs"][0]["env_steps_per_s"]
+    res["over_torch_env_steps_per_s"] = {r["mode"]: round(r["env_steps_per_s"] / base, 2) for r in res["runs"][1:]}
+    return res
+
+
+def train(envs, steps):
+    return {"recipe": f"Env01-v1, {envs} envs x {steps} env steps on the device path, nothing tuned, then 64 evaluation episodes with "
+                      "deterministic=True (an episode lasts at most 6,000 steps)", "run": _run("device_data_device_learner", envs, steps, eval_episodes=64)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kernels", action="store_true"); ap.add_argument("--wall", action="store_true"); ap.add_argument("--train", action="store_true")
+    ap.add_argument("--calls", type=int, default=200); ap.add_argument("--envs", type=int, default=16384); ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--train-envs", type=int, default=256); ap.add_argument("--train-steps", type=int, default=2000)
+    ap.add_argument("--out", default="", help="JSON file to add this mode's section to")
+    a = ap.parse_args()
+    if a.kernels:
+        _emit("kernels", kernels(a.calls), a.out)
+    if a.wall:
+        _emit("wall", wall(a.envs, a.steps), a.out)
+    if a.train:
+        _emit("train", train(a.train_envs, a.train_steps), a.out)
+
+
+if __name__ == "__main__":
+    main()
