@@ -173,7 +173,9 @@ __global__ void __launch_bounds__(POLICY_THREADS) policy_act_kernel(const float*
     const float ls = w[OFF_LOGSTD + k];
     const float a = fmaf(expf(ls), z[k], mean[k]);
     action[(size_t)ACT * i + k] = a;
-    action_clipped[(size_t)ACT * i + k] = fminf(1.0f, fmaxf(-1.0f, a));
+    // fminf / fmaxf drop a NaN operand: a NaN action would leave here as -1 and the simulator's bad-state guard, which resets
+    // a lane that is handed a NaN action, would never see it.  np.clip (what SB3 applies) keeps the NaN; this unit is IEEE
+    action_clipped[(size_t)ACT * i + k] = a != a ? a : fminf(1.0f, fmaxf(-1.0f, a));
     lp += -0.5f * z[k] * z[k] - ls - 0.9189385332046727f;  // log N(a; mean, exp(ls)) with (a - mean) / sigma = z
     if (noise) noise[(size_t)ACT * i + k] = z[k];
   }

@@ -77,7 +77,8 @@ int brs_policy_set_weights(brs_policy*, const float* params_host);
 int brs_policy_use_device_weights(brs_policy*, const float* params_dev);
 
 /* one policy step for n envs: action[n][2] (unclipped sample, what the rollout buffer stores), action_clipped[n][2]
- * (clipped to [-1, 1], what brs_step consumes), logp[n], value[n]; noise[n][2] (the standard normals used) may be NULL.
+ * (clipped to [-1, 1], what brs_step consumes; a NaN action stays NaN, like np.clip, so that brs_step's bad-state guard
+ * sees it), logp[n], value[n]; noise[n][2] (the standard normals used) may be NULL.
  * deterministic != 0: action = mean (SB3 predict(deterministic=True)); logp is then that of the mean. */
 int brs_policy_act(brs_policy*, int32_t n, const float* obs_dev, uint64_t seed, int64_t env_index_base, uint32_t step,
                    int32_t deterministic, float* action_dev, float* action_clipped_dev, float* logp_dev, float* value_dev,
