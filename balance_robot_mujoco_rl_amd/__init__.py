@@ -14,6 +14,8 @@ include/brs.h (libbrs_hip.so).  This package is the host-side mirror of the refe
                                            accumulated by a HIP kernel per env step (include/brs_policy.h: brs_monitor_*)
     learner.DevicePPOLearner               SB3's PPO.train() minibatch body -- clipped-surrogate gradient, clip_grad_norm_, Adam -- as HIP
                                            kernels (include/brs_policy.h: brs_learner_*): the learner side of sb_rl.py:552-556
+    learner.DeviceA2CLearner               SB3's A2C.train() -- one -adv log pi gradient over the whole rollout, clip_grad_norm_,
+                                           RMSpropTFLike -- on the same handle (include/brs_policy.h: brs_a2c_*): sb_rl.py's `-a A2C`
     offpolicy.DeviceDDPGNets / DeviceReplayBuffer / DeviceOffPolicyCollector
                                            SB3's DDPG between two gradient steps -- actor with action noise, replay buffer with the
                                            terminal-observation and time-limit rules, uniform sampling, TD targets -- as HIP kernels
@@ -34,7 +36,7 @@ include/brs.h (libbrs_hip.so).  This package is the host-side mirror of the refe
 There is no CPU fallback: creating a sim without a HIP device raises.
 """
 from .registry import ENV_SPECS, make_vec, spec  # noqa: F401
-from .learner import DevicePPOLearner, LearnerStats  # noqa: F401
+from .learner import DeviceA2CLearner, DevicePPOLearner, LearnerStats  # noqa: F401
 from .offpolicy import (DeviceDDPGLearner, DeviceDDPGNets, DeviceOffPolicyCollector, DeviceReplayBuffer, DeviceSACLearner,  # noqa: F401
                         DeviceSACNets, DeviceTD3Learner, flatten_ddpg_state_dict, flatten_sac_actor, flatten_td3_critics,
                         unflatten_ddpg_state_dict, unflatten_sac_actor, unflatten_td3_critics)
@@ -43,7 +45,7 @@ from .quant import REFERENCE_CALIBRATION, QuantModel, QuantPolicy, quantize_poli
 from .sim import BatchedSim, BrsError  # noqa: F401
 from .vec_env import BalanceVecEnv  # noqa: F401
 
-__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "DeviceDDPGLearner", "DeviceDDPGNets", "DeviceOffPolicyCollector", "DevicePPOLearner", "DeviceReplayBuffer", "DeviceSACLearner", "DeviceSACNets", "DeviceTD3Learner", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "LearnerStats",
+__all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "DeviceA2CLearner", "DeviceDDPGLearner", "DeviceDDPGNets", "DeviceOffPolicyCollector", "DevicePPOLearner", "DeviceReplayBuffer", "DeviceSACLearner", "DeviceSACNets", "DeviceTD3Learner", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "LearnerStats",
            "QuantModel", "QuantPolicy",
            "REFERENCE_CALIBRATION", "episode_count_targets", "evaluate_policy", "flatten_ddpg_state_dict", "flatten_sac_actor", "flatten_td3_critics", "make_vec", "quantize_policy", "spec",
            "unflatten_ddpg_state_dict", "unflatten_sac_actor", "unflatten_td3_critics"]

@@ -71,6 +71,12 @@ class BrsPpoConfig(C.Structure):
                [(k, C.c_int32) for k in ("normalize_adv", "actor_on", "joint_norm")]
 
 
+class BrsA2cConfig(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("lr", "alpha", "eps")] + \
+               [(k, C.c_float) for k in ("vf_coef", "ent_coef", "max_grad_norm_pi", "max_grad_norm_vf", "ret_scale")] + \
+               [(k, C.c_int32) for k in ("normalize_adv", "actor_on", "joint_norm")]
+
+
 class BrsAdamConfig(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("lr", "beta1", "beta2", "eps")]
 
@@ -185,6 +191,8 @@ SIGNATURES = {
         "brs_learner_grad": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(BrsPpoConfig), _vp, _vp]),
         "brs_learner_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(BrsPpoConfig), _vp]),
         "brs_learner_stats": (C.c_int, [_vp, C.POINTER(BrsLearnerInfo), _vp]),
+        "brs_a2c_grad": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(BrsA2cConfig), _vp, _vp]),
+        "brs_a2c_apply": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(BrsA2cConfig), _vp]),
         "brs_ddpg_create": (C.c_int, [_i32, C.POINTER(_vp)]),
         "brs_ddpg_destroy": (C.c_int, [_vp]),
         "brs_ddpg_last_error": (C.c_char_p, [_vp]),

@@ -18,6 +18,9 @@
 //   learner_apply_kernel   one workgroup of 1,024: the two squared norms (fold + tree of fixed pairing, fp64), the clip scale,
 //                          the KL early stop and the Adam step.  The norms are taken here, after a data-parallel caller's
 //                          all-reduce of grad_dev, because that is the gradient torch's clip_grad_norm_ would see.
+//   learner_a2c_grad_kernel, learner_rmsprop_apply_kernel   SB3's A2C.train() on the same handle: the gradient kernel
+//                          with -adv log pi in the actor's head and rows 0..m-1 where idx is null; the clip scale, then RMSpropTFLike.
+//                          The value loss keeps critic_head's 0.5 d^2: SB3's vf_coef = 0.5 on mse_loss is vf_coef = 1.0 here.
 // Padding: a lane past m (or with an index outside the buffer) feeds zero observations and its dz3 is zero, it is left out of
 // the stats, the advantage statistics and the 1 / m.  No floating-point atomic, no communication between workgroups.
 #include <hip/hip_runtime.h>
@@ -285,7 +288,7 @@ __global__ void __launch_bounds__(ADV_THREADS) learner_adv_kernel(const float* _
   __shared__ double S[ADV_THREADS], SS[ADV_THREADS];
   const int t = threadIdx.x;
   double s, ss;
-  fold_adv(adv, idx, m, n_rows, t, s, ss);
+  fold_adv_rows(adv, idx, m, n_rows, t, s, ss);  // idx null (A2C): the buffer's first m rows
   S[t] = s; SS[t] = ss;
   __syncthreads();
   for (int k = ADV_THREADS / 2; k >= 1; k >>= 1) {
@@ -360,6 +363,73 @@ __global__ void __launch_bounds__(GRAD_THREADS) learner_grad_kernel(const float*
   if (tid < NACC) row_out[OFF_LOGSTD + tid] = P[tid * GRAD_THREADS];  // log_std[2], then the stats and the bad-index count: ROW's order
 }
 
+// A2C: learner_grad_kernel with a2c_actor_head in the actor's lambda -- no logp_old -- and the rows taken through
+// row_at (idx null: the whole buffer in its own order).  Grid, chunks, LDS images, partial row and the final tree are the same.
+__global__ void __launch_bounds__(GRAD_THREADS) learner_a2c_grad_kernel(const float* __restrict__ w, const int n_rows, const float* __restrict__ obs,
+                                                                        const float* __restrict__ act, const float* __restrict__ adv,
+                                                                        const float* __restrict__ ret, const int32_t* __restrict__ idx, const int m,
+                                                                        const brs_a2c_config cfg, const float* __restrict__ adv_stat,
+                                                                        float* __restrict__ partial) {
+  __shared__ float Lw[T_SIZE], P[PQ_SIZE], Q[PQ_SIZE], R[R_SIZE];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31;
+  const int nchunks = (m + CHUNK - 1) / CHUNK;
+  const float inv_m = 1.0f / (float)m;
+  const float adv_mean = cfg.normalize_adv ? adv_stat[0] : 0.0f, adv_denom = cfg.normalize_adv ? adv_stat[1] : 1.0f;
+  const float log_std[ACT] = {w[OFF_LOGSTD], w[OFF_LOGSTD + 1]};
+  const brs_ppo_config critic_cfg = shared_fields(cfg);
+  TowerSums pi, vf;
+  zero(pi); zero(vf);
+  float acc[NACC];
+#pragma unroll
+  for (int k = 0; k < NACC; k++) acc[k] = 0.0f;
+  for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {  // uniform over the workgroup
+    const int base = chunk * CHUNK + wave * 64;
+    float x[2][OBS];
+#pragma unroll
+    for (int nt = 0; nt < 2; nt++) {
+      const int e = base + 32 * nt + c;
+      const int32_t row = e < m ? row_at(idx, e) : -1;
+      const bool ok = row >= 0 && row < n_rows;
+#pragma unroll
+      for (int k = 0; k < OBS; k++) x[nt][k] = ok ? obs[(size_t)OBS * row + k] : 0.0f;
+    }
+    const int i = base + lane;
+    const int32_t row = i < m ? row_at(idx, i) : -1;
+    const bool valid = row >= 0 && row < n_rows;
+    if (i < m && !valid) acc[ACT + NSTAT] += 1.0f;
+    tower_chunk<ACT>(w + OFF_PI, Lw, P, Q, R, x, pi, [&](const float (&mean)[ACT], float (&d3)[ACT]) {
+      ActorHead hd = zero_actor_head();
+      if (valid) {
+        const float a[ACT] = {act[(size_t)ACT * row], act[(size_t)ACT * row + 1]};
+        hd = a2c_actor_head(mean, log_std, a, (adv[row] - adv_mean) / adv_denom, cfg, inv_m);
+      }
+      d3[0] = hd.dmean[0]; d3[1] = hd.dmean[1];
+      acc[0] += hd.dlog_std[0]; acc[1] += hd.dlog_std[1];
+      acc[ACT + S_PL] += hd.pl; acc[ACT + S_ENT] += hd.ent;  // the KL and clip-fraction sums stay zero
+    });
+    tower_chunk<1>(w + OFF_VF, Lw, P, Q, R, x, vf, [&](const float (&v)[1], float (&d3)[1]) {
+      CriticHead hd = {0.0f, 0.0f};
+      if (valid) hd = critic_head(v[0], ret[row], critic_cfg, inv_m);
+      d3[0] = hd.dvalue;
+      acc[ACT + S_VL] += hd.vl;
+    });
+  }
+  float* row_out = partial + (size_t)blockIdx.x * ROW;
+  store_tower<ACT>(row_out + OFF_PI, pi);
+  store_tower<1>(row_out + OFF_VF, vf);
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < NACC; k++) P[k * GRAD_THREADS + tid] = acc[k];
+  __syncthreads();
+  for (int s = GRAD_THREADS / 2; s >= 1; s >>= 1) {
+    if (tid < s)
+#pragma unroll
+      for (int k = 0; k < NACC; k++) P[k * GRAD_THREADS + tid] += P[k * GRAD_THREADS + tid + s];
+    __syncthreads();
+  }
+  if (tid < NACC) row_out[OFF_LOGSTD + tid] = P[tid * GRAD_THREADS];
+}
+
 __global__ void __launch_bounds__(256) learner_reduce_kernel(const float* __restrict__ partial, const int G, float* __restrict__ grad,
                                                              brs_learner_info* __restrict__ info) {
   const int col = blockIdx.x * 256 + threadIdx.x;
@@ -399,6 +469,36 @@ __global__ void __launch_bounds__(APPLY_THREADS) learner_apply_kernel(float* __r
     float p = params[i], mi = m[i], vi = v[i];
     adam_update(p, mi, vi, grad[i] * param_scale(i, norm_pi, norm_vf, cfg), a);
     params[i] = p; m[i] = mi; v[i] = vi;
+  }
+}
+
+// A2C's optimiser step: learner_apply_kernel's norms and clip scale, then RMSpropTFLike.  No early stop: `stopped` is not touched.
+__global__ void __launch_bounds__(APPLY_THREADS) learner_rmsprop_apply_kernel(float* __restrict__ params, const float* __restrict__ grad,
+                                                                              float* __restrict__ sq, const brs_a2c_config cfg,
+                                                                              brs_learner_info* __restrict__ info) {
+  __shared__ double SP[APPLY_THREADS], SV[APPLY_THREADS];
+  const int t = threadIdx.x;
+  double sp, sv;
+  fold_squares(grad, t, sp, sv);
+  SP[t] = sp; SV[t] = sv;
+  __syncthreads();
+  for (int k = APPLY_THREADS / 2; k >= 1; k >>= 1) {
+    if (t < k) { SP[t] += SP[t + k]; SV[t] += SV[t + k]; }
+    __syncthreads();
+  }
+  const brs_ppo_config clip_cfg = shared_fields(cfg);
+  float norm_pi, norm_vf;
+  norms(SP[0], SV[0], clip_cfg, norm_pi, norm_vf);
+  if (t == 0) {
+    info->steps = info->steps + 1;
+    for (int k = 0; k < NSTAT; k++) info->stat[k] = grad[NPARAM + k];
+    info->grad_norm_pi = norm_pi; info->grad_norm_vf = norm_vf;
+  }
+  const RmspropScalars r = rmsprop_scalars(cfg);
+  for (int i = t; i < NPARAM; i += APPLY_THREADS) {
+    float p = params[i], s = sq[i];
+    rmsprop_tf_update(p, s, grad[i] * param_scale(i, norm_pi, norm_vf, clip_cfg), r);
+    params[i] = p; sq[i] = s;
   }
 }
 
@@ -494,6 +594,39 @@ int brs_learner_apply(brs_learner* l, float* params_dev, const float* grad_dev, 
   DeviceGuard g(l->device);
   if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_learner_apply: hipSetDevice failed");
   hipLaunchKernelGGL(learner_apply_kernel, dim3(1), dim3(APPLY_THREADS), 0, (hipStream_t)stream, params_dev, grad_dev, m_dev, v_dev, *cfg, l->info);
+  BRS_HIP_TRY(l, hipGetLastError());
+  return BRS_OK;
+}
+
+int brs_a2c_grad(brs_learner* l, const float* params_dev, int32_t n_rows, const float* obs_dev, const float* act_dev, const float* adv_dev,
+                 const float* ret_dev, const int32_t* idx_dev, int32_t m, const brs_a2c_config* cfg, float* grad_dev, void* stream) {
+  if (!cfg) return fail(l, BRS_ERR_ARG, "brs_a2c_grad: null config");
+  if (m < 1) return fail(l, BRS_ERR_ARG, "brs_a2c_grad: an update needs at least one sample");
+  if (cfg->normalize_adv && m < 2) return fail(l, BRS_ERR_ARG, "brs_a2c_grad: normalize_adv needs at least two samples (unbiased std)");
+  if (!idx_dev && m > n_rows) return fail(l, BRS_ERR_ARG, "brs_a2c_grad: null idx takes rows 0..m-1, m must not exceed n_rows");
+  if (!(cfg->ret_scale > 0.0f)) return fail(l, BRS_ERR_ARG, "brs_a2c_grad: ret_scale must be positive");
+  if (!l) return fail<brs_learner>(nullptr, BRS_ERR_ARG, "brs_a2c_grad: null handle");
+  if (n_rows <= 0 || !params_dev || !obs_dev || !act_dev || !adv_dev || !ret_dev || !grad_dev)
+    return fail(l, BRS_ERR_ARG, "brs_a2c_grad: bad argument");
+  DeviceGuard g(l->device);
+  if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_a2c_grad: hipSetDevice failed");
+  hipStream_t s = (hipStream_t)stream;
+  const int nchunks = (m + CHUNK - 1) / CHUNK, G = nchunks < l->max_workgroups ? nchunks : l->max_workgroups;
+  if (cfg->normalize_adv) hipLaunchKernelGGL(learner_adv_kernel, dim3(1), dim3(ADV_THREADS), 0, s, adv_dev, idx_dev, m, n_rows, l->adv_stat);
+  hipLaunchKernelGGL(learner_a2c_grad_kernel, dim3(G), dim3(GRAD_THREADS), 0, s, params_dev, n_rows, obs_dev, act_dev, adv_dev, ret_dev, idx_dev,
+                     m, *cfg, l->adv_stat, l->partial);
+  hipLaunchKernelGGL(learner_reduce_kernel, dim3((ROW + 255) / 256), dim3(256), 0, s, l->partial, G, grad_dev, l->info);
+  BRS_HIP_TRY(l, hipGetLastError());
+  return BRS_OK;
+}
+
+int brs_a2c_apply(brs_learner* l, float* params_dev, const float* grad_dev, float* sq_dev, const brs_a2c_config* cfg, void* stream) {
+  if (!cfg) return fail(l, BRS_ERR_ARG, "brs_a2c_apply: null config");
+  if (!l) return fail<brs_learner>(nullptr, BRS_ERR_ARG, "brs_a2c_apply: null handle");
+  if (!params_dev || !grad_dev || !sq_dev) return fail(l, BRS_ERR_ARG, "brs_a2c_apply: null argument");
+  DeviceGuard g(l->device);
+  if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_a2c_apply: hipSetDevice failed");
+  hipLaunchKernelGGL(learner_rmsprop_apply_kernel, dim3(1), dim3(APPLY_THREADS), 0, (hipStream_t)stream, params_dev, grad_dev, sq_dev, *cfg, l->info);
   BRS_HIP_TRY(l, hipGetLastError());
   return BRS_OK;
 }

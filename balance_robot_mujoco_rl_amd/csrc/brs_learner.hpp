@@ -1,4 +1,4 @@
-// brs_learner.hpp -- the PPO learner of include/brs_policy.h, the part shared by the HIP kernels
+// brs_learner.hpp -- the PPO learner of include/brs_policy.h and the A2C learner on the same handle (7.9), the part shared by the HIP kernels
 // (brs_learner.hip) and the host build the CPU tests hold against fp64 torch autograd (tests/learnerhost): everything that is
 // not a matrix product -- the per-sample loss heads, the order in which partial sums are combined, the clip scale and the Adam
 // update.  The towers themselves are MFMA code in the kernels and plain loops in the host build.
@@ -80,6 +80,44 @@ BRS_HD CriticHead critic_head(float value, float ret, const brs_ppo_config& c, f
   return CriticHead{c.vf_coef * d * inv_m, 0.5f * d * d * inv_m};
 }
 
+// ---- A2C: SB3's A2C.train() on the same towers.  policy loss = -adv_n log pi(a | s), no ratio and no clip, so
+// there is no logp_old, and the KL and clip-fraction slots of the stats stay zero.  The value loss is critic_head's, the
+// convention PPO uses: vf_coef * 0.5 (v - ret / ret_scale)^2 -- SB3's vf_coef = 0.5 on mse_loss is vf_coef = 1.0 here.
+template <class Config>  // brs_a2c_config: anything with actor_on and ent_coef
+BRS_HD ActorHead a2c_actor_head(const float mean[ACT], const float log_std[ACT], const float act[ACT], float adv_n, const Config& c,
+                                float inv_m) {
+  ActorHead o;
+  float z[ACT], inv_sigma[ACT], lp = 0.0f, ent = 0.0f;
+  for (int k = 0; k < ACT; k++) {
+    inv_sigma[k] = expf(-log_std[k]);
+    z[k] = (act[k] - mean[k]) * inv_sigma[k];
+    lp += -0.5f * z[k] * z[k] - log_std[k] - 0.9189385332046727f;
+    ent += 1.4189385332046727f + log_std[k];
+  }
+  o.pl = -adv_n * lp * inv_m;
+  o.ent = ent * inv_m;
+  o.kl = 0.0f;
+  o.clipfrac = 0.0f;
+  const float g_lp = c.actor_on ? -adv_n * inv_m : 0.0f;
+  for (int k = 0; k < ACT; k++) {
+    if (c.actor_on) {
+      o.dmean[k] = g_lp * z[k] * inv_sigma[k];
+      o.dlog_std[k] = g_lp * (z[k] * z[k] - 1.0f) - c.ent_coef * inv_m;
+    } else {
+      o.dmean[k] = 0.0f;
+      o.dlog_std[k] = 0.0f;
+    }
+  }
+  return o;
+}
+// what critic_head, norms and param_scale read of a config, for brs_a2c_config's callers
+BRS_HD brs_ppo_config shared_fields(const brs_a2c_config& c) {
+  brs_ppo_config p = {};
+  p.vf_coef = c.vf_coef; p.ent_coef = c.ent_coef; p.max_grad_norm_pi = c.max_grad_norm_pi; p.max_grad_norm_vf = c.max_grad_norm_vf;
+  p.ret_scale = c.ret_scale; p.normalize_adv = c.normalize_adv; p.actor_on = c.actor_on; p.joint_norm = c.joint_norm;
+  return p;
+}
+
 BRS_HD ActorHead zero_actor_head() { return ActorHead{{0.0f, 0.0f}, {0.0f, 0.0f}, 0.0f, 0.0f, 0.0f, 0.0f}; }
 
 // ---- advantage mean and std of the minibatch: thread t of ADV_THREADS folds entries t, t + ADV_THREADS, ... in ascending
@@ -88,6 +126,18 @@ BRS_HD void fold_adv(const float* adv, const int32_t* idx, int m, int n_rows, in
   s = 0.0; ss = 0.0;
   for (int i = t; i < m; i += ADV_THREADS) {
     const int32_t row = idx[i];
+    if (row < 0 || row >= n_rows) continue;
+    const double a = (double)adv[row];
+    s += a; ss += a * a;
+  }
+}
+// entry i of a minibatch: row idx[i], or row i of the buffer when the minibatch is the whole buffer in its own order (idx null)
+BRS_HD int32_t row_at(const int32_t* idx, int i) { return idx ? idx[i] : (int32_t)i; }
+// fold_adv with the rows taken through row_at: the same sums in the same order where idx is not null
+BRS_HD void fold_adv_rows(const float* adv, const int32_t* idx, int m, int n_rows, int t, double& s, double& ss) {
+  s = 0.0; ss = 0.0;
+  for (int i = t; i < m; i += ADV_THREADS) {
+    const int32_t row = row_at(idx, i);
     if (row < 0 || row >= n_rows) continue;
     const double a = (double)adv[row];
     s += a; ss += a * a;
@@ -146,6 +196,21 @@ BRS_HD void adam_update(float& p, float& m, float& v, float g, const AdamScalars
   v = v * a.beta2 + a.w2 * g * g;                   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
   const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
   p = p - a.step_size * (m / denom);                // param.addcdiv_(exp_avg, denom, value=-step_size)
+}
+
+// ---- SB3's RMSpropTFLike (alpha, eps; no momentum, not centered, no weight decay): square_avg starts at ONE and epsilon sits
+// INSIDE the root -- the two points where it leaves torch.optim.RMSprop.  lr, alpha and eps are rounded to fp32 once
+struct RmspropScalars {
+  float lr, alpha, w, eps;
+};
+template <class Config>  // brs_a2c_config: anything with lr, alpha, eps in fp64
+BRS_HD RmspropScalars rmsprop_scalars(const Config& c) {
+  return RmspropScalars{(float)c.lr, (float)c.alpha, (float)(1.0 - c.alpha), (float)c.eps};
+}
+BRS_HD void rmsprop_tf_update(float& p, float& sq, float g, const RmspropScalars& s) {
+  sq = sq * s.alpha + s.w * g * g;        // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+  const float avg = sqrtf(sq + s.eps);    // square_avg.add(eps).sqrt_()
+  p = p - s.lr * (g / avg);               // param.addcdiv_(grad, avg, value=-lr)
 }
 
 // the tree both reductions use: partial t takes partial t + s for s = n / 2, n / 4, ... 1 (n a power of two)

@@ -4,7 +4,9 @@ The reference calls `model.learn` (src/sb_rl.py:552-556) and SB3's PPO.train() t
 actor/critic forward, clipped surrogate + value loss + entropy bonus, backward, clip_grad_norm_, Adam.  On a 9,413-parameter
 network that is several dozen launch-bound torch kernels per optimiser step.  `DevicePPOLearner` does one optimiser step in four
 HIP kernels (advantage statistics, gradient, reduce, clip + Adam) on the rollout's own tensors; PyTorch owns the parameter vector,
-Adam's moments and the stream, and can all-reduce the gradient buffer between grad() and apply()."""
+Adam's moments and the stream, and can all-reduce the gradient buffer between grad() and apply().
+
+`DeviceA2CLearner` is SB3's A2C.train() on the same handle: one step on the whole rollout, RMSpropTFLike for Adam."""
 import ctypes as C
 import dataclasses
 
@@ -77,14 +79,10 @@ class LearnerStats:
     grad_norm_vf: float
 
 
-class DevicePPOLearner:
-    """One PPO optimiser step per step(): the minibatch body of SB3's PPO.train().  `separate_clip`: clip actor + log_std and
-    critic by norms of their own (tools/train_ppo_torch.py) instead of SB3's single global norm.  `lr`, `ent_coef`, `target_kl`,
-    `ret_scale` (the unit of the critic: its target is ret / ret_scale) and `actor_on` (False: critic warm-up, the loss is
-    vf_coef x value loss) are plain attributes and may change between steps."""
+class _DeviceLearner:
+    """what the learners on a brs_learner handle share: the handle, the flat parameter vector and its conversions, the stats"""
 
-    def __init__(self, device=0, lr=3e-4, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, separate_clip=False, target_kl=None,
-                 normalize_advantage=True, max_workgroups=0, betas=(0.9, 0.999), eps=1e-8):
+    def _create(self, device, max_workgroups):
         if not torch.cuda.is_available():
             raise BrsError("no HIP device visible to PyTorch: the on-device learner has no CPU fallback")
         self.L = _lib.lib()
@@ -94,12 +92,11 @@ class DevicePPOLearner:
         if rc != 0:
             raise BrsError(f"brs_learner_create failed ({rc}): {self.L.brs_learner_last_error(None).decode()}")
         self.h = h
-        self.lr, self.clip_range, self.vf_coef, self.ent_coef = float(lr), float(clip_range), float(vf_coef), float(ent_coef)
-        self.max_grad_norm, self.separate_clip, self.target_kl = float(max_grad_norm), bool(separate_clip), target_kl
-        self.normalize_advantage, self.betas, self.eps = bool(normalize_advantage), (float(betas[0]), float(betas[1])), float(eps)
         self.ret_scale, self.actor_on = 1.0, True
-        z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.params, self.m, self.v, self.grad_buf, self._rollout = z(NPARAM), z(NPARAM), z(NPARAM), z(NPARAM + NSTAT), z(NPARAM)
+        self.params, self.grad_buf, self._rollout = self._zeros(NPARAM), self._zeros(NPARAM + NSTAT), self._zeros(NPARAM)
+
+    def _zeros(self, n):
+        return torch.zeros(n, dtype=torch.float32, device=self.device)
 
     def close(self):
         if getattr(self, "h", None):
@@ -119,17 +116,9 @@ class DevicePPOLearner:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def config(self):
-        kl = self.target_kl
-        return _lib.BrsPpoConfig(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, clip_range=self.clip_range,
-                                 vf_coef=self.vf_coef, ent_coef=self.ent_coef, max_grad_norm_pi=self.max_grad_norm,
-                                 max_grad_norm_vf=self.max_grad_norm, target_kl=0.0 if kl is None else float(kl), ret_scale=float(self.ret_scale),
-                                 normalize_adv=int(self.normalize_advantage), actor_on=int(bool(self.actor_on)),
-                                 joint_norm=int(not self.separate_clip))
-
     # ---- parameters
     def load(self, state_dict):
-        """ActorCritic (tools/train_ppo_torch.py) or SB3 MlpPolicy weights; Adam's moments and step count are kept"""
+        """ActorCritic (tools/train_ppo_torch.py) or SB3 MlpPolicy weights; the optimiser's state and step count are kept"""
         flat, self.ret_scale = flatten_state_dict(state_dict)
         self.params.copy_(torch.from_numpy(flat))
         return self
@@ -144,6 +133,36 @@ class DevicePPOLearner:
         if self.ret_scale != 1.0:
             self._rollout[CRITIC_HEAD] *= self.ret_scale
         return self._rollout
+
+    def stats(self):
+        """waits for the stream; one small copy"""
+        s = _lib.BrsLearnerInfo()
+        self._check(self.L.brs_learner_stats(self.h, C.byref(s), self._stream()), "brs_learner_stats")
+        return LearnerStats(int(s.steps), bool(s.stopped), int(s.bad_index), *[float(x) for x in s.stat], float(s.grad_norm_pi),
+                            float(s.grad_norm_vf))
+
+
+class DevicePPOLearner(_DeviceLearner):
+    """One PPO optimiser step per step(): the minibatch body of SB3's PPO.train().  `separate_clip`: clip actor + log_std and
+    critic by norms of their own (tools/train_ppo_torch.py) instead of SB3's single global norm.  `lr`, `ent_coef`, `target_kl`,
+    `ret_scale` (the unit of the critic: its target is ret / ret_scale) and `actor_on` (False: critic warm-up, the loss is
+    vf_coef x value loss) are plain attributes and may change between steps."""
+
+    def __init__(self, device=0, lr=3e-4, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, separate_clip=False, target_kl=None,
+                 normalize_advantage=True, max_workgroups=0, betas=(0.9, 0.999), eps=1e-8):
+        self._create(device, max_workgroups)
+        self.lr, self.clip_range, self.vf_coef, self.ent_coef = float(lr), float(clip_range), float(vf_coef), float(ent_coef)
+        self.max_grad_norm, self.separate_clip, self.target_kl = float(max_grad_norm), bool(separate_clip), target_kl
+        self.normalize_advantage, self.betas, self.eps = bool(normalize_advantage), (float(betas[0]), float(betas[1])), float(eps)
+        self.m, self.v = self._zeros(NPARAM), self._zeros(NPARAM)
+
+    def config(self):
+        kl = self.target_kl
+        return _lib.BrsPpoConfig(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, clip_range=self.clip_range,
+                                 vf_coef=self.vf_coef, ent_coef=self.ent_coef, max_grad_norm_pi=self.max_grad_norm,
+                                 max_grad_norm_vf=self.max_grad_norm, target_kl=0.0 if kl is None else float(kl), ret_scale=float(self.ret_scale),
+                                 normalize_adv=int(self.normalize_advantage), actor_on=int(bool(self.actor_on)),
+                                 joint_norm=int(not self.separate_clip))
 
     # ---- one optimiser step
     def begin_iteration(self):
@@ -175,9 +194,51 @@ class DevicePPOLearner:
         self.grad(obs, act, logp_old, adv, ret, idx)
         self.apply()
 
-    def stats(self):
-        """waits for the stream; one small copy"""
-        s = _lib.BrsLearnerInfo()
-        self._check(self.L.brs_learner_stats(self.h, C.byref(s), self._stream()), "brs_learner_stats")
-        return LearnerStats(int(s.steps), bool(s.stopped), int(s.bad_index), *[float(x) for x in s.stat], float(s.grad_norm_pi),
-                            float(s.grad_norm_vf))
+
+class DeviceA2CLearner(_DeviceLearner):
+    """SB3's A2C.train() (include/brs_policy.h: brs_a2c_*): one optimiser step per step() on the whole rollout --
+    the gradient of mean(-adv log pi(a | s)) + vf_coef x value loss - ent_coef x entropy, clip_grad_norm_, RMSpropTFLike (`alpha`,
+    `eps` inside the root; its state `sq` starts at ONES).  The defaults are SB3's, except that the value loss is the PPO learner's
+    0.5 (v - ret / ret_scale)^2: SB3's vf_coef = 0.5 on mse_loss is vf_coef = 1.0 here, and stats().value_loss is 0.5 mean(d^2).
+    The returns and advantages are DeviceRollout(n_steps=5, gae_lambda=1.0)'s.  `separate_clip`, `ret_scale`, `actor_on`: as in
+    DevicePPOLearner; every setting is a plain attribute and may change between steps."""
+
+    def __init__(self, device=0, lr=7e-4, alpha=0.99, eps=1e-5, vf_coef=1.0, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=False,
+                 separate_clip=False, ret_scale=1.0, actor_on=True, max_workgroups=0):
+        self._create(device, max_workgroups)
+        self.lr, self.alpha, self.eps, self.vf_coef, self.ent_coef = float(lr), float(alpha), float(eps), float(vf_coef), float(ent_coef)
+        self.max_grad_norm, self.normalize_advantage, self.separate_clip = float(max_grad_norm), bool(normalize_advantage), bool(separate_clip)
+        self.ret_scale, self.actor_on = float(ret_scale), bool(actor_on)
+        self.sq = torch.ones(NPARAM, dtype=torch.float32, device=self.device)
+
+    def config(self):
+        return _lib.BrsA2cConfig(lr=self.lr, alpha=self.alpha, eps=self.eps, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
+                                 max_grad_norm_pi=self.max_grad_norm, max_grad_norm_vf=self.max_grad_norm, ret_scale=float(self.ret_scale),
+                                 normalize_adv=int(self.normalize_advantage), actor_on=int(bool(self.actor_on)),
+                                 joint_norm=int(not self.separate_clip))
+
+    def grad(self, obs, act, adv, ret, idx=None, out=None):
+        """the flat rollout (obs [N, 6], act [N, 2], adv / ret [N], float32) -> gradient buffer [NPARAM + NSTAT] over all N rows in
+        buffer order, or over the rows idx [M] int32: the gradient of the mean loss, then the means of policy loss, value loss
+        and entropy and two zeros.  All-reduce and divide it for data-parallel training, then apply()"""
+        d, f32 = self.device, torch.float32
+        n = obs.shape[0]
+        m = n if idx is None else idx.shape[0]
+        _need(obs, "obs", f32, (n, 6), d); _need(act, "act", f32, (n, 2), d); _need(adv, "adv", f32, (n,), d); _need(ret, "ret", f32, (n,), d)
+        if idx is not None:
+            _need(idx, "idx", torch.int32, (m,), d)
+        out = self.grad_buf if out is None else _need(out, "grad", f32, (NPARAM + NSTAT,), d)
+        cfg = self.config()
+        self._check(self.L.brs_a2c_grad(self.h, _p(self.params), n, _p(obs), _p(act), _p(adv), _p(ret), _p(idx), m,
+                                        C.byref(cfg), _p(out), self._stream()), "brs_a2c_grad")
+        return out
+
+    def apply(self, grad=None):
+        """clip_grad_norm_ + one RMSpropTFLike step"""
+        grad = self.grad_buf if grad is None else _need(grad, "grad", torch.float32, (NPARAM + NSTAT,), self.device)
+        cfg = self.config()
+        self._check(self.L.brs_a2c_apply(self.h, _p(self.params), _p(grad), _p(self.sq), C.byref(cfg), self._stream()), "brs_a2c_apply")
+
+    def step(self, obs, act, adv, ret, idx=None):
+        self.grad(obs, act, adv, ret, idx)
+        self.apply()

@@ -15,6 +15,8 @@
  *   (with targets)        episodes of env i count and the others are ignored, target[i] = (n_eval_episodes + i) / n
  *   brs_learner_grad      PPO.train(), the body of its minibatch loop: evaluate_actions, the clipped surrogate, the value loss and
  *   brs_learner_apply     the entropy bonus, loss.backward(), clip_grad_norm_, Adam's step, and the target_kl early stop
+ *   brs_a2c_grad          A2C.train() (the CLI's `-a A2C`, src/sb_rl.py:72-83 with SB3's defaults): evaluate_actions, -adv log_prob,
+ *   brs_a2c_apply         the value loss and the entropy bonus on the whole rollout, clip_grad_norm_, RMSpropTFLike's step
  *
  * and for the reference's second algorithm, DDPG with net_arch = dict(pi=[300, 200], qf=[200, 150]) and
  * NormalActionNoise(sigma=0.1) (src/sb_rl.py:72-83), what SB3's OffPolicyAlgorithm / TD3 do between two gradient steps:
@@ -189,6 +191,35 @@ int brs_learner_apply(brs_learner*, float* params_dev, const float* grad_dev, fl
                       const brs_ppo_config* cfg, void* stream);
 /* one small device-to-host copy; waits for the stream */
 int brs_learner_stats(brs_learner*, brs_learner_info* out_host, void* stream);
+
+/* ---- A2C on the same handle: SB3's A2C.train() -- ONE optimiser step on the whole rollout, M = n_steps x n_envs
+ * rows in buffer order -- as brs_a2c_grad (the gradient of the mean of -adv log pi(a | s) + vf_coef x value loss - ent_coef x entropy)
+ * and brs_a2c_apply (clip_grad_norm_, then SB3's RMSpropTFLike).  The n-step returns and advantages are brs_gae's at lambda = 1.
+ * The value loss is the PPO learner's, 0.5 (v - ret / ret_scale)^2 per sample: SB3's vf_coef = 0.5 on mse_loss is vf_coef = 1.0 here;
+ * the reported value loss stays 0.5 mean(d^2).  Same rules as above (enqueue only, no allocation, no floating-point atomic, identical
+ * bytes from identical inputs, argument errors are BRS_ERR_ARG); brs_learner_stats serves both algorithms, `stopped` is not used. */
+typedef struct brs_a2c_config {
+  double lr, alpha, eps;       /* RMSpropTFLike: square_avg = alpha square_avg + (1 - alpha) g^2, p -= lr g / sqrt(square_avg + eps) */
+  float vf_coef;
+  float ent_coef;
+  float max_grad_norm_pi;      /* as in brs_ppo_config */
+  float max_grad_norm_vf;
+  float ret_scale;
+  int32_t normalize_adv;       /* (adv - mean) / (unbiased std + 1e-8) over the m rows; needs m >= 2 */
+  int32_t actor_on;
+  int32_t joint_norm;
+} brs_a2c_config;
+
+/* The arrays are brs_learner_grad's, without logp_old.  idx_dev NULL: rows 0..m-1 of the buffer, m <= n_rows.  m >= 1 (m >= 2
+ * with normalize_adv).  Writes grad_dev[BRS_POLICY_NPARAM + BRS_LEARNER_NSTAT]: the gradient of the mean loss, then the means of
+ * policy loss, value loss and entropy, then two zeros (the KL and clip-fraction slots).  Everything in it is a mean: a
+ * data-parallel caller all-reduces and divides it between the two calls. */
+int brs_a2c_grad(brs_learner*, const float* params_dev, int32_t n_rows, const float* obs_dev, const float* act_dev,
+                 const float* adv_dev, const float* ret_dev, const int32_t* idx_dev, int32_t m, const brs_a2c_config* cfg,
+                 float* grad_dev, void* stream);
+/* the clip scale of brs_learner_apply, then one RMSpropTFLike step on params / sq [BRS_POLICY_NPARAM] in place; a fresh optimiser's
+ * sq is all ONES.  Counts brs_learner_info.steps; there is no early stop */
+int brs_a2c_apply(brs_learner*, float* params_dev, const float* grad_dev, float* sq_dev, const brs_a2c_config* cfg, void* stream);
 
 /* ---- DDPG data path: everything SB3's DDPG does between two gradient steps.  The networks are SB3's TD3Policy
  * with the reference's net_arch, widths fixed at compile time; each is a flat fp32 device vector, torch.nn.Linear layout:
