@@ -30,7 +30,7 @@ UNITS = [("brs_kernels.hip", SIM_FLAGS, True), ("brs_policy.hip", [], True), ("b
          ("brs_ddpg_learner.hip", [], False)]
 SRC = os.path.join(_CSRC, UNITS[0][0])  # the unit that takes the A/B flags and the build id stamp
 # what the build id hashes next to the sources of its units; brs_host.hpp holds no kernel code and stays out of it
-HEADERS = [os.path.join(_CSRC, h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp")] + \
+HEADERS = [os.path.join(_CSRC, h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp", "brs_nan.hpp")] + \
           [os.path.join(_INCLUDE, h) for h in ("brs.h", "brs_policy.h")]
 
 POLICY_NPARAM = (64 * 6 + 64 + 64 * 64 + 64 + 2 * 64 + 2) + (64 * 6 + 64 + 64 * 64 + 64 + 64 + 1) + 2

@@ -44,8 +44,8 @@ inline SampleSplit sample_split(int m) {
   return SampleSplit{mp, span, nsplit};
 }
 
-// ReLU's backward gate, as torch's: the pre-activation is positive (equivalently: the ReLU's output is)
-BRS_HD bool relu_gate(float pre) { return pre > 0.0f; }
+// ReLU's backward gate, as torch's: closed where the pre-activation (equivalently: the ReLU's output) is <= 0, so open for a NaN
+BRS_HD bool relu_gate(float pre) { return relu_gate_keep_nan(pre); }
 
 // ---- the loss heads; everything carries the 1 / m of the mean, so that sums over rows are means
 struct CriticHead { float dq, loss, q; };
@@ -65,7 +65,7 @@ BRS_HD float actor_sat_share(const float* a, float inv_m) { return 0.5f * (a[0] 
 BRS_HD void tanh_with_grad(float x, float* a, float* g) {
   const float e = expf(2.0f * x), d = e + 1.0f;
   *a = 1.0f - 2.0f / d;
-  *g = e < 1e18f ? 4.0f * e / (d * d) : 0.0f;  // (e + 1)^2 overflows past 1.8e19; the factor is below 4e-18 there
+  *g = e >= 1e18f ? 0.0f : 4.0f * e / (d * d);  // (e + 1)^2 overflows past 1.8e19; the factor is below 4e-18 there.  A NaN stays
 }
 
 // ---- column `col` of G partial rows of `len` floats, summed in ascending order of the row (brs_learner.hpp's combine_rows)
@@ -126,12 +126,12 @@ template <class N> inline void forward_row_keep(const float* w, const float* x, 
   for (int u = 0; u < N::H1; u++) {
     float s = w[O::B1 + u];
     for (int k = 0; k < N::IN; k++) s = fmaf(w[O::W1 + u * N::IN + k], x[k], s);
-    t.h1[u] = relu_gate(s) ? s : 0.0f;
+    t.h1[u] = relu_keep_nan(s);
   }
   for (int u = 0; u < N::H2; u++) {
     float s = w[O::B2 + u];
     for (int k = 0; k < N::H1; k++) s = fmaf(w[O::W2 + u * N::H1 + k], t.h1[k], s);
-    t.h2[u] = relu_gate(s) ? s : 0.0f;
+    t.h2[u] = relu_keep_nan(s);
   }
   for (int u = 0; u < N::OUT; u++) {
     float s = 0.0f;

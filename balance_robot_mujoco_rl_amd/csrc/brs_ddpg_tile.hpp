@@ -112,7 +112,7 @@ __device__ __forceinline__ void forward_tile(const float* __restrict__ w, float*
   for (int mt = 0; mt < T::MT1; mt++)
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-      h1[mt][r] = fmaxf(h1[mt][r], 0.0f);
+      h1[mt][r] = relu_keep_nan(h1[mt][r]);
       keep.h1(mt, r, h1[mt][r]);
     }
   // layer 2: K = H1P walked in ACCUMULATOR order: step (ch, r) contracts the two units 32 ch + BRS_UNIT(r) of the two halves
@@ -145,7 +145,7 @@ __device__ __forceinline__ void forward_tile(const float* __restrict__ w, float*
   for (int mt = 0; mt < T::MT2; mt++)
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-      const float t = fmaxf(acc[mt][r], 0.0f);
+      const float t = relu_keep_nan(acc[mt][r]);
       keep.h2(mt, r, t);
 #pragma unroll
       for (int k = 0; k < N::OUT; k++) p[k] = fmaf(L[T::L_W3 + k * T::H2P + 32 * mt + BRS_UNIT(r)], t, p[k]);

@@ -8,6 +8,7 @@
 
 #include "../../include/brs.h"
 #include "../../include/brs_policy.h"
+#include "brs_nan.hpp"  // the selects that keep a NaN
 
 #ifndef BRS_HD
 #if defined(__HIPCC__)
@@ -50,14 +51,15 @@ BRS_HD ActorHead actor_head(const float mean[ACT], const float log_std[ACT], con
     ent += 1.4189385332046727f + log_std[k];  // 0.5 + 0.5 log(2 pi) + log sigma
   }
   const float lr = lp - logp_old, ratio = expf(lr);
-  const float clamped = fminf(fmaxf(ratio, 1.0f - c.clip_range), 1.0f + c.clip_range);
+  const float clamped = fminf(fmaxf(ratio, 1.0f - c.clip_range), 1.0f + c.clip_range);  // of a NaN ratio: a number; s1 keeps the NaN
   const float s1 = ratio * adv_n, s2 = clamped * adv_n;
-  o.pl = -fminf(s1, s2) * inv_m;
+  o.pl = -min_keep_nan(s1, s2) * inv_m;
   o.ent = ent * inv_m;
   o.kl = ((ratio - 1.0f) - lr) * inv_m;
   o.clipfrac = fabsf(ratio - 1.0f) > c.clip_range ? inv_m : 0.0f;
-  // the clamped branch has no gradient where the clamp is active, and where it is not the two branches are the same function
-  const float g_lp = (c.actor_on && s1 <= s2) ? -adv_n * ratio * inv_m : 0.0f;
+  // the clamped branch has no gradient where the clamp is active, and where it is not the two branches are the same function;
+  // a NaN on either side leaves the gate open, so that the row's NaN reaches the gradient as it reaches torch.min's
+  const float g_lp = (c.actor_on && !(s1 > s2)) ? -adv_n * ratio * inv_m : 0.0f;
   for (int k = 0; k < ACT; k++) {
     if (c.actor_on) {
       o.dmean[k] = g_lp * z[k] * inv_sigma[k];

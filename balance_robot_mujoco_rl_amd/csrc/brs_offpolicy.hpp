@@ -9,6 +9,7 @@
 #include "../../include/brs.h"
 #include "../../include/brs_policy.h"
 #include "brs_core.hpp"  // philox4x32_10, BRS_HD
+#include "brs_nan.hpp"   // the selects that keep a NaN
 
 namespace brs {
 namespace offpolicy {
@@ -51,14 +52,15 @@ BRS_HD void normal_pair(uint32_t w0, uint32_t w1, float* z) {
 // every step is exact in fp32
 BRS_HD float uniform_action(uint32_t w) { return (float)((int32_t)(w >> 8) - 8388608) * (1.0f / 8388608.0f); }
 
-// SB3 _sample_action: clip(mean + sigma z, -1, 1); a product and a sum, on the device as on the host
+// SB3 _sample_action: clip(mean + sigma z, -1, 1); a product and a sum, on the device as on the host; a NaN mean stays a NaN
+// (np.clip), so that the simulator's bad-state guard sees it
 BRS_HD float noisy_action(float mean, float sigma, float z) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
   const float p = sigma * z;
   const float a = mean + p;
-  return fminf(1.0f, fmaxf(-1.0f, a));
+  return clip_keep_nan(a, -1.0f, 1.0f);
 }
 
 // the per-row tail of brs_ddpg_act: mean[2] is the actor's output (ignored when random != 0)
@@ -73,7 +75,8 @@ BRS_HD void act_tail(uint64_t seed, int64_t gid, uint32_t step, float sigma, int
   }
 }
 
-// y = r + (1 - done) gamma Q'(s', pi'(s')); a row with done != 0 returns r itself
+// y = r + (1 - done) gamma Q'(s', pi'(s')); a row with done != 0 returns r itself, bit for bit, whatever Q' is: where SB3
+// computes 0 * NaN for a poisoned next_obs or target network, this returns the reward
 BRS_HD float td_combine(float reward, uint8_t done, float gamma, float q_next) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -90,9 +93,9 @@ BRS_HD float smoothed_action(float mean, float policy_noise, float clip, float z
 #pragma clang fp contract(off)
 #endif
   float p = policy_noise * z;
-  p = fminf(clip, fmaxf(-clip, p));
+  p = clip_keep_nan(p, -clip, clip);
   const float a = mean + p;
-  return fminf(1.0f, fmaxf(-1.0f, a));
+  return clip_keep_nan(a, -1.0f, 1.0f);
 }
 // the per-row tail of brs_td3_td_target before the two critics: z[2] from the row's Philox block, next_action[2] from mean[2]
 BRS_HD void td3_action_tail(uint64_t seed, uint32_t draw, uint32_t row, float policy_noise, float clip, const float* mean, float* next_action,
@@ -102,8 +105,8 @@ BRS_HD void td3_action_tail(uint64_t seed, uint32_t draw, uint32_t row, float po
   normal_pair(o[0], o[1], z);
   for (int k = 0; k < ACT; k++) next_action[k] = smoothed_action(mean[k], policy_noise, clip, z[k]);
 }
-// ... and after them: clipped double-Q, then td_combine
-BRS_HD float td3_combine(float reward, uint8_t done, float gamma, float q1, float q2) { return td_combine(reward, done, gamma, fminf(q1, q2)); }
+// ... and after them: clipped double-Q (a NaN from either critic stays, as torch.minimum), then td_combine
+BRS_HD float td3_combine(float reward, uint8_t done, float gamma, float q1, float q2) { return td_combine(reward, done, gamma, min_keep_nan(q1, q2)); }
 // the argument rules of brs_td3_td_target that need no device: 0 or the text after "brs_td3_td_target: "
 inline const char* td3_target_argument_error(const void* actor_t, const void* critics_t, int32_t m, const void* next_obs, const void* reward,
                                              const void* done, float policy_noise, float noise_clip, const void* y) {
@@ -137,12 +140,12 @@ template <class N> inline void forward_row(const float* w, const float* x, float
   for (int u = 0; u < N::H1; u++) {
     float s = w[O::B1 + u];
     for (int k = 0; k < N::IN; k++) s = fmaf(w[O::W1 + u * N::IN + k], x[k], s);
-    h1[u] = s > 0.0f ? s : 0.0f;
+    h1[u] = relu_keep_nan(s);
   }
   for (int u = 0; u < N::H2; u++) {
     float s = w[O::B2 + u];
     for (int k = 0; k < N::H1; k++) s = fmaf(w[O::W2 + u * N::H1 + k], h1[k], s);
-    h2[u] = s > 0.0f ? s : 0.0f;
+    h2[u] = relu_keep_nan(s);
   }
   for (int u = 0; u < N::OUT; u++) {
     float s = 0.0f;

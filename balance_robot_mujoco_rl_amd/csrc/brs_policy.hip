@@ -23,6 +23,7 @@
 #include "../../include/brs_policy.h"
 #include "brs_host.hpp"
 #include "brs_core.hpp"  // philox4x32_10 (same generator as the simulator)
+#include "brs_nan.hpp"   // clip_keep_nan
 
 namespace {
 
@@ -175,7 +176,7 @@ __global__ void __launch_bounds__(POLICY_THREADS) policy_act_kernel(const float*
     action[(size_t)ACT * i + k] = a;
     // fminf / fmaxf drop a NaN operand: a NaN action would leave here as -1 and the simulator's bad-state guard, which resets
     // a lane that is handed a NaN action, would never see it.  np.clip (what SB3 applies) keeps the NaN; this unit is IEEE
-    action_clipped[(size_t)ACT * i + k] = a != a ? a : fminf(1.0f, fmaxf(-1.0f, a));
+    action_clipped[(size_t)ACT * i + k] = brs::clip_keep_nan(a, -1.0f, 1.0f);
     lp += -0.5f * z[k] * z[k] - ls - 0.9189385332046727f;  // log N(a; mean, exp(ls)) with (a - mean) / sigma = z
     if (noise) noise[(size_t)ACT * i + k] = z[k];
   }

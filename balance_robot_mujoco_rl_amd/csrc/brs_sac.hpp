@@ -34,7 +34,7 @@ BRS_HD void sac_row_block(uint32_t tag, uint64_t seed, uint32_t draw, uint32_t j
 }
 
 // torch.clamp(log_std, -20, 2) and where its backward lets the gradient through (both ends included, as torch)
-BRS_HD float clamp_log_std(float raw) { return fminf(LOG_STD_MAX, fmaxf(LOG_STD_MIN, raw)); }
+BRS_HD float clamp_log_std(float raw) { return clip_keep_nan(raw, LOG_STD_MIN, LOG_STD_MAX); }  // a NaN stays, as torch.clamp
 BRS_HD bool log_std_gate(float raw) { return raw >= LOG_STD_MIN && raw <= LOG_STD_MAX; }
 BRS_HD float ent_coef(const float* actor) { return expf(actor[SAC_NACTOR]); }
 
@@ -84,8 +84,8 @@ BRS_HD void sac_act_tail(uint64_t seed, int64_t gid, uint32_t step, int determin
   }
 }
 
-// which critic's Q is the minimum: critic 0 on a tie, as torch.min over the stacked pair
-BRS_HD int min_select(float q0, float q1) { return q1 < q0 ? 1 : 0; }
+// which critic's Q is the minimum: critic 0 on a tie, as torch.min over the stacked pair; a NaN is selected, from whichever critic
+BRS_HD int min_select(float q0, float q1) { return (q1 < q0 || (q1 != q1 && q0 == q0)) ? 1 : 0; }
 
 // y = r + (1 - done) gamma (min(Q1', Q2') - alpha logp')
 BRS_HD float sac_combine(float reward, uint8_t done, float gamma, float q0, float q1, float alpha, float logp) {
