@@ -32,6 +32,8 @@ include/brs.h (libbrs_hip.so).  This package is the host-side mirror of the refe
                                            brs_ddpg_learner_create_sac): sb_rl.py's `-a SAC` with the DDPG net_arch
     quant.quantize_policy / QuantPolicy    int8 post-training quantisation of the actor and the int8 network as a HIP kernel
                                            (include/brs_qpolicy.h): quantize_tflite.py and sb_rl.py:285-364 on the GPU
+    quant.quantize_actor / QuantActor      the same deployment check for the actor DDPG, TD3 and SAC train, 6-300-200-2 with ReLU and
+                                           a tanh output (include/brs_qpolicy.h: brs_qpolicy_actor_*)
 
 There is no CPU fallback: creating a sim without a HIP device raises.
 """
@@ -41,11 +43,12 @@ from .offpolicy import (DeviceDDPGLearner, DeviceDDPGNets, DeviceOffPolicyCollec
                         DeviceSACNets, DeviceTD3Learner, flatten_ddpg_state_dict, flatten_sac_actor, flatten_td3_critics,
                         unflatten_ddpg_state_dict, unflatten_sac_actor, unflatten_td3_critics)
 from .monitor import EpisodeMonitor, EpisodeStats, episode_count_targets, evaluate_policy  # noqa: F401
-from .quant import REFERENCE_CALIBRATION, QuantModel, QuantPolicy, quantize_policy  # noqa: F401
+from .quant import (REFERENCE_CALIBRATION, QuantActor, QuantActorModel, QuantModel, QuantPolicy, quantize_actor,  # noqa: F401
+                    quantize_policy)
 from .sim import BatchedSim, BrsError  # noqa: F401
 from .vec_env import BalanceVecEnv  # noqa: F401
 
 __all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "DeviceA2CLearner", "DeviceDDPGLearner", "DeviceDDPGNets", "DeviceOffPolicyCollector", "DevicePPOLearner", "DeviceReplayBuffer", "DeviceSACLearner", "DeviceSACNets", "DeviceTD3Learner", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "LearnerStats",
-           "QuantModel", "QuantPolicy",
-           "REFERENCE_CALIBRATION", "episode_count_targets", "evaluate_policy", "flatten_ddpg_state_dict", "flatten_sac_actor", "flatten_td3_critics", "make_vec", "quantize_policy", "spec",
+           "QuantActor", "QuantActorModel", "QuantModel", "QuantPolicy",
+           "REFERENCE_CALIBRATION", "episode_count_targets", "evaluate_policy", "flatten_ddpg_state_dict", "flatten_sac_actor", "flatten_td3_critics", "make_vec", "quantize_actor", "quantize_policy", "spec",
            "unflatten_ddpg_state_dict", "unflatten_sac_actor", "unflatten_td3_critics"]

@@ -20,14 +20,14 @@ SIM_FLAGS = ["-Xarch_device", "-ffast-math", "-Xarch_device", "-fgpu-flush-denor
              # for register pressure and leaves serial chains (a dependent VALU instruction issues ~1.7x slower than
              # an independent one for a lone wave).  The ILP strategy: +4.3 % Env03, +2.7 % Env01 (same-box A/B)
              "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
-# the translation units of libbrs_hip.so: (source, its own flags, in the build id).  Policy / GAE kernels, renderer and int8 actor
+# the translation units of libbrs_hip.so: (source, its own flags, in the build id).  Policy / GAE kernels, renderer and int8 actors
 # keep IEEE math (checked against fp32 torch at rtol 1e-5 / bit for bit against their host builds under tests/), and so does the
 # episode monitor, the PPO learner (fp64 torch autograd at 1e-5 per parameter block), the DDPG data path (fp64 numpy at 1e-5) and
 # the DDPG learner (fp64 torch autograd at 1e-5 per block); the build id names the step and policy kernels that committed profiles
-# were measured on, so the other six units stay out of it.
+# were measured on, so the other seven units stay out of it.
 UNITS = [("brs_kernels.hip", SIM_FLAGS, True), ("brs_policy.hip", [], True), ("brs_render.hip", [], False), ("brs_qpolicy.hip", [], False),
          ("brs_monitor.hip", [], False), ("brs_learner.hip", [], False), ("brs_offpolicy.hip", [], False),
-         ("brs_ddpg_learner.hip", [], False)]
+         ("brs_ddpg_learner.hip", [], False), ("brs_qactor.hip", [], False)]
 SRC = os.path.join(_CSRC, UNITS[0][0])  # the unit that takes the A/B flags and the build id stamp
 # what the build id hashes next to the sources of its units; brs_host.hpp holds no kernel code and stays out of it
 HEADERS = [os.path.join(_CSRC, h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp", "brs_nan.hpp")] + \
@@ -97,6 +97,11 @@ class BrsQLayer(C.Structure):
 
 class BrsQModel(C.Structure):
     _fields_ = [("input_scale", C.c_double), ("input_zero", C.c_int32), ("reserved", C.c_int32), ("layer", BrsQLayer * 3)]
+
+
+class BrsQActorModel(C.Structure):
+    _fields_ = [("input_scale", C.c_double), ("input_zero", C.c_int32), ("action_zero", C.c_int32), ("action_scale", C.c_double),
+                ("layer", BrsQLayer * 3)]
 
 
 FLAG_AUTO_RESET, FLAG_NOISE_ON, FLAG_NOISE_OFF, FLAG_NO_LANE_GROUPING = 1, 2, 4, 8
@@ -231,6 +236,11 @@ SIGNATURES = {
         "brs_qpolicy_quantize_multiplier": (C.c_int, [C.c_double, _i32p, _i32p]),
         "brs_qpolicy_set_model": (C.c_int, [_vp, C.POINTER(BrsQModel)]),
         "brs_qpolicy_act": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
+        "brs_qpolicy_actor_create": (C.c_int, [_i32, C.POINTER(_vp)]),
+        "brs_qpolicy_actor_destroy": (C.c_int, [_vp]),
+        "brs_qpolicy_actor_last_error": (C.c_char_p, [_vp]),
+        "brs_qpolicy_actor_set_model": (C.c_int, [_vp, C.POINTER(BrsQActorModel)]),
+        "brs_qpolicy_actor_act": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
     },
 }
 SYMBOLS = list(SIGNATURES["brs.h"]) + list(SIGNATURES["brs_policy.h"])

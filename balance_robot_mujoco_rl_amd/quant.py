@@ -7,6 +7,9 @@ the int8 network in closed loop in the simulator (src/sb_rl.py:285-364, `test-tf
     quantize_policy   post-training quantisation of the actor tower of a float parameter vector (DevicePolicy's) or an SB3
                       state_dict: no TFLite needed
     QuantPolicy       the int8 network for n envs as a HIP kernel (brs_qpolicy_act), bit-exact integer arithmetic
+    QuantActorModel, quantize_actor, QuantActor
+                      the same three for the off-policy actor 6 -> 300 -> ReLU -> 200 -> ReLU -> 2 -> tanh of DDPG, TD3 and SAC
+                      (brs_qpolicy_actor_act)
 
 PyTorch only owns the buffers and the stream.  There is no CPU fallback."""
 import ctypes as C
@@ -241,4 +244,196 @@ class QuantPolicy:
             _need(out_q, "out_q", torch.int8, (n, 2), d)
         self._check(self.L.brs_qpolicy_act(self.h, n, _p(obs), _p(out), _p(out_q),
                                            C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "brs_qpolicy_act")
+        return out
+
+
+# ------------------------------------------------------------------- the off-policy actor, 6 -> 300 -> ReLU -> 200 -> ReLU -> 2 -> tanh
+_ACTOR_SIZES = ((6, 300), (300, 200), (200, 2))
+
+
+class QuantActorModel:
+    """An int8 actor 6 -> 300 -> ReLU -> 200 -> ReLU -> 2 -> tanh, the network DDPG, TD3 and SAC train.
+    `layers[k]` is a dict: W int8 [out][in], b int32 [out], ws float64 [out] (weight scale per output channel), bs float64 [out]
+    (bias scale = input scale x ws), os / oz (scale and zero point of the layer's output; on a hidden layer oz is the code of
+    real 0, below which ReLU clamps).  `action_scale` / `action_zero`: of the output tanh table's result."""
+
+    def __init__(self, input_scale, input_zero, layers, action_scale=1.0 / 128.0, action_zero=0):
+        self.input_scale, self.input_zero = float(input_scale), int(input_zero)
+        self.action_scale, self.action_zero = float(action_scale), int(action_zero)
+        if len(layers) != 3:
+            raise ValueError(f"expected three layers, got {len(layers)}")
+        self.layers = []
+        for k, (L, (n_in, n_out)) in enumerate(zip(layers, _ACTOR_SIZES)):
+            W, b = np.asarray(L["W"]), np.asarray(L["b"])
+            if W.shape != (n_out, n_in) or b.shape != (n_out,):
+                raise ValueError(f"layer {k}: expected weights {(n_out, n_in)} and bias {(n_out,)}, got {W.shape} and {b.shape}")
+            if np.abs(W).max(initial=0) > 128 or np.abs(b.astype(np.int64)).max(initial=0) > 2 ** 31 - 1:
+                raise ValueError(f"layer {k}: weights must fit int8 and biases int32")
+            self.layers.append(dict(W=np.ascontiguousarray(W, np.int8), b=np.ascontiguousarray(b, np.int32),
+                                    ws=np.ascontiguousarray(np.broadcast_to(np.asarray(L["ws"], np.float64).ravel(), (n_out,))),
+                                    bs=np.ascontiguousarray(np.broadcast_to(np.asarray(L["bs"], np.float64).ravel(), (n_out,))),
+                                    os=float(L["os"]), oz=int(L["oz"])))
+
+    # ------------------------------------------------------------------------------------------------------------ files
+    @classmethod
+    def load(cls, path):
+        z = np.load(path)  # allow_pickle stays False
+        s = lambda k: float(np.asarray(z[k], np.float64).ravel()[0])
+        layers = [dict(W=z[f"fc{k}_weight_q"], ws=z[f"fc{k}_weight_scale"], b=z[f"fc{k}_bias_q"], bs=z[f"fc{k}_bias_scale"],
+                       os=s(f"fc{k}_out_scale"), oz=int(s(f"fc{k}_out_zero_point"))) for k in range(3)]
+        return cls(s("input_scale"), int(s("input_zero_point")), layers, s("action_scale"), int(s("action_zero_point")))
+
+    def arrays(self):
+        """the npz key set, in the style of QuantModel's"""
+        i64 = lambda v: np.full(1, int(v), np.int64)
+        out = {"input_scale": np.array([self.input_scale]), "input_zero_point": i64(self.input_zero),
+               "action_scale": np.array([self.action_scale]), "action_zero_point": i64(self.action_zero)}
+        for k, L in enumerate(self.layers):
+            out[f"fc{k}_weight_q"], out[f"fc{k}_weight_scale"] = L["W"], L["ws"]
+            out[f"fc{k}_bias_q"], out[f"fc{k}_bias_scale"] = L["b"], L["bs"]
+            out[f"fc{k}_out_scale"], out[f"fc{k}_out_zero_point"] = np.array([L["os"]]), i64(L["oz"])
+        return out
+
+    def save(self, path):
+        np.savez(path, **self.arrays())
+
+    # --------------------------------------------------------------------------------------------------------- contents
+    def table(self):
+        """the output layer's tanh table, int8 [256], indexed by q + 128 (fp64, half to even)"""
+        L = self.layers[2]
+        return tanh_table(L["os"], L["oz"], self.action_scale, self.action_zero)
+
+    def float_params(self):
+        """the same network with DEQUANTISED weights as the flat float32 DDPG actor vector (what DeviceDDPGNets.act takes)"""
+        parts = []
+        for L in self.layers:
+            parts += [(L["W"].astype(np.float64) * L["ws"][:, None]).ravel(), L["b"].astype(np.float64) * L["bs"]]
+        flat = np.concatenate(parts).astype(np.float32)
+        assert flat.size == _lib.DDPG_NACTOR
+        return flat
+
+    def c_model(self):
+        """-> (include/brs_qpolicy.h brs_qactor_model, the arrays its pointers refer to: keep them alive while it is used)"""
+        m = _lib.BrsQActorModel()
+        m.input_scale, m.input_zero = self.input_scale, self.input_zero
+        m.action_scale, m.action_zero = self.action_scale, self.action_zero
+        table = np.ascontiguousarray(self.table(), np.int8)
+        keep = [table]
+        for k, L in enumerate(self.layers):
+            c = m.layer[k]
+            c.n_in, c.n_out = L["W"].shape[1], L["W"].shape[0]
+            c.weight, c.bias, c.bias_scale = L["W"].ctypes.data, L["b"].ctypes.data, L["bs"].ctypes.data
+            c.out_scale, c.out_zero, c.tanh_zero = L["os"], L["oz"], 0
+            c.tanh_table = table.ctypes.data if k == 2 else None
+            keep += [L["W"], L["b"], L["bs"]]
+        return m, keep
+
+
+def _actor_flat(params, head):
+    """-> the fp64 DDPG-layout actor vector [DDPG_NACTOR]; with head = "sac" the mu head of a SAC actor (log_std dropped)"""
+    from .offpolicy import flatten_ddpg_state_dict, flatten_sac_actor
+    if head not in ("ddpg", "sac"):
+        raise ValueError(f"head must be 'ddpg' or 'sac', got {head!r}")
+    n01 = 300 * 6 + 300 + 200 * 300 + 200
+    if head == "ddpg":
+        flat = flatten_ddpg_state_dict(params) if isinstance(params, dict) else np.asarray(params)
+        if flat.size != _lib.DDPG_NACTOR:
+            raise ValueError(f"expected {_lib.DDPG_NACTOR} parameters, got {flat.size}")
+        return flat.astype(np.float64).ravel()
+    flat = flatten_sac_actor(params) if isinstance(params, dict) else np.asarray(params)
+    if flat.size not in (_lib.SAC_NACTOR, _lib.SAC_NACTOR + 1):
+        raise ValueError(f"expected {_lib.SAC_NACTOR} (+ 1) parameters, got {flat.size}")
+    flat = flat.astype(np.float64).ravel()
+    # the SAC vector stacks the heads into one [4][200] layer: mu's weights, log_std's weights, mu's bias, log_std's bias
+    return np.concatenate([flat[:n01], flat[n01:n01 + 400], flat[n01 + 800:n01 + 802]])
+
+
+def quantize_actor(params, calibration_obs=None, head="ddpg"):
+    """Post-training int8 quantisation of the off-policy actor -> QuantActorModel.  `params`: the flat DDPG_NACTOR vector
+    (DeviceDDPGNets) or an SB3 / train-tool state_dict; with head = "sac" a SAC actor (flat SAC_NACTOR (+ 1) or a state_dict), of
+    which the deterministic action tanh(mu(s)) is quantised and the log_std head dropped.  `calibration_obs` [k, 6] as in
+    quantize_policy, whose rules hold here too: half away from zero, symmetric weights per output channel, bias_scale = input
+    scale x ws, ranges from the FLOAT network in fp64 on the calibration rows.  A hidden layer's output is the POST-ReLU
+    activation: range [0, max], so its zero point is always -128 (the code of real 0; a degenerate range gets scale 1).  The
+    output pre-activation gets an asymmetric range; the tanh table's result has scale 1 / 128 and zero point 0."""
+    flat = _actor_flat(params, head)
+    cal = np.asarray(REFERENCE_CALIBRATION if calibration_obs is None else calibration_obs, np.float64)
+    if cal.ndim != 2 or cal.shape[1] != 6 or cal.shape[0] < 1 or not np.isfinite(cal).all():
+        raise ValueError("calibration_obs: expected finite [k, 6]")
+    if not np.isfinite(flat).all():
+        raise ValueError("the actor's parameters are not finite")
+    in_scale, in_zero = _activation_qparams(cal.min(), cal.max())
+    input_scale, input_zero = in_scale, in_zero
+    x, off, layers = cal, 0, []
+    for k, (n_in, n_out) in enumerate(_ACTOR_SIZES):
+        W = flat[off:off + n_in * n_out].reshape(n_out, n_in); off += n_in * n_out
+        b = flat[off:off + n_out]; off += n_out
+        amax = np.abs(W).max(axis=1)
+        ws = np.where(amax > 0, amax / 127.0, 1.0)
+        Wq = np.clip(_round_half_away(W / ws[:, None]), -127, 127).astype(np.int8)
+        bs = in_scale * ws
+        bq = _round_half_away(b / bs)
+        if np.abs(bq).max() > 2 ** 31 - 1:
+            raise ValueError(f"layer {k}: a quantised bias leaves int32 (bias {np.abs(b).max():.3g} at scale {bs.min():.3g})")
+        pre = x @ W.T + b  # the float network on the calibration rows
+        if k < 2:
+            x = np.maximum(pre, 0.0)
+            hi = float(x.max())
+            os_, oz = (hi / 255.0, -128) if hi > 0.0 else (1.0, -128)
+            in_scale = os_
+        else:
+            os_, oz = _activation_qparams(pre.min(), pre.max())
+        layers.append(dict(W=Wq, b=bq.astype(np.int32), ws=ws, bs=bs, os=os_, oz=oz))
+    return QuantActorModel(input_scale, input_zero, layers, 1.0 / 128.0, 0)
+
+
+class QuantActor:
+    """The int8 off-policy actor evaluated by the HIP kernel: obs [n, 6] -> action [n, 2], with integer arithmetic only"""
+
+    def __init__(self, model, device=0):
+        if not torch.cuda.is_available():
+            raise BrsError("no HIP device visible to PyTorch: the int8 actor has no CPU fallback")
+        self.L = _lib.lib()
+        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+        h = C.c_void_p()
+        rc = self.L.brs_qpolicy_actor_create(self.device.index, C.byref(h))
+        if rc != 0:
+            raise BrsError(f"brs_qpolicy_actor_create failed ({rc}): {self.L.brs_qpolicy_actor_last_error(None).decode()}")
+        self.h = h
+        self.set_model(model)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.brs_qpolicy_actor_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise BrsError(f"{what} failed ({rc}): {self.L.brs_qpolicy_actor_last_error(self.h).decode()}")
+
+    def set_model(self, model):
+        """load another QuantActorModel (synchronous; takes effect on the next act)"""
+        m, keep = model.c_model()
+        self._check(self.L.brs_qpolicy_actor_set_model(self.h, C.byref(m)), "brs_qpolicy_actor_set_model")
+        del keep
+        self.model = model
+
+    def act(self, obs, out=None, out_q=None):
+        """obs [n, 6] f32 cuda -> action [n, 2] f32 (not clipped); `out_q` [n, 2] int8 receives the int8 codes"""
+        n = obs.shape[0]
+        d = self.device
+        _need(obs, "obs", torch.float32, (n, 6), d)
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float32, device=d)
+        _need(out, "out", torch.float32, (n, 2), d)
+        if out_q is not None:
+            _need(out_q, "out_q", torch.int8, (n, 2), d)
+        self._check(self.L.brs_qpolicy_actor_act(self.h, n, _p(obs), _p(out), _p(out_q),
+                                                 C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "brs_qpolicy_actor_act")
         return out

@@ -78,6 +78,60 @@ int brs_qpolicy_set_model(brs_qpolicy*, const brs_qmodel*);
  * only enqueues on `stream`: no synchronisation, no allocation, capturable into a graph like brs_render. */
 int brs_qpolicy_act(brs_qpolicy*, int32_t n, const float* obs_dev, float* action_dev, int8_t* action_q_dev, void* stream);
 
+/*
+ * The int8 form of the OFF-POLICY actor, the network DDPG, TD3 and SAC train (include/brs_policy.h: brs_ddpg_act, and
+ * the deterministic action tanh(mu) of brs_sac_act):
+ *
+ *     obs[6] -> 300 -> ReLU -> 200 -> ReLU -> 2 -> tanh
+ *
+ * Hidden layers carry NO table (tanh_table == NULL, tanh_zero ignored); the output layer carries one.  Steps, each
+ * defined so that every platform gives the same bits:
+ *
+ *   1. input        as step 1 above
+ *   2. accumulate   acc[c] = b[c] + sum_i W[c][i] (q_in[i] - z_in) in int32.  z_in of layer 0 is input_zero, of layers 1
+ *                   and 2 the previous layer's out_zero: there is no table in between, so the previous layer's output code
+ *                   IS the next layer's input code.  The fold into the bias happens once, at set_model, as above.
+ *   3. requantise   as step 3 above: one rounding, clamp to [-128, 127]
+ *   4. ReLU         hidden layers only: q <- max(q, out_zero), out_zero being the code of real 0
+ *   5. tanh         output layer only: q <- table[q + 128], made by the caller; no transcendental on the device
+ *   6. output       action = (float)((double)(q - action_zero) action_scale), not clipped; the code q is available too
+ *
+ * The entry points are named brs_qpolicy_actor_... because every function this header declares belongs to the
+ * brs_qpolicy_ family of the library's symbol table.
+ */
+#define BRS_QACTOR_OBS 6
+#define BRS_QACTOR_H0 300
+#define BRS_QACTOR_H1 200
+#define BRS_QACTOR_ACT 2
+
+typedef struct brs_qactor_model {
+  double input_scale;  /* of the observation */
+  int32_t input_zero;
+  int32_t action_zero; /* zero point of the output table's result */
+  double action_scale; /* its scale */
+  brs_qlayer layer[3]; /* 6/300, 300/200, 200/2; only layer[2] has a table */
+} brs_qactor_model;
+
+typedef struct brs_qactor brs_qactor;
+
+/* needs a HIP device */
+int brs_qpolicy_actor_create(int32_t device, brs_qactor** out);
+int brs_qpolicy_actor_destroy(brs_qactor*);
+const char* brs_qpolicy_actor_last_error(const brs_qactor*);
+
+/* load a model (HOST pointers; nothing is kept).  Checked, each failure is BRS_ERR_ARG with a message that names layer
+ * and channel: the sizes are exactly 6/300/200/2, the output layer has a table and the hidden layers have none, every
+ * zero point is in [-128, 127], every scale is positive and finite, every multiplier is valid, and no int8 input can
+ * take an accumulator (with or without the folded zero point) out of int32.  The model is checked BEFORE the handle is
+ * looked at: with a NULL handle a bad model gives BRS_ERR_ARG and a good one BRS_ERR_STATE.  Synchronous: it drains the
+ * device, then copies. */
+int brs_qpolicy_actor_set_model(brs_qactor*, const brs_qactor_model*);
+
+/* one step of the int8 actor for n envs: obs[n][6] floats -> action[n][2] floats, and the int8 codes action_q[n][2]
+ * (may be NULL).  Device pointers; only enqueues on `stream`: no synchronisation, no allocation, capturable into a
+ * graph.  Rows beyond n - 1 are never written. */
+int brs_qpolicy_actor_act(brs_qactor*, int32_t n, const float* obs_dev, float* action_dev, int8_t* action_q_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,28 @@
+// Host build of the int8 off-policy actor's kernel source (balance_robot_mujoco_rl_amd/csrc/brs_qactor.hpp): the checks and the
+// zero-point fold of brs_qpolicy_actor_set_model, and the per-env scalar form of the kernel's arithmetic, for the CPU tests
+// (tests/test_qactor_cpu.py builds this with g++ as a shared object; qactorhost_main.cpp is the program the sanitizers run).
+#include "brs_qactor.hpp"
+
+#include <string.h>
+
+extern "C" {
+
+int qah_image_bytes() { return (int)sizeof(brs::qactor::Image); }
+
+// brs_qpolicy_actor_set_model without the device: 0 and the image, or BRS_ERR_ARG and the reason in err[err_len]
+int qah_build(const brs_qactor_model* model, void* image, char* err, int err_len) {
+  std::string why;
+  const int rc = brs::qactor::build_image(model, (brs::qactor::Image*)image, &why);
+  if (err && err_len > 0) { strncpy(err, why.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
+  return rc;
+}
+
+// brs_qpolicy_actor_act on the host: obs[n][6] -> action[n][2], action_q[n][2] (may be NULL)
+void qah_act(const void* image, int n, const float* obs, float* action, int8_t* action_q) {
+  const brs::qactor::Image& im = *(const brs::qactor::Image*)image;
+  for (int i = 0; i < n; i++)
+    brs::qactor::act_env(im, obs + (size_t)brs::qactor::OBS * i, action + (size_t)brs::qactor::ACT * i,
+                         action_q ? action_q + (size_t)brs::qactor::ACT * i : nullptr);
+}
+
+}  // extern "C"

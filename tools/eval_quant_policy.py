@@ -13,6 +13,12 @@ output, unclipped, as the reference does (envs/RobotMoveBaseEnv.py:178-208).
                its dequantised weights
 --params PATH  a float parameter vector (.npy, the order of include/brs_policy.h): quantised here with quantize_policy and
                the reference's calibration rows; the float run uses the vector itself
+--actor PATH   an OFF-POLICY actor, 6-300-200-2: the flat vector (.npy) or the state_dict (.pt) that
+               tools/train_ddpg_torch.py, train_td3_torch.py or train_sac_torch.py write with --save-actor; --algo ddpg|td3|sac
+               says how to read it.  Quantised here with quantize_actor; the float run is DeviceDDPGNets.act with sigma 0, or
+               DeviceSACNets.act deterministic, and the int8 run QuantActor (for SAC: the deterministic action tanh(mu))
+
+    python tools/eval_quant_policy.py --env Env01-v1 --actor actor.npy --algo td3 --save actor_int8.npz
 """
 import argparse, json, os, sys
 import numpy as np
@@ -40,14 +46,51 @@ def evaluate(env, n, steps, act, seed=123):
                 mean_ep_len=s.mean_len, median_ep_len=median, mean_reward_per_step=(s.sum_ret + s.running_ret) / (n * steps))
 
 
+def evaluate_actor(a):
+    """--actor: the same three lines for the off-policy actor"""
+    from balance_robot_mujoco_rl_amd import DeviceDDPGNets, DeviceSACNets, QuantActor, flatten_sac_actor, quantize_actor
+    sac = a.algo == "sac"
+    params = torch.load(a.actor, map_location="cpu", weights_only=True) if a.actor.endswith(".pt") else np.load(a.actor).astype(np.float32).ravel()
+    qm = quantize_actor(params, head="sac" if sac else "ddpg")
+    if a.save:
+        qm.save(a.save)
+    if sac:
+        flat = flatten_sac_actor(params) if isinstance(params, dict) else params
+        flat = np.concatenate([flat, np.zeros(1, np.float32)]) if flat.size == _lib.SAC_NACTOR else flat   # log_ent_coef: unused by act
+        nets = DeviceSACNets(device=0)
+        weights = torch.from_numpy(np.ascontiguousarray(flat, np.float32)).cuda()
+        float_act, name = (lambda obs, t: nets.act(weights, obs, t, deterministic=True)), "float (DeviceSACNets, deterministic)"
+    else:
+        nets = DeviceDDPGNets(device=0)
+        weights = torch.from_numpy(ddpg_flat(params)).cuda()
+        float_act, name = (lambda obs, t: nets.act(weights, obs, t, 0.0)), "float (DeviceDDPGNets, sigma 0)"
+    qact = QuantActor(qm, device=0)
+    common = dict(env=a.env, envs=a.envs, steps=a.steps, policy=f"{os.path.basename(a.actor)} ({a.algo} actor, quantised here)", build_id=_lib.build_id())
+    f = evaluate(a.env, a.envs, a.steps, float_act)
+    print(json.dumps(dict(common, network=name, **f)))
+    q = evaluate(a.env, a.envs, a.steps, lambda obs, t: qact.act(obs))
+    print(json.dumps(dict(common, network="int8 (QuantActor)", **q)))
+    diff = {k: (None if f[k] is None or q[k] is None else q[k] - f[k]) for k in f}
+    print(json.dumps(dict(common, network="int8 - float", **diff)))
+
+
+def ddpg_flat(params):
+    """a DDPG / TD3 actor, flat or as a state_dict -> the flat float32 vector"""
+    from balance_robot_mujoco_rl_amd import flatten_ddpg_state_dict
+    return np.ascontiguousarray(flatten_ddpg_state_dict(params) if isinstance(params, dict) else params, np.float32)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--env", default="Env01-v3"); ap.add_argument("--envs", type=int, default=4096); ap.add_argument("--steps", type=int, default=1500)
     src = ap.add_mutually_exclusive_group()
-    src.add_argument("--npz"); src.add_argument("--params")
+    src.add_argument("--npz"); src.add_argument("--params"); src.add_argument("--actor")
+    ap.add_argument("--algo", choices=("ddpg", "td3", "sac"), default="ddpg", help="how --actor is read")
     ap.add_argument("--head", choices=("mean", "actions"), default="mean")
     ap.add_argument("--save", help="write the int8 model that was evaluated to this .npz")
     a = ap.parse_args()
+    if a.actor:
+        return evaluate_actor(a)
     if a.params:
         flat = np.load(a.params).astype(np.float32).ravel()
         qm, what = quantize_policy(flat), f"{os.path.basename(a.params)} (quantised here)"

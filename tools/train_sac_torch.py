@@ -216,6 +216,8 @@ def main(argv=None):
     ap.add_argument("--device-learner", action="store_true", help="the update by the HIP kernels too (needs --device-data)")
     ap.add_argument("--eval-episodes", type=int, default=0); ap.add_argument("--eval-envs", type=int, default=256)
     ap.add_argument("--out", default="")
+    ap.add_argument("--save-actor", default="", help="write the trained actor on exit: the flat vector as .npy, or a state_dict as .pt "
+                                                     "(either is what tools/eval_quant_policy.py --actor PATH --algo sac reads)")
     a = ap.parse_args(argv)
     if a.device_learner and not a.device_data:
         ap.error("--device-learner requires --device-data")
@@ -254,6 +256,13 @@ def main(argv=None):
     if a.eval_episodes:
         log["eval_mean_return"], log["eval_std_return"], log["eval_mean_len"] = evaluate(a.env, model, a.eval_episodes, a.eval_envs, a.device_data)
     print(json.dumps(log))
+    if a.save_actor:
+        from balance_robot_mujoco_rl_amd import unflatten_sac_actor
+        flat = model.flat["actor"].detach().cpu().numpy()
+        if a.save_actor.endswith(".pt"):
+            torch.save(unflatten_sac_actor(flat, "tool"), a.save_actor)
+        else:
+            np.save(a.save_actor, flat)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(log, f, indent=1)
