@@ -59,6 +59,17 @@ __device__ __forceinline__ unsigned long long* brs_tim_slots() {  // 16 x u64 pe
 #ifndef BRS_FLIP_TOL
 #define BRS_FLIP_TOL 1e-6
 #endif
+// a contact loop of the verify pass: one contact per iteration, in order.  With the flip tests flat (Solver::rows_) the loop
+// vectoriser would take two contacts at a time: a 2-wide body plus a remainder loop per contact family, and under -ffast-math
+// a re-associated cost sum.  _ROLLED: not unrolled either (the Env03 kernels, whose loops were rolled before the tests became
+// flat; the Env01 family's robot loop stays with the unroller, which has always unrolled it around its prefetch)
+#if defined(__clang__)
+#define BRS_CONTACT_LOOP _Pragma("clang loop vectorize(disable) interleave(disable)")
+#define BRS_CONTACT_LOOP_ROLLED _Pragma("clang loop vectorize(disable) interleave(disable) unroll(disable)")
+#else
+#define BRS_CONTACT_LOOP
+#define BRS_CONTACT_LOOP_ROLLED
+#endif
 // (Tried and not kept, round 3: the robot<->floor contacts in the same frame algebra as the patch -- they all share the world-aligned
 // frame, so they can accumulate one 8x8 matrix in (frame-coordinate twist, two wheel rates) and enter H by one congruence: 840
 // instead of ~1,400 instructions per trip on paper, but scalar and serially dependent where contact_into is packed and
@@ -1451,8 +1462,11 @@ template <typename R, bool BLK> struct Sim {
       for (int i = 0; i < NN; i++) cst += (R)0.5 * dx[i] * Md[i];
     }
 
-    // rows of one contact from (cn, c1, c2): e = cn +- c1, cn +- c2; returns mask, accumulates cost; l = max(-e, 0)
-    static BRS_HD int rows_(R cn, R c1, R c2, R D, R& cst, R* l, int mh, bool& sm) {
+    // rows of one contact from (cn, c1, c2): e = cn +- c1, cn +- c2; returns mask, accumulates cost; l = max(-e, 0).
+    // flips collects the rows whose flip counts (bits of any contact OR-ed together; the caller asks flips == 0).  It is an int
+    // on purpose: as a bool it lives in an SGPR pair as a lane mask, and merging it across the contact loops' divergent exits
+    // and the nested tests below cost ~14 scalar instructions per contact, each an issue slot of the lone wave
+    static BRS_HD int rows_(R cn, R c1, R c2, R D, R& cst, R* l, int mh, int& flips) {
       R e1 = cn + c1, e2 = cn - c1, e3 = cn + c2, e4 = cn - c2;
       l[0] = max_(-e1, (R)0); l[1] = max_(-e2, (R)0); l[2] = max_(-e3, (R)0); l[3] = max_(-e4, (R)0);
       cst += (R)0.5 * D * (l[0] * l[0] + l[1] * l[1] + l[2] * l[2] + l[3] * l[3]);
@@ -1460,10 +1474,10 @@ template <typename R, bool BLK> struct Sim {
       // a row that sits on its own boundary (|e| below the rounding of its terms) carries no force either way:
       // its flip does not invalidate the quadratic piece H was built for
       int df = mk ^ mh;
-      if (df) {  // rare (a wave usually skips this block)
+      if (df) {  // rare (a wave usually skips this block); all four rows tested flat, no saved-exec region per row
         R tol = (R)BRS_FLIP_TOL * (abs_(cn) + abs_(c1) + abs_(c2));
-        if (((df & 1) && abs_(e1) > tol) || ((df & 2) && abs_(e2) > tol) || ((df & 4) && abs_(e3) > tol) || ((df & 8) && abs_(e4) > tol))
-          sm = false;
+        int off = (abs_(e1) > tol ? 1 : 0) | (abs_(e2) > tol ? 2 : 0) | (abs_(e3) > tol ? 4 : 0) | (abs_(e4) > tol ? 8 : 0);
+        flips |= df & off;
       }
       return mk;
     }
@@ -1471,7 +1485,7 @@ template <typename R, bool BLK> struct Sim {
     // rows of the block<->wheel contact at x (and its force when FORCES)
     template <bool FORCES>
     static BRS_HD void passA_coupled(const Params<R>& P, Store<R>& st, const Frame& F, Masks& M, const R* x, Coupled& C, R& cst, R* l, R* fcon,
-                                     bool& sm) {
+                                     int& sm) {
       constexpr int c = PATCH_MAX;
       coupled_load(P, st, F, C);
       R t[3];
@@ -1515,12 +1529,13 @@ template <typename R, bool BLK> struct Sim {
     }
     // rows of the whole block<->torso patch at x (and its wrench when FORCES), patch-frame algebra
     template <bool FORCES>
-    static BRS_HD void passA_patch(const Params<R>& P, Store<R>& st, const Frame& F, Masks& M, const R* x, R& cst, R* l, R* fcon, bool& sm) {
+    static BRS_HD void passA_patch(const Params<R>& P, Store<R>& st, const Frame& F, Masks& M, const R* x, R& cst, R* l, R* fcon, int& sm) {
       Patch Q;
       patch_load(st, Q);
       R Vp[3], Wp[3], Ft[3] = {0, 0, 0}, Mt[3] = {0, 0, 0};
       patch_twist(Q, x, Vp, Wp);
       const R mu = P.cc[CC_BLOCK_ROBOT].mu;
+      BRS_CONTACT_LOOP_ROLLED
       for (int c = 0; c < F.nc; c++) {
         const R r[3] = {st.getc(c, 0), st.getc(c, 1), st.getc(c, 2)};
         const R An = st.getc(c, 3), Bt1 = st.getc(c, 4), Bt2 = st.getc(c, 5), D = st.getc(c, 6);
@@ -1559,7 +1574,7 @@ template <typename R, bool BLK> struct Sim {
       if constexpr (FORCES) gauss(P, x, a0, Md, cst);  // the cost only steers the damped fallback
 #pragma unroll
       for (int i = 0; i < NN; i++) fcon[i] = 0;
-      bool sm = true;
+      int sm = 0;  // rows whose flip counts (rows_)
       // Env01 family: the record of the NEXT contact is requested from LDS before this one is evaluated -- a lone wave cannot hide
       // the ~100-cycle return behind another wave's work (+2.5 % Env01-v2, same box).  Not for Env03: the 7 live words cost it
       // 30 more SGPR spills and the gain is gone (profiles/r03_ab_experiments.json).
@@ -1569,6 +1584,7 @@ template <typename R, bool BLK> struct Sim {
 #pragma unroll
         for (int w_ = 0; w_ < SLOT_WORDS; w_++) nx_[w_] = st.get(SLOT_ROBOT, w_);
       }
+      BRS_CONTACT_LOOP
       for (int c = 0; c < F.nfr; c++) {
         int s = SLOT_ROBOT + c;
         R r[3], An, Bt1, Bt2, D;
@@ -1604,6 +1620,7 @@ template <typename R, bool BLK> struct Sim {
         }
       }
       if constexpr (BLK) {
+        BRS_CONTACT_LOOP_ROLLED
         for (int c = 0; c < F.nfb; c++) {
           int s = SLOT_BLOCK + c;
           R r[3] = {st.get(s, 0), st.get(s, 1), st.get(s, 2)};
@@ -1628,7 +1645,7 @@ template <typename R, bool BLK> struct Sim {
         if (sel_wheel_contact(F.sels)) passA_coupled<FORCES>(P, st, F, M, x, C, cst, l, fcon, sm);
       }
       cost = cst;
-      same = sm;
+      same = sm == 0;
     }
 
     static constexpr int NP = (NN + 1) / 2, NH2 = hp_count(NN);
@@ -1950,7 +1967,9 @@ template <typename R, bool BLK> struct Sim {
   struct SubCtx {
     Frame F;
     R f[8], fcon[NV], cost;
-    bool clL, clR, conv, first;
+    int cl;  // servo force clamped: bit 0 left, bit 1 right (an int: two bools held from sub_begin to sub_end are two lane masks
+             // in SGPR pairs, and the step kernels have none to spare -- they came back from their spill slots in every trip)
+    bool conv, first;
     int it;
     Masks M;
   };
@@ -1983,8 +2002,7 @@ template <typename R, bool BLK> struct Sim {
     // outcome: a wheel gains 0.26 rad/s per substep clamped and 0.10 unclamped
     const double uLd = min_(max_(ctrlL, -P.ctrlrange_d), P.ctrlrange_d), uRd = min_(max_(ctrlR, -P.ctrlrange_d), P.ctrlrange_d);
     const double fLd = P.kv_d * (uLd - S.wwd[0]), fRd = P.kv_d * (uRd - S.wwd[1]);
-    C.clL = fLd >= P.forcerange_d || fLd <= -P.forcerange_d;
-    C.clR = fRd >= P.forcerange_d || fRd <= -P.forcerange_d;
+    C.cl = ((fLd >= P.forcerange_d || fLd <= -P.forcerange_d) ? 1 : 0) | ((fRd >= P.forcerange_d || fRd <= -P.forcerange_d) ? 2 : 0);
     R fL = (R)min_(max_(fLd, -P.forcerange_d), P.forcerange_d), fR = (R)min_(max_(fRd, -P.forcerange_d), P.forcerange_d);
     f[6] = fL - P.damping * S.ww[0];
     f[7] = fR - P.damping * S.ww[1];
@@ -2055,7 +2073,7 @@ template <typename R, bool BLK> struct Sim {
     const Frame& F = C.F;
     const R* f = C.f;
     const R* fcon = C.fcon;
-    const bool clL = C.clL, clR = C.clR;
+    const bool clL = (C.cl & 1) != 0, clR = (C.cl & 2) != 0;
     // implicitfast: (M + h*diag(damping + kv[unclamped])) acc = smooth + constraint
     R rhs[8], acc[8];
 #pragma unroll

@@ -5,7 +5,9 @@ with the product's flags).  Used to compare A/B variants of brs_core.hpp before 
     python tools/isa_count.py [-DFLAG ...] [--kernel 'brs_step_kernelILb1ELi3E'] [--markers]
 
 --markers: build with -DBRS_MARKERS and print the instruction count between consecutive `; BRS_MARK name` comments (the
-phases of one trip in source order; compiler scheduling moves a few instructions across the fences' neighbours).
+phases of one trip in source order; compiler scheduling moves a few instructions across the fences' neighbours).  salu =
+scalar ALU instructions, lanemov = v_readlane + v_writelane (the SGPR spill traffic).  A region holds a loop's preheader
+as well as its body: what runs once per trip and what runs once per contact are told apart in the assembly, not here.
 """
 import collections, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,12 +52,14 @@ def main():
         return dict(total=sum(c.values()), valu=valu, packed=sum(v for k, v in c.items() if k.startswith("v_pk_")),
                     f64=sum(v for k, v in c.items() if k.endswith("_f64") or "_f64_" in k), lds=sum(v for k, v in c.items() if k.startswith("ds_")),
                     mov=c.get("v_mov_b32_e32", 0) + sum(v for k, v in c.items() if k.startswith("v_accvgpr")), cndmask=sum(v for k, v in c.items() if k.startswith("v_cndmask")),
-                    branch=sum(v for k, v in c.items() if k.startswith("s_cbranch") or k == "s_branch"), nop=c.get("s_nop", 0))
+                    branch=sum(v for k, v in c.items() if k.startswith("s_cbranch") or k == "s_branch"), nop=c.get("s_nop", 0),
+                    salu=sum(v for k, v in c.items() if k.startswith("s_") and not k.startswith(("s_cbranch", "s_branch", "s_nop", "s_waitcnt"))),
+                    lanemov=c.get("v_readlane_b32", 0) + c.get("v_writelane_b32", 0))
     print(m.group(1)); print(" ", summary(ops))
     if markers:
         for ph, c in per_phase.items():
             s = summary(c)
-            print(f"  {ph:28s} total {s['total']:6d} valu {s['valu']:6d} packed {s['packed']:5d} f64 {s['f64']:4d} lds {s['lds']:4d} mov {s['mov']:4d} cndmask {s['cndmask']:4d}")
+            print(f"  {ph:28s} total {s['total']:6d} valu {s['valu']:6d} packed {s['packed']:5d} f64 {s['f64']:4d} lds {s['lds']:4d} mov {s['mov']:4d} cndmask {s['cndmask']:4d} salu {s['salu']:4d} branch {s['branch']:3d} lanemov {s['lanemov']:3d}")
 
 
 if __name__ == "__main__":
