@@ -29,7 +29,8 @@ include/brs.h (libbrs_hip.so).  This package is the host-side mirror of the refe
     offpolicy.DeviceSACNets / DeviceSACLearner
                                            SAC on the same widths -- squashed-Gaussian actor, entropy target, the actor's chain through
                                            both critics, the learned temperature -- (include/brs_policy.h: brs_sac_*,
-                                           brs_ddpg_learner_create_sac): sb_rl.py's `-a SAC` with the DDPG net_arch
+                                           brs_ddpg_learner_create_sac): sb_rl.py's `-a SAC` with the DDPG net_arch, or with
+                                           net_arch="sb3" on SB3's default [256, 256], what `-a SAC` itself builds
     quant.quantize_policy / QuantPolicy    int8 post-training quantisation of the actor and the int8 network as a HIP kernel
                                            (include/brs_qpolicy.h): quantize_tflite.py and sb_rl.py:285-364 on the GPU
     quant.quantize_actor / QuantActor      the same deployment check for the actor DDPG, TD3 and SAC train, 6-300-200-2 with ReLU and

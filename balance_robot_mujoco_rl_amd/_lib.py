@@ -40,6 +40,9 @@ DDPG_TAG_ACT, DDPG_TAG_SAMPLE = 0x44445047, 0x5245504c
 TD3_TAG_NOISE = 0x5444334e                                      # BRS_TD3_TAG_NOISE
 SAC_NACTOR = 300 * 6 + 300 + 200 * 300 + 200 + 4 * 200 + 4      # BRS_SAC_NACTOR; the actor vector holds one more, log_ent_coef
 SAC_TAG_ACT, SAC_TAG_TARGET, SAC_TAG_PI = 0x53414341, 0x53414354, 0x53414350
+ARCH_REFERENCE, ARCH_SAC_DEFAULT = 0, 1                         # BRS_ARCH_*: pi=[300, 200] qf=[200, 150]; SB3's default [256, 256]
+SAC256_NACTOR = 256 * 6 + 256 + 256 * 256 + 256 + 4 * 256 + 4   # BRS_SAC256_NACTOR; the actor vector holds one more, log_ent_coef
+SAC256_NCRITIC = 256 * 8 + 256 + 256 * 256 + 256 + 1 * 256 + 1  # BRS_SAC256_NCRITIC
 
 
 class BrsConfig(C.Structure):
@@ -223,6 +226,8 @@ SIGNATURES = {
         "brs_ddpg_learner_create_sac": (C.c_int, [_i32, _i32, C.POINTER(_vp)]),
         "brs_sac_twin_critic_grad": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
         "brs_sac_actor_grad": (C.c_int, [_vp, _vp, _vp, _i32, _vp, C.c_uint64, C.c_uint32, _i32, _f32, _vp, _vp]),
+        "brs_ddpg_create_arch": (C.c_int, [_i32, _i32, C.POINTER(_vp)]),
+        "brs_ddpg_learner_create_sac_arch": (C.c_int, [_i32, _i32, _i32, C.POINTER(_vp)]),
     },
     "brs_render.h": {
         "brs_render_default_camera": (None, [C.POINTER(BrsCamera)]),

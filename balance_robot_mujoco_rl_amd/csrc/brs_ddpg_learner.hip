@@ -31,6 +31,11 @@
 // weight kernels are instantiated for the SAC actor with five per-sample sums behind b3 (the temperature's gradient and four
 // statistics).  SB3's 0.5
 // in front of the critic loss is a `loss_scale` at the head of ddpg_critic_backward_kernel; the DDPG / TD3 calls pass 1.
+// Architectures: every kernel of the SAC calls is a template over the networks it walks -- the critic's backward over
+// the critic and its scratch layout, the two kernels of the actor's chain over the architecture (brs_sac.hpp: ArchReference,
+// ArchSacDefault), the weight kernels over network and layout as before -- and ArchDims<A> holds what a handle of architecture A
+// needs; the handle remembers its architecture and the SAC calls dispatch on it.  The reference instantiations are the kernels
+// they were.
 // Padding: a row past m runs on zero inputs; its dq / dz3 is zero, so every product it enters is zero, and it is left out of the
 // statistics and of the 1 / m.  Padded units are zeros in the LDS image, their scratch rows are written (as zeros) by every call
 // and their gradient is never stored.  No floating-point atomic, no communication between workgroups.
@@ -51,6 +56,7 @@ using namespace brs::ddpg_learner;
 using namespace brs::ddpg_tile;
 using brs::learner::AdamScalars;
 using brs::sac::SacActor, brs::sac::SAC_TAIL, brs::sac::SAC_Z3_ROWS, brs::sac::SAC_ROW_LEN, brs::sac::SAC_NACTOR;
+using brs::sac::ArchReference, brs::sac::ArchSacDefault;
 
 // rows of a scratch image (each `ld` floats, ld = max_batch padded to the workgroup's 128 rows) sized for network N.  The single
 // calls use the actor's, the wider net, for both networks; the twin call keeps two images of the critic's back to back.
@@ -68,6 +74,24 @@ static_assert(SacActor::OUT + SAC_TAIL <= SAC_Z3_ROWS && Tile<SacActor>::H1P == 
 constexpr int SAC_SCRATCH_ROWS = SacLay::ROWS > TWIN_SCRATCH_ROWS ? SacLay::ROWS : TWIN_SCRATCH_ROWS;
 constexpr int SAC_PARTIAL_LEN = SAC_ROW_LEN > TWIN_PARTIAL_LEN ? SAC_ROW_LEN : TWIN_PARTIAL_LEN;
 constexpr int SAC_LDS_FLOATS = Tile<SacActor>::L_SIZE > LDS_FLOATS ? Tile<SacActor>::L_SIZE : LDS_FLOATS;
+constexpr int imax(int a, int b) { return a > b ? a : b; }
+// The same for the SAC calls of architecture A: the actor's image with its nine per-sample rows, two images of the
+// critic's back to back, the longer of the actor's and the twin row as a partial row, one LDS image for both networks.
+template <class A> struct ArchDims {
+  using Pi = typename A::Pi;
+  using Qf = typename A::Qf;
+  using PiLay = Layout<Pi, SAC_Z3_ROWS>;
+  using QfLay = Layout<Qf>;
+  static constexpr int ROW_LEN = nparam<Pi>() + SAC_TAIL, TWIN_ROW_LEN = 2 * nparam<Qf>() + BRS_TD3_NSTAT;
+  static constexpr int SCRATCH_ROWS = imax(PiLay::ROWS, 2 * QfLay::ROWS), PARTIAL = imax(ROW_LEN, TWIN_ROW_LEN);
+  static constexpr int LDS = imax(Tile<Pi>::L_SIZE, Tile<Qf>::L_SIZE);
+  static_assert(Pi::OUT + SAC_TAIL <= SAC_Z3_ROWS && Qf::OUT + NSTAT <= Z3_ROWS, "rows");
+  static_assert(2 * LDS * sizeof(float) <= 160 * 1024, "two workgroups per CU");
+};
+// the reference widths keep the sizes they had (a reference handle also serves the DDPG / TD3 calls: Wide fits in SacLay)
+static_assert(ArchDims<ArchReference>::SCRATCH_ROWS == SAC_SCRATCH_ROWS && ArchDims<ArchReference>::PARTIAL == SAC_PARTIAL_LEN &&
+              ArchDims<ArchReference>::LDS == SAC_LDS_FLOATS && ArchDims<ArchReference>::ROW_LEN == SAC_ROW_LEN &&
+              ArchDims<ArchReference>::TWIN_ROW_LEN == TWIN_LEN, "the reference architecture's sizes are unchanged");
 
 struct Scratch {
   float* base;
@@ -118,15 +142,15 @@ template <class Lay = Wide> struct StoreSink {
   __device__ __forceinline__ void dz1(int mt, int r, float v) { dz1col[UNIFORM_UNIT(mt, r) * ld] = v; }
 };
 // the critic inside the actor's chain: only d q / d action is wanted, da[k] = sum_u W1c[u][6 + k] dz1[u] over this half's units
-struct ActionSink {
+template <class Q = Critic> struct ActionSink {
   const float* W1;  // the critic's first layer in the LDS image
   float da[ACT];
   int h;
-  __device__ __forceinline__ ActionSink(const float* L) : W1(L + Tile<Critic>::L_W1), da{0.0f, 0.0f}, h(wave_half()) {}
+  __device__ __forceinline__ ActionSink(const float* L) : W1(L + Tile<Q>::L_W1), da{0.0f, 0.0f}, h(wave_half()) {}
   __device__ __forceinline__ void dz2(int, int, float) {}
   __device__ __forceinline__ void dz1(int mt, int r, float v) {
 #pragma unroll
-    for (int k = 0; k < ACT; k++) da[k] = fmaf(W1[(32 * mt + BRS_UNIT(r)) * Tile<Critic>::W1_LD + OBS + k], v, da[k]);
+    for (int k = 0; k < ACT; k++) da[k] = fmaf(W1[(32 * mt + BRS_UNIT(r)) * Tile<Q>::W1_LD + OBS + k], v, da[k]);
   }
 };
 
@@ -180,19 +204,20 @@ __device__ __forceinline__ void backward_tile(const float* __restrict__ w, float
 }
 
 // blockIdx.y: which of the critics laid back to back in `critics` (and which scratch image); one critic, one image in the single call
-template <class Lay> __global__ void __launch_bounds__(THREADS) ddpg_critic_backward_kernel(const float* __restrict__ critics, const int m,
-                                                                                            const float* __restrict__ obs, const float* __restrict__ act,
-                                                                                            const float* __restrict__ y, const Scratch all,
-                                                                                            const float loss_scale) {
-  __shared__ float L[Tile<Critic>::L_SIZE];
-  const float* __restrict__ critic = critics + (size_t)blockIdx.y * nparam<Critic>();
+template <class Q, class Lay> __global__ void __launch_bounds__(THREADS) ddpg_critic_backward_kernel(const float* __restrict__ critics, const int m,
+                                                                                                     const float* __restrict__ obs,
+                                                                                                     const float* __restrict__ act,
+                                                                                                     const float* __restrict__ y, const Scratch all,
+                                                                                                     const float loss_scale) {
+  __shared__ float L[Tile<Q>::L_SIZE];
+  const float* __restrict__ critic = critics + (size_t)blockIdx.y * nparam<Q>();
   const Scratch S = all.image(blockIdx.y, Lay::ROWS);
   const int i = tile_row();  // < gridDim.x * 128 <= S.ld
   float xb[(OBS + ACT) / 2], v[1];
   load_obs_operands(obs, m, i, xb);
   xb[OBS / 2] = i < m ? act[(size_t)ACT * i + wave_half()] : 0.0f;
-  Tape<Critic, true, Lay> tape(S, i);
-  forward_tile<Critic>(critic, L, xb, v, tape);
+  Tape<Q, true, Lay> tape(S, i);
+  forward_tile<Q>(critic, L, xb, v, tape);
   CriticHead hd = {0.0f, 0.0f, 0.0f};
   if (i < m) hd = brs::sac::scale_head(critic_head(v[0], y[i], 1.0f / (float)m), loss_scale);  // 1 (exact) but for SAC's 0.5
   if (finishes_row()) {
@@ -201,7 +226,7 @@ template <class Lay> __global__ void __launch_bounds__(THREADS) ddpg_critic_back
     S.row(Lay::Z3 + 2)[i] = hd.q;
   }
   const float dz3[1] = {hd.dq};
-  backward_tile<Critic, false>(critic, L, dz3, tape.g1, tape.g2, StoreSink<Lay>(S, i));
+  backward_tile<Q, false>(critic, L, dz3, tape.g1, tape.g2, StoreSink<Lay>(S, i));
 }
 
 __global__ void __launch_bounds__(THREADS) ddpg_actor_backward_kernel(const float* __restrict__ actor, const float* __restrict__ critic, const int m,
@@ -219,7 +244,7 @@ __global__ void __launch_bounds__(THREADS) ddpg_actor_backward_kernel(const floa
   forward_tile<Critic>(critic, L, xb, v, tc);
   const float inv_m = 1.0f / (float)m;
   const float dq[1] = {i < m ? actor_dq(inv_m) : 0.0f};
-  ActionSink to_action(L);
+  ActionSink<> to_action(L);
   backward_tile<Critic, false>(critic, L, dq, tc.g1, tc.g2, to_action);
   float dz3[ACT];
 #pragma unroll
@@ -236,33 +261,37 @@ __global__ void __launch_bounds__(THREADS) ddpg_actor_backward_kernel(const floa
 // SAC's actor chain up to dz3.  Both halves of a wave compute the row's Philox block and its sample: the action is the B operand of
 // both.  The critics are walked 0, 1 forward and 1, 0 backward, so that critic 1's resident image serves its own backward; the sink
 // adds both critics' d q / d action (the unselected one's is an exact zero: its dq is).
-__global__ void __launch_bounds__(THREADS) sac_actor_backward_kernel(const float* __restrict__ actor, const float* __restrict__ critics, const int m,
-                                                                     const float* __restrict__ obs, const uint64_t seed, const uint32_t draw,
-                                                                     const int learn_alpha, const float target_entropy, const Scratch S) {
-  __shared__ float L[SAC_LDS_FLOATS];
+template <class A> __global__ void __launch_bounds__(THREADS) sac_actor_backward_kernel(const float* __restrict__ actor, const float* __restrict__ critics,
+                                                                                       const int m, const float* __restrict__ obs, const uint64_t seed,
+                                                                                       const uint32_t draw, const int learn_alpha,
+                                                                                       const float target_entropy, const Scratch S) {
+  using Pi = typename A::Pi;
+  using Qf = typename A::Qf;
+  using PiLay = typename ArchDims<A>::PiLay;
+  __shared__ float L[ArchDims<A>::LDS];
   const int i = tile_row();
-  const float* __restrict__ critic1 = critics + nparam<Critic>();
-  float sb[OBS / 2], out[SacActor::OUT], z[ACT], q0[1], q1[1];
+  const float* __restrict__ critic1 = critics + nparam<Qf>();
+  float sb[OBS / 2], out[Pi::OUT], z[ACT], q0[1], q1[1];
   load_obs_operands(obs, m, i, sb);
-  Tape<SacActor, true, SacLay> ta(S, i);
-  forward_tile<SacActor>(actor, L, sb, out, ta);
+  Tape<Pi, true, PiLay> ta(S, i);
+  forward_tile<typename SeriesOf<A>::Pi>(actor, L, sb, out, ta);
   uint32_t o[4];
   brs::sac::sac_row_block(BRS_SAC_TAG_PI, seed, draw, (uint32_t)i, o);
   normal_pair(o[0], o[1], z);
   brs::sac::Sample sm;
   brs::sac::sample(out, z, sm);
   const float xb[(OBS + ACT) / 2] = {sb[0], sb[1], sb[2], wave_half() ? sm.a[1] : sm.a[0]};
-  Tape<Critic, false> tc0(S, i), tc1(S, i);
-  forward_tile<Critic>(critics, L, xb, q0, tc0);
-  forward_tile<Critic>(critic1, L, xb, q1, tc1);
+  Tape<Qf, false> tc0(S, i), tc1(S, i);
+  forward_tile<typename SeriesOf<A>::Qf>(critics, L, xb, q0, tc0);
+  forward_tile<typename SeriesOf<A>::Qf>(critic1, L, xb, q1, tc1);
   const bool live = i < m;
-  const float inv_m = 1.0f / (float)m, alpha = brs::sac::ent_coef(actor);
+  const float inv_m = 1.0f / (float)m, alpha = brs::sac::ent_coef_of<Pi>(actor);
   const int sel = brs::sac::min_select(q0[0], q1[0]);
   const float dq0[1] = {live && sel == 0 ? actor_dq(inv_m) : 0.0f}, dq1[1] = {live && sel == 1 ? actor_dq(inv_m) : 0.0f};
-  ActionSink to_action(L);
-  backward_tile<Critic, false>(critic1, L, dq1, tc1.g1, tc1.g2, to_action);
-  backward_tile<Critic, true>(critics, L, dq0, tc0.g1, tc0.g2, to_action);
-  float dz3[SacActor::OUT];
+  ActionSink<Qf> to_action(L);
+  backward_tile<Qf, false>(critic1, L, dq1, tc1.g1, tc1.g2, to_action);
+  backward_tile<Qf, true>(critics, L, dq0, tc0.g1, tc0.g2, to_action);
+  float dz3[Pi::OUT];
 #pragma unroll
   for (int k = 0; k < ACT; k++) {
     const float da = to_action.da[k] + __shfl_xor(to_action.da[k], 32, 64);
@@ -274,21 +303,23 @@ __global__ void __launch_bounds__(THREADS) sac_actor_backward_kernel(const float
     float share[SAC_TAIL];
     brs::sac::sac_shares(learn_alpha, target_entropy, alpha, sm.logp, sel ? q1[0] : q0[0], inv_m, share);
 #pragma unroll
-    for (int k = 0; k < SacActor::OUT; k++) S.row(SacLay::Z3 + k)[i] = dz3[k];
+    for (int k = 0; k < Pi::OUT; k++) S.row(PiLay::Z3 + k)[i] = dz3[k];
 #pragma unroll
-    for (int k = 0; k < SAC_TAIL; k++) S.row(SacLay::Z3 + SacActor::OUT + k)[i] = live ? share[k] : 0.0f;
+    for (int k = 0; k < SAC_TAIL; k++) S.row(PiLay::Z3 + Pi::OUT + k)[i] = live ? share[k] : 0.0f;
   }
 }
 
 // ... and the second launch: the actor's backward from what the first left in the scratch -- dz3 in its four per-sample rows, the
 // ReLU gates as the signs of the stored activations (relu_gate of the output is relu_gate of the pre-activation)
-__global__ void __launch_bounds__(THREADS) sac_actor_tail_kernel(const float* __restrict__ actor, const Scratch S) {
-  __shared__ float L[Tile<SacActor>::L_SIZE];
-  using T = Tile<SacActor>;
+template <class A> __global__ void __launch_bounds__(THREADS) sac_actor_tail_kernel(const float* __restrict__ actor, const Scratch S) {
+  using Pi = typename A::Pi;
+  using PiLay = typename ArchDims<A>::PiLay;
+  __shared__ float L[Tile<Pi>::L_SIZE];
+  using T = Tile<Pi>;
   const int i = tile_row();  // < gridDim.x * 128 <= S.ld: every row of the padded batch was written by the first launch
-  Tape<SacActor, false> ta(S, i);
-  const float* __restrict__ h1col = column(S, SacLay::H1, i);
-  const float* __restrict__ h2col = column(S, SacLay::H2, i);
+  Tape<Pi, false> ta(S, i);
+  const float* __restrict__ h1col = column(S, PiLay::H1, i);
+  const float* __restrict__ h2col = column(S, PiLay::H2, i);
 #pragma unroll
   for (int mt = 0; mt < T::MT1; mt++)
 #pragma unroll
@@ -299,10 +330,10 @@ __global__ void __launch_bounds__(THREADS) sac_actor_tail_kernel(const float* __
 #pragma unroll
     for (int r = 0; r < 16; r++)
       if (relu_gate(h2col[UNIFORM_UNIT(mt, r) * S.ld])) ta.g2[mt >> 1] |= 1u << (16 * (mt & 1) + r);
-  float dz3[SacActor::OUT];
+  float dz3[Pi::OUT];
 #pragma unroll
-  for (int k = 0; k < SacActor::OUT; k++) dz3[k] = S.row(SacLay::Z3 + k)[i];
-  backward_tile<SacActor, true>(actor, L, dz3, ta.g1, ta.g2, StoreSink<SacLay>(S, i));
+  for (int k = 0; k < Pi::OUT; k++) dz3[k] = S.row(PiLay::Z3 + k)[i];
+  backward_tile<Pi, true>(actor, L, dz3, ta.g1, ta.g2, StoreSink<PiLay>(S, i));
 }
 
 // where a workgroup row (blockIdx.y) of the two sample-contracting kernels reads and writes, for the network of its plane
@@ -444,10 +475,16 @@ struct brs_ddpg_learner {
   size_t bytes = 0;
   bool twin = false;         // from brs_ddpg_learner_create_twin: two critic images fit the rows, a twin row fits a partial row
   bool sac = false;          // from brs_ddpg_learner_create_sac: a twin handle that also fits the SAC actor's image and row
+  int arch = BRS_ARCH_REFERENCE;  // whose widths the SAC calls take; another than the reference's only with `sac`
   std::string err;
 };
 
 using brs::host::DeviceGuard, brs::host::fail;
+
+// the DDPG / TD3 calls exist at the reference widths only
+#define BRS_REFERENCE_ARCH_ONLY(l, who)                                                                                                  \
+  if ((l)->arch != BRS_ARCH_REFERENCE)                                                                                                   \
+    return fail(l, BRS_ERR_ARG, who ": the handle's architecture does not serve this call (DDPG and TD3 run at BRS_ARCH_REFERENCE only)")
 
 namespace {
 
@@ -464,10 +501,29 @@ template <class N, class Lay = Wide, int NETS = 1, int NS = NSTAT> void launch_w
   if (nsplit > 1) hipLaunchKernelGGL(ddpg_combine_kernel, dim3((len + 255) / 256), dim3(256), 0, s, l->partial, nsplit, len, grad);
 }
 
-int create(const char* who, bool twin, bool sac, int32_t device, int32_t max_batch, brs_ddpg_learner** out) {
+// the launches of the two SAC gradient calls for architecture A
+template <class A> void sac_twin_critic_launch(brs_ddpg_learner* l, const float* critics, int m, const float* obs, const float* act, const float* y,
+                                               float* grad, hipStream_t s) {
+  using Qf = typename A::Qf;
+  using QfLay = typename ArchDims<A>::QfLay;
+  hipLaunchKernelGGL((ddpg_critic_backward_kernel<Qf, QfLay>), dim3(pad128(m) / WG_ROWS, 2), dim3(THREADS), 0, s, critics, m, obs, act, y,
+                     Scratch{l->block, l->ld}, 0.5f);
+  launch_weight_kernels<Qf, QfLay, 2>(l, m, obs, act, grad, s);
+}
+template <class A> void sac_actor_launch(brs_ddpg_learner* l, const float* actor, const float* critics, int m, const float* obs, uint64_t seed,
+                                         uint32_t draw, int learn_alpha, float target_entropy, float* grad, hipStream_t s) {
+  using PiLay = typename ArchDims<A>::PiLay;
+  hipLaunchKernelGGL(sac_actor_backward_kernel<A>, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, actor, critics, m, obs, seed, draw, learn_alpha,
+                     target_entropy, Scratch{l->block, l->ld});
+  hipLaunchKernelGGL(sac_actor_tail_kernel<A>, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, actor, Scratch{l->block, l->ld});
+  launch_weight_kernels<typename A::Pi, PiLay, 1, SAC_TAIL>(l, m, obs, nullptr, grad, s);
+}
+
+int create(const char* who, bool twin, bool sac, int32_t device, int32_t max_batch, brs_ddpg_learner** out, int32_t arch = BRS_ARCH_REFERENCE) {
   const std::string w(who);
   if (!out) return fail<brs_ddpg_learner>(nullptr, BRS_ERR_ARG, w + ": null argument");
   *out = nullptr;
+  if (!brs::sac::known_arch(arch)) return fail<brs_ddpg_learner>(nullptr, BRS_ERR_ARG, w + ": unknown architecture");
   if (max_batch < 1 || max_batch > (1 << 22)) return fail<brs_ddpg_learner>(nullptr, BRS_ERR_ARG, w + ": max_batch must be in [1, 2^22]");
   std::string why;
   if (const int rc = brs::host::check_device(device, who, &why)) return fail<brs_ddpg_learner>(nullptr, rc, why);
@@ -479,8 +535,11 @@ int create(const char* who, bool twin, bool sac, int32_t device, int32_t max_bat
   l->ld = pad128(max_batch);
   l->twin = twin;
   l->sac = sac;
-  const size_t scratch = (size_t)(sac ? SAC_SCRATCH_ROWS : twin ? TWIN_SCRATCH_ROWS : SCRATCH_ROWS) * l->ld,
-               bytes = (scratch + (sac ? (size_t)MAX_SPLIT * SAC_PARTIAL_LEN : partial_floats(twin))) * sizeof(float);
+  l->arch = arch;
+  const bool wide = arch == BRS_ARCH_SAC_DEFAULT;  // (only with sac)
+  const size_t scratch = (size_t)(wide ? ArchDims<ArchSacDefault>::SCRATCH_ROWS : sac ? SAC_SCRATCH_ROWS : twin ? TWIN_SCRATCH_ROWS : SCRATCH_ROWS) * l->ld,
+               partial = wide ? (size_t)MAX_SPLIT * ArchDims<ArchSacDefault>::PARTIAL : sac ? (size_t)MAX_SPLIT * SAC_PARTIAL_LEN : partial_floats(twin),
+               bytes = (scratch + partial) * sizeof(float);
   if (hipMalloc((void**)&l->block, bytes) != hipSuccess || hipMemset(l->block, 0, bytes) != hipSuccess) {
     if (l->block) (void)hipFree(l->block);
     delete l;
@@ -506,6 +565,10 @@ int brs_ddpg_learner_create_twin(int32_t device, int32_t max_batch, brs_ddpg_lea
 
 int brs_ddpg_learner_create_sac(int32_t device, int32_t max_batch, brs_ddpg_learner** out) {
   return create("brs_ddpg_learner_create_sac", true, true, device, max_batch, out);
+}
+
+int brs_ddpg_learner_create_sac_arch(int32_t device, int32_t max_batch, int32_t arch, brs_ddpg_learner** out) {
+  return create("brs_ddpg_learner_create_sac_arch", true, true, device, max_batch, out, arch);
 }
 
 int brs_ddpg_learner_destroy(brs_ddpg_learner* l) {
@@ -534,11 +597,12 @@ int brs_ddpg_learner_critic_grad(brs_ddpg_learner* l, const float* critic_dev, i
   if (!critic_dev || !obs_dev || !act_dev || !y_dev || !grad_dev) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_critic_grad: null argument");
   if (m < 1) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_critic_grad: m must be at least 1");
   if (!l) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_critic_grad: null handle");
+  BRS_REFERENCE_ARCH_ONLY(l, "brs_ddpg_learner_critic_grad");
   if (m > l->max_batch) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_critic_grad: m exceeds the handle's max_batch");
   DeviceGuard g(l->device);
   if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_ddpg_learner_critic_grad: hipSetDevice failed");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ddpg_critic_backward_kernel<Wide>, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, critic_dev, m, obs_dev, act_dev, y_dev,
+  hipLaunchKernelGGL((ddpg_critic_backward_kernel<Critic, Wide>), dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, critic_dev, m, obs_dev, act_dev, y_dev,
                      Scratch{l->block, l->ld}, 1.0f);
   launch_weight_kernels<Critic>(l, m, obs_dev, act_dev, grad_dev, s);
   BRS_HIP_TRY(l, hipGetLastError());
@@ -551,14 +615,15 @@ int brs_ddpg_learner_twin_critic_grad(brs_ddpg_learner* l, const float* critics_
     return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: null argument");
   if (m < 1) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: m must be at least 1");
   if (!l) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: null handle");
+  BRS_REFERENCE_ARCH_ONLY(l, "brs_ddpg_learner_twin_critic_grad");
   if (!l->twin)
     return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: the handle was not created with brs_ddpg_learner_create_twin");
   if (m > l->max_batch) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: m exceeds the handle's max_batch");
   DeviceGuard g(l->device);
   if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_ddpg_learner_twin_critic_grad: hipSetDevice failed");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ddpg_critic_backward_kernel<Narrow>, dim3(pad128(m) / WG_ROWS, 2), dim3(THREADS), 0, s, critics_dev, m, obs_dev, act_dev,
-                     y_dev, Scratch{l->block, l->ld}, 1.0f);
+  hipLaunchKernelGGL((ddpg_critic_backward_kernel<Critic, Narrow>), dim3(pad128(m) / WG_ROWS, 2), dim3(THREADS), 0, s, critics_dev, m, obs_dev,
+                     act_dev, y_dev, Scratch{l->block, l->ld}, 1.0f);
   launch_weight_kernels<Critic, Narrow, 2>(l, m, obs_dev, act_dev, grad_dev, s);
   BRS_HIP_TRY(l, hipGetLastError());
   return BRS_OK;
@@ -574,9 +639,8 @@ int brs_sac_twin_critic_grad(brs_ddpg_learner* l, const float* critics_dev, int3
   DeviceGuard g(l->device);
   if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_sac_twin_critic_grad: hipSetDevice failed");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ddpg_critic_backward_kernel<Narrow>, dim3(pad128(m) / WG_ROWS, 2), dim3(THREADS), 0, s, critics_dev, m, obs_dev, act_dev,
-                     y_dev, Scratch{l->block, l->ld}, 0.5f);
-  launch_weight_kernels<Critic, Narrow, 2>(l, m, obs_dev, act_dev, grad_dev, s);
+  if (l->arch == BRS_ARCH_SAC_DEFAULT) sac_twin_critic_launch<ArchSacDefault>(l, critics_dev, m, obs_dev, act_dev, y_dev, grad_dev, s);
+  else sac_twin_critic_launch<ArchReference>(l, critics_dev, m, obs_dev, act_dev, y_dev, grad_dev, s);
   BRS_HIP_TRY(l, hipGetLastError());
   return BRS_OK;
 }
@@ -591,10 +655,10 @@ int brs_sac_actor_grad(brs_ddpg_learner* l, const float* actor_dev, const float*
   DeviceGuard g(l->device);
   if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_sac_actor_grad: hipSetDevice failed");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(sac_actor_backward_kernel, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, actor_dev, critics_dev, m, obs_dev, seed, draw,
-                     learn_alpha != 0, target_entropy, Scratch{l->block, l->ld});
-  hipLaunchKernelGGL(sac_actor_tail_kernel, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, actor_dev, Scratch{l->block, l->ld});
-  launch_weight_kernels<SacActor, SacLay, 1, SAC_TAIL>(l, m, obs_dev, nullptr, grad_dev, s);
+  if (l->arch == BRS_ARCH_SAC_DEFAULT)
+    sac_actor_launch<ArchSacDefault>(l, actor_dev, critics_dev, m, obs_dev, seed, draw, learn_alpha != 0, target_entropy, grad_dev, s);
+  else
+    sac_actor_launch<ArchReference>(l, actor_dev, critics_dev, m, obs_dev, seed, draw, learn_alpha != 0, target_entropy, grad_dev, s);
   BRS_HIP_TRY(l, hipGetLastError());
   return BRS_OK;
 }
@@ -604,6 +668,7 @@ int brs_ddpg_learner_actor_grad(brs_ddpg_learner* l, const float* actor_dev, con
   if (!actor_dev || !critic_dev || !obs_dev || !grad_dev) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_actor_grad: null argument");
   if (m < 1) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_actor_grad: m must be at least 1");
   if (!l) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_actor_grad: null handle");
+  BRS_REFERENCE_ARCH_ONLY(l, "brs_ddpg_learner_actor_grad");
   if (m > l->max_batch) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_actor_grad: m exceeds the handle's max_batch");
   DeviceGuard g(l->device);
   if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_ddpg_learner_actor_grad: hipSetDevice failed");

@@ -56,9 +56,27 @@ template <class N> __device__ __forceinline__ void stage_resident(const float* _
   if (threadIdx.x < 4) L[T::L_B3 + threadIdx.x] = threadIdx.x < N::OUT ? w[O::B3 + threadIdx.x] : 0.0f;
 }
 
+// InSeries<N>: network N in a kernel that runs several forwards of networks WITHOUT padded units one after the other (the
+// [256, 256] actor and its two critics of DESIGN.md 7.12: the SAC target and the SAC actor's chain).  The same network in every
+// respect; forward_tile<InSeries<N>> only fetches its chunks by another address form: one offset per thread plus a base that is the
+// same for the whole workgroup, and nothing to test.  With load_chunk's offset per word the compiler keeps the 32 offsets of every
+// chunk alive from one forward to the next of the same shape and spills them (128 registers in the target, 338 in the chain), and
+// every reload then waits in front of its global load.  A kernel with one forward is better off with the plain form (the
+// [256, 256] critic's backward kernel: no spill against 32), and so is backward_tile's rolled loop, where the 32 bases would be
+// computed at run time.
+template <class N> struct InSeries : N { static_assert(N::H1 % 32 == 0 && N::H2 % 32 == 0, "no padded unit"); };
+template <class N> struct in_series { static constexpr bool value = false; };
+template <class N> struct in_series<InSeries<N>> { static constexpr bool value = true; };
+
 // chunk ch of the second layer: W2[all units][32 ch .. 32 ch + 31]; word e of the chunk is unit e / 32, input 32 ch + e % 32
 // (a wave reads two 128-byte runs per instruction)
 template <class N> __device__ __forceinline__ void load_chunk(const float* __restrict__ w, const int ch, float (&reg)[Tile<N>::CH_PER_THREAD]) {
+  if constexpr (in_series<N>::value) {
+    const int mine = (threadIdx.x >> 5) * N::H1 + (threadIdx.x & 31);
+#pragma unroll
+    for (int j = 0; j < Tile<N>::CH_PER_THREAD; j++) reg[j] = (w + Offsets<N>::W2 + (THREADS / 32) * j * N::H1 + 32 * ch)[mine];
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < Tile<N>::CH_PER_THREAD; j++) {
     const int e = threadIdx.x + THREADS * j, u = e >> 5, k = 32 * ch + (e & 31);
@@ -167,6 +185,15 @@ __device__ __forceinline__ void load_obs_operands(const float* __restrict__ obs,
 #pragma unroll
   for (int s = 0; s < OBS / 2; s++) xb[s] = i < n ? obs[(size_t)OBS * i + 2 * s + wave_half()] : 0.0f;
 }
+
+// the networks of architecture A (brs_sac.hpp: Pi, Qf) as a kernel with several forwards names them: InSeries where no unit is
+// padded, the plain network otherwise (the reference widths: their instantiations are what they were)
+template <class N, bool PADDED = (N::H1 % 32 != 0 || N::H2 % 32 != 0)> struct series_net { using type = InSeries<N>; };
+template <class N> struct series_net<N, true> { using type = N; };
+template <class A> struct SeriesOf {
+  using Pi = typename series_net<typename A::Pi>::type;
+  using Qf = typename series_net<typename A::Qf>::type;
+};
 
 }  // namespace ddpg_tile
 }  // namespace brs

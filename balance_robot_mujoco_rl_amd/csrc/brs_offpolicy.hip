@@ -15,6 +15,8 @@
 // buffer after them, one barrier per chunk.  PADDING: padded units get zero weight rows, zero weight columns and zero bias in
 // the LDS image (written, not assumed), so a padded hidden unit is ReLU(0) = 0 and meets a zero column; rows past n are
 // computed on zero inputs (the matrix instructions need whole waves) and not stored.
+// Architectures: the SAC act, the SAC target and the critic's forward are templates over the networks of the handle's
+// architecture; SB3's default [256, 256] is eight tiles per layer with no padded unit (LDS image 80,912 bytes: two workgroups per CU).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -30,9 +32,15 @@ namespace {
 
 using namespace brs::offpolicy;
 using namespace brs::ddpg_tile;
-using brs::sac::SacActor;
+using brs::sac::SacActor, brs::sac::ArchReference, brs::sac::ArchSacDefault;
 constexpr int SAC_LDS_FLOATS = Tile<SacActor>::L_SIZE > LDS_FLOATS ? Tile<SacActor>::L_SIZE : LDS_FLOATS;
 static_assert(Tile<SacActor>::L_SIZE == Tile<Actor>::L_SIZE + 2 * Tile<Actor>::H2P && SAC_LDS_FLOATS * sizeof(float) <= 160 * 1024, "LDS");
+// the LDS image of architecture A's SAC kernels: its actor's and its critic's forwards share it one after the other
+template <class A> constexpr int sac_lds_floats() {
+  return Tile<typename A::Pi>::L_SIZE > Tile<typename A::Qf>::L_SIZE ? Tile<typename A::Pi>::L_SIZE : Tile<typename A::Qf>::L_SIZE;
+}
+// (two workgroups of the [256, 256] actor's 80,912 bytes still fit a CU's 160 KB)
+static_assert(sac_lds_floats<ArchReference>() == SAC_LDS_FLOATS && 2 * sac_lds_floats<ArchSacDefault>() * sizeof(float) <= 160 * 1024, "LDS");
 
 __global__ void __launch_bounds__(THREADS) ddpg_act_kernel(const float* __restrict__ actor, const int n, const float* __restrict__ obs,
                                                            const uint64_t seed, const int64_t gid_base, const uint32_t step, const float sigma,
@@ -70,14 +78,14 @@ __global__ void __launch_bounds__(256) ddpg_random_kernel(const int n, const uin
   }
 }
 
-__global__ void __launch_bounds__(THREADS) ddpg_q_kernel(const float* __restrict__ critic, const int n, const float* __restrict__ obs,
-                                                         const float* __restrict__ act, float* __restrict__ q) {
-  __shared__ float L[Tile<Critic>::L_SIZE];
+template <class Q> __global__ void __launch_bounds__(THREADS) ddpg_q_kernel(const float* __restrict__ critic, const int n, const float* __restrict__ obs,
+                                                                           const float* __restrict__ act, float* __restrict__ q) {
+  __shared__ float L[Tile<Q>::L_SIZE];
   const int i = tile_row();
   float xb[(OBS + ACT) / 2], v[1];
   load_obs_operands(obs, n, i, xb);
   xb[OBS / 2] = i < n ? act[(size_t)ACT * i + wave_half()] : 0.0f;
-  forward_tile<Critic>(critic, L, xb, v);
+  forward_tile<Q>(critic, L, xb, v);
   if (i < n && finishes_row()) q[i] = v[0];
 }
 
@@ -122,16 +130,19 @@ __global__ void __launch_bounds__(THREADS) td3_td_target_kernel(const float* __r
   }
 }
 
-// SAC's actor: the forward with four outputs, then the per-row tail of brs_sac.hpp
-__global__ void __launch_bounds__(THREADS) sac_act_kernel(const float* __restrict__ actor, const int n, const float* __restrict__ obs,
-                                                          const uint64_t seed, const int64_t gid_base, const uint32_t step, const int deterministic,
-                                                          float* __restrict__ action, float* __restrict__ mu, float* __restrict__ log_std,
-                                                          float* __restrict__ noise) {
-  __shared__ float L[Tile<SacActor>::L_SIZE];
+// SAC's actor: the forward with four outputs, then the per-row tail of brs_sac.hpp; A: the handle's architecture
+// 
+template <class A> __global__ void __launch_bounds__(THREADS) sac_act_kernel(const float* __restrict__ actor, const int n, const float* __restrict__ obs,
+                                                                            const uint64_t seed, const int64_t gid_base, const uint32_t step,
+                                                                            const int deterministic, float* __restrict__ action,
+                                                                            float* __restrict__ mu, float* __restrict__ log_std,
+                                                                            float* __restrict__ noise) {
+  using Pi = typename A::Pi;
+  __shared__ float L[Tile<Pi>::L_SIZE];
   const int i = tile_row();
-  float xb[OBS / 2], out[SacActor::OUT];
+  float xb[OBS / 2], out[Pi::OUT];
   load_obs_operands(obs, n, i, xb);
-  forward_tile<SacActor>(actor, L, xb, out);
+  forward_tile<Pi>(actor, L, xb, out);
   if (i >= n || !finishes_row()) return;
   float a[ACT], m[ACT], ls[ACT], z[ACT];
   brs::sac::sac_act_tail(seed, gid_base + (int64_t)i, step, deterministic, 0, out, a, m, ls, z);
@@ -162,27 +173,31 @@ __global__ void __launch_bounds__(256) sac_random_kernel(const int n, const uint
 }
 
 // SAC's target: the CURRENT actor -> sample and logp -> target critic 0 -> target critic 1 -> minimum, entropy term, combine in one
-// launch; the three forwards share the LDS image one after the other.  alpha = exp(actor[BRS_SAC_NACTOR]) is read here.
-__global__ void __launch_bounds__(THREADS) sac_td_target_kernel(const float* __restrict__ actor, const float* __restrict__ critics_t, const int m,
-                                                                const float* __restrict__ next_obs, const float* __restrict__ reward,
-                                                                const uint8_t* __restrict__ done, const float gamma, const uint64_t seed,
-                                                                const uint32_t draw, float* __restrict__ y, float* __restrict__ next_action,
-                                                                float* __restrict__ logp, float* __restrict__ noise) {
-  __shared__ float L[SAC_LDS_FLOATS];
+// launch; the three forwards share the LDS image one after the other.  alpha = exp(log_ent_coef), the element behind the actor's b3,
+// is read here.
+template <class A> __global__ void __launch_bounds__(THREADS) sac_td_target_kernel(const float* __restrict__ actor, const float* __restrict__ critics_t,
+                                                                                  const int m, const float* __restrict__ next_obs,
+                                                                                  const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                                                  const float gamma, const uint64_t seed, const uint32_t draw,
+                                                                                  float* __restrict__ y, float* __restrict__ next_action,
+                                                                                  float* __restrict__ logp, float* __restrict__ noise) {
+  using Pi = typename A::Pi;
+  using Qf = typename A::Qf;
+  __shared__ float L[sac_lds_floats<A>()];
   const int i = tile_row();
-  float sb[OBS / 2], out[SacActor::OUT], z[ACT], q1[1], q2[1];
+  float sb[OBS / 2], out[Pi::OUT], z[ACT], q1[1], q2[1];
   load_obs_operands(next_obs, m, i, sb);
-  forward_tile<SacActor>(actor, L, sb, out);
+  forward_tile<typename SeriesOf<A>::Pi>(actor, L, sb, out);
   uint32_t o[4];
   brs::sac::sac_row_block(BRS_SAC_TAG_TARGET, seed, draw, (uint32_t)i, o);
   normal_pair(o[0], o[1], z);
   brs::sac::Sample sm;
   brs::sac::sample(out, z, sm);
   const float xb[(OBS + ACT) / 2] = {sb[0], sb[1], sb[2], wave_half() ? sm.a[1] : sm.a[0]};
-  forward_tile<Critic>(critics_t, L, xb, q1);
-  forward_tile<Critic>(critics_t + nparam<Critic>(), L, xb, q2);
+  forward_tile<typename SeriesOf<A>::Qf>(critics_t, L, xb, q1);
+  forward_tile<typename SeriesOf<A>::Qf>(critics_t + nparam<Qf>(), L, xb, q2);
   if (i >= m || !finishes_row()) return;
-  y[i] = brs::sac::sac_combine(reward[i], done[i], gamma, q1[0], q2[0], brs::sac::ent_coef(actor), sm.logp);
+  y[i] = brs::sac::sac_combine(reward[i], done[i], gamma, q1[0], q2[0], brs::sac::ent_coef_of<Pi>(actor), sm.logp);
   if (logp) logp[i] = sm.logp;
 #pragma unroll
   for (int k = 0; k < ACT; k++) {
@@ -267,23 +282,36 @@ bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0;
 
 struct brs_ddpg {
   int device = 0;
+  int arch = BRS_ARCH_REFERENCE;  // whose widths the SAC calls and brs_ddpg_q take
   std::string err;
 };
 
 using brs::host::DeviceGuard, brs::host::fail;
 
+// the DDPG / TD3 calls exist at the reference widths only
+#define BRS_REFERENCE_ARCH_ONLY(d, who)                                                                                                  \
+  if ((d)->arch != BRS_ARCH_REFERENCE)                                                                                                   \
+    return fail(d, BRS_ERR_ARG, who ": the handle's architecture does not serve this call (DDPG and TD3 run at BRS_ARCH_REFERENCE only)")
+
 extern "C" {
 
-int brs_ddpg_create(int32_t device, brs_ddpg** out) {
-  if (!out) return fail<brs_ddpg>(nullptr, BRS_ERR_ARG, "brs_ddpg_create: null argument");
+static int create_ddpg(const char* who, int32_t device, int32_t arch, brs_ddpg** out) {
+  const std::string w(who);
+  if (!out) return fail<brs_ddpg>(nullptr, BRS_ERR_ARG, w + ": null argument");
   *out = nullptr;
+  if (!brs::sac::known_arch(arch)) return fail<brs_ddpg>(nullptr, BRS_ERR_ARG, w + ": unknown architecture");
   std::string why;
-  if (const int rc = brs::host::check_device(device, "brs_ddpg_create", &why)) return fail<brs_ddpg>(nullptr, rc, why);
+  if (const int rc = brs::host::check_device(device, who, &why)) return fail<brs_ddpg>(nullptr, rc, why);
   brs_ddpg* d = new brs_ddpg();
   d->device = device;
+  d->arch = arch;
   *out = d;
   return BRS_OK;
 }
+
+int brs_ddpg_create(int32_t device, brs_ddpg** out) { return create_ddpg("brs_ddpg_create", device, BRS_ARCH_REFERENCE, out); }
+
+int brs_ddpg_create_arch(int32_t device, int32_t arch, brs_ddpg** out) { return create_ddpg("brs_ddpg_create_arch", device, arch, out); }
 
 int brs_ddpg_destroy(brs_ddpg* d) {
   if (!d) return BRS_ERR_STATE;
@@ -300,6 +328,7 @@ int brs_ddpg_act(brs_ddpg* d, const float* actor_dev, int32_t n, const float* ob
   if (!(sigma >= 0.0f)) return fail(d, BRS_ERR_ARG, "brs_ddpg_act: sigma must be >= 0");
   if (!action_dev || (!random && (!actor_dev || !obs_dev))) return fail(d, BRS_ERR_ARG, "brs_ddpg_act: null argument");
   if (!d) return fail(d, BRS_ERR_ARG, "brs_ddpg_act: null handle");
+  BRS_REFERENCE_ARCH_ONLY(d, "brs_ddpg_act");
   DeviceGuard g(d->device);
   if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_ddpg_act: hipSetDevice failed");
   if (random)
@@ -318,7 +347,11 @@ int brs_ddpg_q(brs_ddpg* d, const float* critic_dev, int32_t n, const float* obs
   if (!d) return fail(d, BRS_ERR_ARG, "brs_ddpg_q: null handle");
   DeviceGuard g(d->device);
   if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_ddpg_q: hipSetDevice failed");
-  hipLaunchKernelGGL(ddpg_q_kernel, dim3((n + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, critic_dev, n, obs_dev, act_dev, q_dev);
+  const dim3 grid((n + WG_ROWS - 1) / WG_ROWS);
+  if (d->arch == BRS_ARCH_SAC_DEFAULT)
+    hipLaunchKernelGGL(ddpg_q_kernel<Critic256>, grid, dim3(THREADS), 0, (hipStream_t)stream, critic_dev, n, obs_dev, act_dev, q_dev);
+  else
+    hipLaunchKernelGGL(ddpg_q_kernel<Critic>, grid, dim3(THREADS), 0, (hipStream_t)stream, critic_dev, n, obs_dev, act_dev, q_dev);
   BRS_HIP_TRY(d, hipGetLastError());
   return BRS_OK;
 }
@@ -329,6 +362,7 @@ int brs_ddpg_td_target(brs_ddpg* d, const float* actor_target_dev, const float* 
   if (!actor_target_dev || !critic_target_dev || !next_obs_dev || !reward_dev || !done_dev || !y_dev)
     return fail(d, BRS_ERR_ARG, "brs_ddpg_td_target: null argument");
   if (!d) return fail(d, BRS_ERR_ARG, "brs_ddpg_td_target: null handle");
+  BRS_REFERENCE_ARCH_ONLY(d, "brs_ddpg_td_target");
   DeviceGuard g(d->device);
   if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_ddpg_td_target: hipSetDevice failed");
   hipLaunchKernelGGL(ddpg_td_target_kernel, dim3((m + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_target_dev,
@@ -344,6 +378,7 @@ int brs_td3_td_target(brs_ddpg* d, const float* actor_target_dev, const float* c
                                                   noise_clip, y_dev))
     return fail(d, BRS_ERR_ARG, std::string("brs_td3_td_target: ") + why);
   if (!d) return fail(d, BRS_ERR_ARG, "brs_td3_td_target: null handle");
+  BRS_REFERENCE_ARCH_ONLY(d, "brs_td3_td_target");
   DeviceGuard g(d->device);
   if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_td3_td_target: hipSetDevice failed");
   hipLaunchKernelGGL(td3_td_target_kernel, dim3((m + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_target_dev,
@@ -363,9 +398,12 @@ int brs_sac_act(brs_ddpg* d, const float* actor_dev, int32_t n, const float* obs
   if (random)
     hipLaunchKernelGGL(sac_random_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, env_index_base, step, action_dev,
                        mu_dev, log_std_dev, z_dev);
+  else if (d->arch == BRS_ARCH_SAC_DEFAULT)
+    hipLaunchKernelGGL(sac_act_kernel<ArchSacDefault>, dim3((n + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_dev, n,
+                       obs_dev, seed, env_index_base, step, deterministic != 0, action_dev, mu_dev, log_std_dev, z_dev);
   else
-    hipLaunchKernelGGL(sac_act_kernel, dim3((n + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_dev, n, obs_dev, seed,
-                       env_index_base, step, deterministic != 0, action_dev, mu_dev, log_std_dev, z_dev);
+    hipLaunchKernelGGL(sac_act_kernel<ArchReference>, dim3((n + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_dev, n,
+                       obs_dev, seed, env_index_base, step, deterministic != 0, action_dev, mu_dev, log_std_dev, z_dev);
   BRS_HIP_TRY(d, hipGetLastError());
   return BRS_OK;
 }
@@ -378,8 +416,13 @@ int brs_sac_td_target(brs_ddpg* d, const float* actor_dev, const float* critics_
   if (!d) return fail(d, BRS_ERR_ARG, "brs_sac_td_target: null handle");
   DeviceGuard g(d->device);
   if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_sac_td_target: hipSetDevice failed");
-  hipLaunchKernelGGL(sac_td_target_kernel, dim3((m + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_dev,
-                     critics_target_dev, m, next_obs_dev, reward_dev, done_dev, gamma, seed, draw, y_dev, next_action_dev, logp_dev, z_dev);
+  const dim3 grid((m + WG_ROWS - 1) / WG_ROWS);
+  if (d->arch == BRS_ARCH_SAC_DEFAULT)
+    hipLaunchKernelGGL(sac_td_target_kernel<ArchSacDefault>, grid, dim3(THREADS), 0, (hipStream_t)stream, actor_dev, critics_target_dev, m,
+                       next_obs_dev, reward_dev, done_dev, gamma, seed, draw, y_dev, next_action_dev, logp_dev, z_dev);
+  else
+    hipLaunchKernelGGL(sac_td_target_kernel<ArchReference>, grid, dim3(THREADS), 0, (hipStream_t)stream, actor_dev, critics_target_dev, m,
+                       next_obs_dev, reward_dev, done_dev, gamma, seed, draw, y_dev, next_action_dev, logp_dev, z_dev);
   BRS_HIP_TRY(d, hipGetLastError());
   return BRS_OK;
 }

@@ -20,6 +20,9 @@ struct Actor { static constexpr int IN = OBS, H1 = 300, H2 = 200, OUT = ACT; sta
 struct Critic { static constexpr int IN = OBS + ACT, H1 = 200, H2 = 150, OUT = 1; static constexpr bool TANH = false; };
 template <class N> constexpr int nparam() { return N::H1 * N::IN + N::H1 + N::H2 * N::H1 + N::H2 + N::OUT * N::H2 + N::OUT; }
 static_assert(nparam<Actor>() == BRS_DDPG_NACTOR && nparam<Critic>() == BRS_DDPG_NCRITIC, "include/brs_policy.h");
+// BRS_ARCH_SAC_DEFAULT: SB3's default net_arch = [256, 256]; eight 32-unit tiles per layer, no padded unit
+struct Critic256 { static constexpr int IN = OBS + ACT, H1 = 256, H2 = 256, OUT = 1; static constexpr bool TANH = false; };
+static_assert(nparam<Critic256>() == BRS_SAC256_NCRITIC, "include/brs_policy.h");
 // offsets of the blocks of a flat parameter vector: W1[H1][IN] b1[H1] W2[H2][H1] b2[H2] W3[OUT][H2] b3[OUT]
 template <class N> struct Offsets {
   static constexpr int W1 = 0, B1 = W1 + N::H1 * N::IN, W2 = B1 + N::H1, B2 = W2 + N::H2 * N::H1, W3 = B2 + N::H2, B3 = W3 + N::OUT * N::H2;

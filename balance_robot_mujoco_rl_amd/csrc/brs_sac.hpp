@@ -1,4 +1,5 @@
-// brs_sac.hpp -- SAC on the DDPG widths (include/brs_policy.h: brs_sac_*), the part shared by the HIP kernels
+// brs_sac.hpp -- SAC on the DDPG widths and on SB3's default [256, 256] (include/brs_policy.h: brs_sac_*, BRS_ARCH_*; DESIGN.md 7.8,
+// 7.12), the part shared by the HIP kernels
 // (brs_offpolicy.hip: act and target; brs_ddpg_learner.hip: the actor's chain) and the host build the CPU tests hold against fp64
 // torch autograd (tests/sachost): the shape of the squashed-Gaussian actor, the Philox blocks of the three noise streams, and
 // everything that is not a matrix product -- the log-std clamp and its gate, the sample, logp, the two dz3 formulas, the
@@ -19,6 +20,14 @@ struct SacActor { static constexpr int IN = OBS, H1 = 300, H2 = 200, OUT = 2 * A
 constexpr int SAC_NACTOR = nparam<SacActor>();        // the actor VECTOR has one more element: log_ent_coef
 static_assert(SAC_NACTOR == BRS_SAC_NACTOR, "include/brs_policy.h");
 constexpr int SAC_NSTAT = BRS_SAC_NSTAT;
+// ... and with SB3's default net_arch = [256, 256]
+struct SacActor256 { static constexpr int IN = OBS, H1 = 256, H2 = 256, OUT = 2 * ACT; static constexpr bool TANH = false; };
+static_assert(nparam<SacActor256>() == BRS_SAC256_NACTOR && SacActor256::OUT == SacActor::OUT, "include/brs_policy.h");
+// an architecture: the SAC actor and the critic of a handle.  Kernels and host loops are templates over it; the per-row
+// arithmetic below does not depend on the widths.
+struct ArchReference { static constexpr int ID = BRS_ARCH_REFERENCE; using Pi = SacActor; using Qf = Critic; };
+struct ArchSacDefault { static constexpr int ID = BRS_ARCH_SAC_DEFAULT; using Pi = SacActor256; using Qf = Critic256; };
+inline bool known_arch(int32_t arch) { return arch == BRS_ARCH_REFERENCE || arch == BRS_ARCH_SAC_DEFAULT; }
 // the per-sample rows next to the hidden ones: dz3[4], the temperature's gradient share, then the SAC_NSTAT statistics; in the
 // gradient buffer the last five follow b3 directly (b3 is the last parameter block)
 constexpr int SAC_TAIL = 1 + SAC_NSTAT, SAC_Z3_ROWS = SacActor::OUT + SAC_TAIL, SAC_ROW_LEN = SAC_NACTOR + SAC_TAIL;
@@ -37,6 +46,7 @@ BRS_HD void sac_row_block(uint32_t tag, uint64_t seed, uint32_t draw, uint32_t j
 BRS_HD float clamp_log_std(float raw) { return clip_keep_nan(raw, LOG_STD_MIN, LOG_STD_MAX); }  // a NaN stays, as torch.clamp
 BRS_HD bool log_std_gate(float raw) { return raw >= LOG_STD_MIN && raw <= LOG_STD_MAX; }
 BRS_HD float ent_coef(const float* actor) { return expf(actor[SAC_NACTOR]); }
+template <class P> BRS_HD float ent_coef_of(const float* actor) { return expf(actor[nparam<P>()]); }  // log_ent_coef follows actor P's b3
 
 // u = mu + sigma z: a product and a sum, on the device as on the host
 BRS_HD float pre_squash(float mu, float sigma, float z) {

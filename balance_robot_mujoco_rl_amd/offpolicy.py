@@ -79,13 +79,36 @@ def unflatten_ddpg_state_dict(flat, net="actor", naming="sb3"):
 TD3_CRITIC_NAMINGS = {"sb3": "{net}.qf{k}.{i}.", "tool": "{net}.{k}.{i}."}
 
 
-def _td3_layout(net, naming):
+# SB3's default net_arch = [256, 256] (BRS_ARCH_SAC_DEFAULT) next to the reference's widths
+CRITIC256_SHAPES = [((256, 8), (256,)), ((256, 256), (256,)), ((1, 256), (1,))]
+NCRITIC256 = _lib.SAC256_NCRITIC
+_CRITIC_WIDTHS = ((NCRITIC, CRITIC_SHAPES), (NCRITIC256, CRITIC256_SHAPES))
+
+
+def _td3_layout(net, naming, shapes=None):
     if net not in ("critic", "critic_target"):
         raise ValueError(f"net must be 'critic' or 'critic_target', got {net!r}")
     if naming not in TD3_CRITIC_NAMINGS:
         raise ValueError(f"naming must be 'sb3' or 'tool', got {naming!r}")
-    return [(TD3_CRITIC_NAMINGS[naming].format(net=net, k=k, i=i) + kind, shape) for k in (0, 1) for i, pair in zip(_LAYER_INDEX, CRITIC_SHAPES)
-            for kind, shape in zip(("weight", "bias"), pair)]
+    return [(TD3_CRITIC_NAMINGS[naming].format(net=net, k=k, i=i) + kind, shape) for k in (0, 1)
+            for i, pair in zip(_LAYER_INDEX, CRITIC_SHAPES if shapes is None else shapes) for kind, shape in zip(("weight", "bias"), pair)]
+
+
+def _widths_of(sd, layouts, what):
+    """the first of `layouts` (lists of (name, shape)) whose every tensor is in `sd` with its shape; ValueError naming the first
+    tensor that is missing or fits none of them"""
+    for name, _ in layouts[0]:
+        if name not in sd:
+            raise ValueError(f"{name}: missing")
+    for layout in layouts:
+        if all(tuple(sd[name].shape) == shape for name, shape in layout):
+            return layout
+    for i, (name, shape) in enumerate(layouts[0]):
+        if not any(tuple(sd[name].shape) == layout[i][1] for layout in layouts):
+            expected = " or ".join(str(layout[i][1]) for layout in layouts)
+            raise ValueError(f"{name}: expected shape {expected}, got {tuple(sd[name].shape)}")
+    name = next(name for i, (name, shape) in enumerate(layouts[0]) if tuple(sd[name].shape) != shape)
+    raise ValueError(f"{name}: shape {tuple(sd[name].shape)} mixes the widths of two architectures of {what}")
 
 
 def _td3_naming_of(sd, net):
@@ -101,28 +124,28 @@ def flatten_td3_critics(sd, net="critic"):
     """state_dict -> the flat float32 vector [2 NCRITIC] of TD3's two critics, critic 0 then critic 1, each in the critic's flat
     order.  `net`: 'critic' or 'critic_target'.  Two namings are understood: SB3's TD3Policy (critic.qf0.{0,2,4}.{weight,bias} and
     critic.qf1.*) and tools/train_td3_torch.py's, an nn.ModuleList of two nn.Sequential (critic.0.{0,2,4}.{weight,bias} and
-    critic.1.*)."""
+    critic.1.*).  The widths are read off the shapes: qf=[200, 150], or SB3's default [256, 256] -> [2 NCRITIC256]."""
+    naming = _td3_naming_of(sd, net)
+    layout = _widths_of(sd, [_td3_layout(net, naming, shapes) for _, shapes in _CRITIC_WIDTHS], "the critics")
     parts = []
-    for name, shape in _td3_layout(net, _td3_naming_of(sd, net)):
-        if name not in sd:
-            raise ValueError(f"{name}: missing")
+    for name, shape in layout:
         a = sd[name]
         a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-        if tuple(a.shape) != shape:
-            raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
         parts.append(a.astype(np.float32).ravel())
     flat = np.concatenate(parts)
-    assert flat.size == 2 * NCRITIC
+    assert flat.size in (2 * NCRITIC, 2 * NCRITIC256)
     return flat
 
 
 def unflatten_td3_critics(flat, net="critic", naming="sb3"):
-    """the flat vector [2 NCRITIC] of the two critics -> {name: tensor} in `naming` ('sb3' or 'tool', as flatten_td3_critics)"""
+    """the flat vector [2 NCRITIC] (or [2 NCRITIC256]: the widths follow the length) of the two critics -> {name: tensor} in
+    `naming` ('sb3' or 'tool', as flatten_td3_critics)"""
     flat = np.ascontiguousarray(flat.detach().cpu().numpy() if hasattr(flat, "detach") else flat, dtype=np.float32)
-    if flat.shape != (2 * NCRITIC,):
-        raise ValueError(f"{net}: expected {2 * NCRITIC} parameters, got shape {flat.shape}")
+    shapes = next((shapes for n, shapes in _CRITIC_WIDTHS if flat.shape == (2 * n,)), None)
+    if shapes is None:
+        raise ValueError(f"{net}: expected {2 * NCRITIC} or {2 * NCRITIC256} parameters, got shape {flat.shape}")
     out, at = {}, 0
-    for name, shape in _td3_layout(net, naming):
+    for name, shape in _td3_layout(net, naming, shapes):
         k = int(np.prod(shape))
         out[name] = torch.from_numpy(flat[at:at + k].reshape(shape).copy())
         at += k
@@ -572,6 +595,31 @@ SAC_GRAD_LEN = SAC_NACTOR + 1 + _lib.SAC_NSTAT
 SAC_ACTOR_NAMINGS = {"sb3": ("actor.latent_pi.0.", "actor.latent_pi.2.", "actor.mu.", "actor.log_std."),
                      "tool": ("actor.body.0.", "actor.body.2.", "actor.mu.", "actor.log_std.")}
 _SAC_LAYER_SHAPES = (((300, 6), (300,)), ((200, 300), (200,)), ((2, 200), (2,)), ((2, 200), (2,)))
+_SAC256_LAYER_SHAPES = (((256, 6), (256,)), ((256, 256), (256,)), ((2, 256), (2,)), ((2, 256), (2,)))
+SAC256_NACTOR = _lib.SAC256_NACTOR
+_SAC_ACTOR_WIDTHS = ((SAC_NACTOR, _SAC_LAYER_SHAPES), (SAC256_NACTOR, _SAC256_LAYER_SHAPES))
+
+
+class SacArch:
+    """one network architecture of the SAC path (include/brs_policy.h: BRS_ARCH_*): its id and the lengths of its vectors"""
+
+    def __init__(self, name, arch_id, nactor, ncritic):
+        self.name, self.id, self.nactor, self.ncritic = name, arch_id, nactor, ncritic
+        self.grad_len = nactor + 1 + _lib.SAC_NSTAT
+
+
+# net_arch -> architecture: 'reference' is the reference's DDPG widths pi=[300, 200], qf=[200, 150]; 'sb3' is SB3's default
+# [256, 256], what SAC("MlpPolicy", env) builds.  (TD3's default [400, 300] would be a third entry and a third set of kernels.)
+SAC_ARCHS = {"reference": SacArch("reference", _lib.ARCH_REFERENCE, SAC_NACTOR, NCRITIC),
+             "sb3": SacArch("sb3", _lib.ARCH_SAC_DEFAULT, SAC256_NACTOR, NCRITIC256)}
+
+
+def sac_arch(net_arch):
+    if isinstance(net_arch, SacArch):
+        return net_arch
+    if net_arch not in SAC_ARCHS:
+        raise ValueError(f"net_arch must be 'reference' or 'sb3', got {net_arch!r}")
+    return SAC_ARCHS[net_arch]
 
 
 def _sac_naming_of(sd):
@@ -582,19 +630,16 @@ def _sac_naming_of(sd):
 
 
 def flatten_sac_actor(sd):
-    """state_dict in either naming, with a scalar `log_ent_coef` in it -> the flat float32 actor vector [SAC_NACTOR + 1]"""
+    """state_dict in either naming, with a scalar `log_ent_coef` in it -> the flat float32 actor vector [SAC_NACTOR + 1], or
+    [SAC256_NACTOR + 1] for SB3's default [256, 256]: the widths are read off the shapes"""
     prefixes = SAC_ACTOR_NAMINGS[_sac_naming_of(sd)]
+    layouts = [[(prefix + kind, shape) for prefix, pair in zip(prefixes, shapes) for kind, shape in zip(("weight", "bias"), pair)]
+               for _, shapes in _SAC_ACTOR_WIDTHS]
     got = {}
-    for prefix, (wshape, bshape) in zip(prefixes, _SAC_LAYER_SHAPES):
-        for kind, shape in (("weight", wshape), ("bias", bshape)):
-            name = prefix + kind
-            if name not in sd:
-                raise ValueError(f"{name}: missing")
-            a = sd[name]
-            a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-            if tuple(a.shape) != shape:
-                raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
-            got[name] = a.astype(np.float32)
+    for name, shape in _widths_of(sd, layouts, "the SAC actor"):
+        a = sd[name]
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        got[name] = a.astype(np.float32)
     if "log_ent_coef" not in sd:
         raise ValueError("log_ent_coef: missing")
     t = sd["log_ent_coef"]
@@ -605,15 +650,17 @@ def flatten_sac_actor(sd):
     flat = np.concatenate([got[p[0] + "weight"].ravel(), got[p[0] + "bias"], got[p[1] + "weight"].ravel(), got[p[1] + "bias"],
                            got[p[2] + "weight"].ravel(), got[p[3] + "weight"].ravel(), got[p[2] + "bias"], got[p[3] + "bias"],
                            t.astype(np.float32).ravel()])
-    assert flat.size == SAC_NACTOR + 1
+    assert flat.size in (SAC_NACTOR + 1, SAC256_NACTOR + 1)
     return flat
 
 
 def unflatten_sac_actor(flat, naming="sb3"):
-    """the actor vector [SAC_NACTOR + 1] -> {name: tensor} in `naming` ('sb3' or 'tool'), log_ent_coef as a tensor of shape (1,)"""
+    """the actor vector [SAC_NACTOR + 1] (or [SAC256_NACTOR + 1]: the widths follow the length) -> {name: tensor} in `naming`
+    ('sb3' or 'tool'), log_ent_coef as a tensor of shape (1,)"""
     flat = np.ascontiguousarray(flat.detach().cpu().numpy() if hasattr(flat, "detach") else flat, dtype=np.float32)
-    if flat.shape != (SAC_NACTOR + 1,):
-        raise ValueError(f"expected {SAC_NACTOR + 1} elements, got shape {flat.shape}")
+    shapes = next((shapes for n, shapes in _SAC_ACTOR_WIDTHS if flat.shape == (n + 1,)), None)
+    if shapes is None:
+        raise ValueError(f"expected {SAC_NACTOR + 1} or {SAC256_NACTOR + 1} elements, got shape {flat.shape}")
     if naming not in SAC_ACTOR_NAMINGS:
         raise ValueError(f"naming must be 'sb3' or 'tool', got {naming!r}")
     p, out, at = SAC_ACTOR_NAMINGS[naming], {}, 0
@@ -624,9 +671,9 @@ def unflatten_sac_actor(flat, naming="sb3"):
         t = torch.from_numpy(flat[at:at + k].reshape(shape).copy())
         at += k
         return t
-    for prefix, (wshape, bshape) in zip(p[:2], _SAC_LAYER_SHAPES[:2]):
+    for prefix, (wshape, bshape) in zip(p[:2], shapes[:2]):
         out[prefix + "weight"], out[prefix + "bias"] = take(wshape), take(bshape)
-    out[p[2] + "weight"], out[p[3] + "weight"] = take((2, 200)), take((2, 200))
+    out[p[2] + "weight"], out[p[3] + "weight"] = take(shapes[2][0]), take(shapes[3][0])
     out[p[2] + "bias"], out[p[3] + "bias"] = take((2,)), take((2,))
     out["log_ent_coef"] = take((1,))
     return out
@@ -635,7 +682,32 @@ def unflatten_sac_actor(flat, naming="sb3"):
 class DeviceSACNets(DeviceDDPGNets):
     """SB3's SACPolicy on the reference's DDPG widths, evaluated by the HIP kernels (brs_sac_act, brs_sac_td_target): the
     squashed-Gaussian actor [SAC_NACTOR + 1] (the last element is log_ent_coef) and the two target critics [2 NCRITIC].  act() has
-    DeviceDDPGNets.act's surface, so DeviceOffPolicyCollector drives it unchanged; q() is inherited."""
+    DeviceDDPGNets.act's surface, so DeviceOffPolicyCollector drives it unchanged.  net_arch='sb3': SB3's default [256, 256]
+    (DESIGN.md 7.12), the vectors then [SAC256_NACTOR + 1] and [2 NCRITIC256]; the DDPG / TD3 calls are refused on such an object."""
+
+    def __init__(self, device=0, seed=0, env_index_base=0, net_arch="reference"):
+        if not torch.cuda.is_available():
+            raise BrsError("no HIP device visible to PyTorch: the on-device SAC networks have no CPU fallback")
+        self.arch = sac_arch(net_arch)
+        self.L = _lib.lib()
+        self.device = _device(device)
+        h = C.c_void_p()
+        rc = self.L.brs_ddpg_create_arch(self.device.index, self.arch.id, C.byref(h))
+        if rc != 0:
+            raise BrsError(f"brs_ddpg_create_arch failed ({rc}): {self.L.brs_ddpg_last_error(None).decode()}")
+        self.h = h
+        self.seed, self.env_index_base = int(seed), int(env_index_base)
+
+    def q(self, critic_params, obs, action, out=None):
+        """Q(s, a) of one critic of this architecture: obs [n,6], action [n,2] -> [n]"""
+        d, f32, n = self.device, torch.float32, obs.shape[0]
+        _need(critic_params, "critic_params", f32, (self.arch.ncritic,), d); _need(obs, "obs", f32, (n, 6), d)
+        _need(action, "action", f32, (n, 2), d)
+        if out is None:
+            out = torch.empty(n, dtype=f32, device=d)
+        _need(out, "q", f32, (n,), d)
+        self._check(self.L.brs_ddpg_q(self.h, _p(critic_params), n, _p(obs), _p(action), _p(out), self._stream()), "brs_ddpg_q")
+        return out
 
     def act(self, actor_params, obs, step, sigma=None, random=False, deterministic=False, out=None, mean=None, log_std=None, noise=None):
         """obs [n,6] -> action [n,2] = tanh(mu + exp(clamp(log_std, -20, 2)) z); deterministic: tanh(mu); `random`: the learning_starts
@@ -644,7 +716,7 @@ class DeviceSACNets(DeviceDDPGNets):
         d, f32 = self.device, torch.float32
         n = out.shape[0] if random and obs is None else obs.shape[0]
         if not random:
-            _need(actor_params, "actor_params", f32, (SAC_NACTOR + 1,), d); _need(obs, "obs", f32, (n, 6), d)
+            _need(actor_params, "actor_params", f32, (self.arch.nactor + 1,), d); _need(obs, "obs", f32, (n, 6), d)
         if out is None:
             out = torch.empty((n, 2), dtype=f32, device=d)
         _need(out, "action", f32, (n, 2), d)
@@ -661,7 +733,7 @@ class DeviceSACNets(DeviceDDPGNets):
         from the CURRENT actor and alpha = exp(actor[-1]); `draw`: the counter of this call's noise (with the object's seed);
         next_action [m,2], logp [m], noise [m,2]: optional outputs -> y [m]"""
         d, f32, m = self.device, torch.float32, next_obs.shape[0]
-        _need(actor, "actor", f32, (SAC_NACTOR + 1,), d); _need(critics_target, "critics_target", f32, (2 * NCRITIC,), d)
+        _need(actor, "actor", f32, (self.arch.nactor + 1,), d); _need(critics_target, "critics_target", f32, (2 * self.arch.ncritic,), d)
         _need(next_obs, "next_obs", f32, (m, 6), d); _need(reward, "reward", f32, (m,), d); _need(done, "done", torch.uint8, (m,), d)
         if out is None:
             out = torch.empty(m, dtype=f32, device=d)
@@ -681,20 +753,24 @@ class DeviceSACLearner:
     both UPDATED critics with the temperature's in the same buffer (brs_sac_actor_grad), and one Adam over the [SAC_NACTOR + 1]
     vector, actor and log_ent_coef together (SB3 gives both the same learning rate, and Adam is element-wise).  The vectors are the
     caller's flat float32 device tensors, updated in place; this object owns the two gradient buffers, the moment vectors and the
-    step counter.  With learn_alpha=False the temperature's gradient is written as 0 and Adam leaves the element as it is."""
+    step counter.  With learn_alpha=False the temperature's gradient is written as 0 and Adam leaves the element as it is.
+    net_arch='sb3': SB3's default [256, 256] (DESIGN.md 7.12); every length below is then that architecture's (self.arch)."""
 
-    def __init__(self, device=0, max_batch=256, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, tau=0.005, target_entropy=-2.0, learn_alpha=True, seed=0):
+    def __init__(self, device=0, max_batch=256, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, tau=0.005, target_entropy=-2.0, learn_alpha=True, seed=0,
+                 net_arch="reference"):
         if not torch.cuda.is_available():
             raise BrsError("no HIP device visible to PyTorch: the on-device SAC learner has no CPU fallback")
+        self.arch = sac_arch(net_arch)
         self.L = _lib.lib()
         self.device = _device(device)
         self.max_batch, self.tau, self.target_entropy, self.learn_alpha, self.seed = int(max_batch), float(tau), float(target_entropy), bool(learn_alpha), int(seed)
         self.cfg = _lib.BrsAdamConfig(float(lr), float(betas[0]), float(betas[1]), float(eps))
         h = C.c_void_p()
-        rc = self.L.brs_ddpg_learner_create_sac(self.device.index, self.max_batch, C.byref(h))
+        rc = self.L.brs_ddpg_learner_create_sac_arch(self.device.index, self.max_batch, self.arch.id, C.byref(h))
         if rc != 0:
-            raise BrsError(f"brs_ddpg_learner_create_sac failed ({rc}): {self.L.brs_ddpg_learner_last_error(None).decode()}")
+            raise BrsError(f"brs_ddpg_learner_create_sac_arch failed ({rc}): {self.L.brs_ddpg_learner_last_error(None).decode()}")
         self.h = h
+        NCRITIC, SAC_NACTOR, SAC_GRAD_LEN = self.arch.ncritic, self.arch.nactor, self.arch.grad_len
         z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
         self.grad_critics, self.grad_actor = z(2 * NCRITIC + _lib.TD3_NSTAT), z(SAC_GRAD_LEN)
         self.m_critics, self.v_critics, self.m_actor, self.v_actor = z(2 * NCRITIC), z(2 * NCRITIC), z(SAC_NACTOR + 1), z(SAC_NACTOR + 1)
@@ -706,7 +782,7 @@ class DeviceSACLearner:
     def twin_critic_grad(self, critics, obs, action, y, out=None):
         """-> [2 NCRITIC + 4]: the gradient of 0.5 (mse(Q1(s, a), y) + mse(Q2(s, a), y)) w.r.t. critic 0 and critic 1, then 0.5 mse and
         the mean Q of critic 0 and of critic 1"""
-        d, f32, m = self.device, torch.float32, obs.shape[0]
+        d, f32, m, NCRITIC = self.device, torch.float32, obs.shape[0], self.arch.ncritic
         out = self.grad_critics if out is None else out
         _need(critics, "critics", f32, (2 * NCRITIC,), d); _need(obs, "obs", f32, (m, 6), d); _need(action, "action", f32, (m, 2), d)
         _need(y, "y", f32, (m,), d); _need(out, "grad", f32, (2 * NCRITIC + _lib.TD3_NSTAT,), d)
@@ -718,7 +794,7 @@ class DeviceSACLearner:
         """-> [SAC_NACTOR + 1 + 4]: the gradient of La = mean(alpha logp - min(Q1, Q2)(s, a)) in the actor's flat order, the
         temperature's -(mean logp + target_entropy) (0 with learn_alpha=False), then La, mean logp, mean min Q and alpha; `draw`: the
         counter of this call's noise (with the object's seed)"""
-        d, f32, m = self.device, torch.float32, obs.shape[0]
+        d, f32, m, NCRITIC, SAC_NACTOR, SAC_GRAD_LEN = self.device, torch.float32, obs.shape[0], self.arch.ncritic, self.arch.nactor, self.arch.grad_len
         out = self.grad_actor if out is None else out
         _need(actor, "actor", f32, (SAC_NACTOR + 1,), d); _need(critics, "critics", f32, (2 * NCRITIC,), d); _need(obs, "obs", f32, (m, 6), d)
         _need(out, "grad", f32, (SAC_GRAD_LEN,), d)
@@ -737,12 +813,14 @@ class DeviceSACLearner:
 
     def apply_critics(self, critics, critics_target=None, grad=None):
         """one Adam step over both critics from grad_critics (or `grad`), then the Polyak update of critics_target"""
+        NCRITIC = self.arch.ncritic
         self._apply(2 * NCRITIC, critics, self.grad_critics if grad is None else grad, 2 * NCRITIC + _lib.TD3_NSTAT, self.m_critics, self.v_critics,
                     critics_target, self.steps_critics + 1, "critics")
         self.steps_critics += 1
 
     def apply_actor(self, actor, grad=None):
         """one Adam step over the actor and log_ent_coef from grad_actor (or `grad`); SAC has no target actor"""
+        SAC_NACTOR, SAC_GRAD_LEN = self.arch.nactor, self.arch.grad_len
         self._apply(SAC_NACTOR + 1, actor, self.grad_actor if grad is None else grad, SAC_GRAD_LEN, self.m_actor, self.v_actor, None,
                     self.steps_actor + 1, "actor")
         self.steps_actor += 1
@@ -759,7 +837,7 @@ class DeviceSACLearner:
     def stats(self):
         """one device-to-host copy: critic_loss (SB3's 0.5 (mse1 + mse2)), mean_q1, mean_q2, actor_loss, mean_logp, mean_qmin and
         ent_coef (the alpha the last actor gradient used), ent_coef_grad"""
-        c0, q0, c1, q1, ge, la, lp, qm, al = torch.cat([self.grad_critics[2 * NCRITIC:], self.grad_actor[SAC_NACTOR:]]).cpu().tolist()
+        c0, q0, c1, q1, ge, la, lp, qm, al = torch.cat([self.grad_critics[2 * self.arch.ncritic:], self.grad_actor[self.arch.nactor:]]).cpu().tolist()
         return {"critic_loss": c0 + c1, "mean_q1": q0, "mean_q2": q1, "actor_loss": la, "mean_logp": lp, "mean_qmin": qm, "ent_coef": al,
                 "ent_coef_grad": ge}
 

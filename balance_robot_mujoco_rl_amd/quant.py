@@ -341,6 +341,9 @@ def _actor_flat(params, head):
             raise ValueError(f"expected {_lib.DDPG_NACTOR} parameters, got {flat.size}")
         return flat.astype(np.float64).ravel()
     flat = flatten_sac_actor(params) if isinstance(params, dict) else np.asarray(params)
+    if flat.size in (_lib.SAC256_NACTOR, _lib.SAC256_NACTOR + 1):
+        raise ValueError("this is a [256, 256] SAC actor (net_arch='sb3'): the int8 actor kernel has the reference widths pi=[300, 200] "
+                         "only and cannot run it")
     if flat.size not in (_lib.SAC_NACTOR, _lib.SAC_NACTOR + 1):
         raise ValueError(f"expected {_lib.SAC_NACTOR} (+ 1) parameters, got {flat.size}")
     flat = flat.astype(np.float64).ravel()

@@ -377,6 +377,25 @@ int brs_sac_twin_critic_grad(brs_ddpg_learner*, const float* critics_dev, int32_
 int brs_sac_actor_grad(brs_ddpg_learner*, const float* actor_dev, const float* critics_dev, int32_t m, const float* obs_dev, uint64_t seed,
                        uint32_t draw, int32_t learn_alpha, float target_entropy, float* grad_dev, void* stream);
 
+/* ---- network architectures.  The widths of a brs_ddpg / brs_ddpg_learner handle are those of its architecture,
+ * fixed at create; every call on the handle takes and returns vectors of that architecture's lengths, its contract otherwise
+ * unchanged.
+ *   BRS_ARCH_REFERENCE   pi=[300, 200], qf=[200, 150]: the reference's DDPG net_arch, everything above; what brs_ddpg_create and
+ *                        brs_ddpg_learner_create / _create_twin / _create_sac make.
+ *   BRS_ARCH_SAC_DEFAULT net_arch=[256, 256] for the actor and both critics: SB3's SAC("MlpPolicy", env).
+ *     SAC actor: W1[256][6] b1[256] W2[256][256] b2[256] W3[4][256] b3[4], then log_ent_coef   [BRS_SAC256_NACTOR + 1]
+ *     critic   : W1[256][8] b1[256] W2[256][256] b2[256] W3[1][256] b3[1]                      [BRS_SAC256_NCRITIC], two back to back
+ * An arch-1 handle serves the SAC calls -- brs_sac_act, brs_sac_td_target, brs_ddpg_q, brs_sac_twin_critic_grad, brs_sac_actor_grad,
+ * brs_ddpg_learner_apply, brs_ddpg_learner_scratch -- with BRS_SAC256_* in the place of BRS_SAC_NACTOR and BRS_DDPG_NCRITIC.  SB3 has
+ * no DDPG or TD3 at these widths: brs_ddpg_act, brs_ddpg_td_target, brs_td3_td_target, brs_ddpg_learner_critic_grad,
+ * _twin_critic_grad and _actor_grad return BRS_ERR_ARG on it and enqueue nothing.  An unknown arch is BRS_ERR_ARG. */
+#define BRS_ARCH_REFERENCE 0
+#define BRS_ARCH_SAC_DEFAULT 1
+#define BRS_SAC256_NACTOR (256 * 6 + 256 + 256 * 256 + 256 + 4 * 256 + 4)  /* 68,612 */
+#define BRS_SAC256_NCRITIC (256 * 8 + 256 + 256 * 256 + 256 + 1 * 256 + 1) /* 68,353 */
+int brs_ddpg_create_arch(int32_t device, int32_t arch, brs_ddpg** out);
+int brs_ddpg_learner_create_sac_arch(int32_t device, int32_t max_batch, int32_t arch, brs_ddpg_learner** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,11 @@ alternating in the same process, medians and all repeats written down, the build
              torch, then --device-data, then --device-data --device-learner, after a 20-step warm-up run
   --train    (e) one run as found: --train-envs envs x --train-steps steps on the device path, then 64 evaluation episodes,
              deterministic
+  --archs    (f) DESIGN.md 7.12: every call of the SAC path at m = 256 on the reference widths and on SB3's [256, 256] in one
+             process, the two alternating repeat by repeat: act, target, critic gradient, actor gradient, the two applies, the whole
+             update, with the ratio sb3 / reference next to the ratio of the parameter counts
+  --net-arch reference|sb3   the widths of --wall and --train (default reference); --kernels compares with the DDPG / TD3 calls
+             and runs on the reference widths only
       python3 tools/sac_kernel_time.py --kernels --wall --train --out profiles/sac_kernel_stats.json
 """
 import argparse, os, statistics, sys, time
@@ -73,23 +78,80 @@ def kernels(calls):
     return res
 
 
+def archs(calls, m=256):
+    import torch
+    import train_sac_torch as T
+    from balance_robot_mujoco_rl_amd import DeviceSACLearner, DeviceSACNets
+    from balance_robot_mujoco_rl_amd.offpolicy import SAC_ARCHS
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev); gen.manual_seed(m)
+    scale = torch.tensor([1.5, 4.0, 0.5, 0.5, 0.5, 0.5], device=dev)
+    obs, next_obs = (torch.randn((m, 6), generator=gen, device=dev) * scale for _ in range(2))
+    act = torch.rand((m, 2), generator=gen, device=dev) * 2 - 1
+    y, reward = torch.randn(m, generator=gen, device=dev), torch.randn(m, generator=gen, device=dev)
+    done = (torch.arange(m, device=dev) % 3 == 1).to(torch.uint8)
+    y_out, a_out, draw = torch.empty(m, device=dev), torch.empty((m, 2), device=dev), [0]
+    side = {}
+    for name in ("reference", "sb3"):
+        side[name] = dict(f=T.SAC(dev, seed=0, net_arch=name).flat, nets=DeviceSACNets(device=0, seed=0, net_arch=name),
+                          lrn=DeviceSACLearner(device=0, max_batch=m, net_arch=name))
+
+    def call(name, what):
+        s = side[name]
+        f, nets, lrn = s["f"], s["nets"], s["lrn"]
+
+        def run():
+            draw[0] += 1
+            if what == "act":
+                nets.act(f["actor"], obs, draw[0], out=a_out)
+            elif what == "target":
+                nets.sac_target(f["actor"], f["critics_target"], next_obs, reward, done, GAMMA, draw[0], out=y_out)
+            elif what == "critic_grad":
+                lrn.twin_critic_grad(f["critics"], obs, act, y)
+            elif what == "actor_grad":
+                lrn.actor_grad(f["actor"], f["critics"], obs, draw[0])
+            elif what == "apply_critics":
+                lrn.apply_critics(f["critics"], f["critics_target"])
+            elif what == "apply_actor":
+                lrn.apply_actor(f["actor"])
+            else:
+                nets.sac_target(f["actor"], f["critics_target"], next_obs, reward, done, GAMMA, draw[0], out=y_out)
+                lrn.step(f, obs, act, y_out, draw[0])
+        return run
+    n = {k: (v.nactor + 1, 2 * v.ncritic) for k, v in SAC_ARCHS.items()}
+    res = {"m": m, "calls_per_repeat": calls, "repeats": 3, "warmup": 10, "units": "microseconds per call",
+           "parameters": {k: {"actor": a, "critics": c, "all": a + c} for k, (a, c) in n.items()},
+           "parameter_ratio": round((n["sb3"][0] + n["sb3"][1]) / (n["reference"][0] + n["reference"][1]), 3), "calls": {}}
+    for what in ("act", "target", "critic_grad", "actor_grad", "apply_critics", "apply_actor", "target_and_update"):
+        t = _alternate(torch, {"reference": call("reference", what), "sb3": call("sb3", what)}, calls)
+        med = {k: statistics.median(v) for k, v in t.items()}
+        res["calls"][what] = dict(**_sides(t), sb3_over_reference=round(med["sb3"] / med["reference"], 3))
+    res["finite"] = bool(all(torch.isfinite(v).all() for s in side.values() for v in s["f"].values()))
+    for s in side.values():
+        s["nets"].close(); s["lrn"].close()
+    return res
+
+
+NET_ARCH = ["reference"]   # --net-arch, for --wall and --train
+
+
 def _run(mode, envs, steps, seed=0, eval_episodes=0):
     import torch
     import train_sac_torch as T
     from balance_robot_mujoco_rl_amd import BatchedSim, DeviceSACLearner, EpisodeMonitor
     sim = BatchedSim("Env01-v1", envs, device=0, seed=seed, auto_reset=True)
-    model = T.SAC(sim.device, seed=seed)
+    model = T.SAC(sim.device, seed=seed, net_arch=NET_ARCH[0])
     mon = EpisodeMonitor(envs, device=0, max_len=int(sim.max_episode_steps))
     cap = max(1, 1_000_000 // envs)
     data = T.SACTorchData(sim, model, cap, 0.0, seed) if mode == "torch" else T.SACDeviceData(sim, model, cap, seed)
-    learner = DeviceSACLearner(device=0, max_batch=256, seed=seed) if mode == "device_data_device_learner" else None
+    learner = DeviceSACLearner(device=0, max_batch=256, seed=seed, net_arch=NET_ARCH[0]) if mode == "device_data_device_learner" else None
     log = {}
     torch.cuda.synchronize(); t0 = time.perf_counter()
     updates = T.train(sim, model, data, steps, batch=256, learning_starts=100, gamma=GAMMA, gradient_steps=1, train_freq=1, monitor=mon, log=log,
                       learner=learner)
     torch.cuda.synchronize(); wall = time.perf_counter() - t0
     s = mon.stats()
-    out = dict(mode=mode, envs=envs, steps=steps, updates=updates, wall_s=round(wall, 3), env_steps_per_s=round(steps * envs / wall),
+    out = dict(mode=mode, net_arch=NET_ARCH[0], envs=envs, steps=steps, updates=updates, wall_s=round(wall, 3), env_steps_per_s=round(steps * envs / wall),
                train_episodes=s.episodes, train_mean_len=s.mean_len, **log, finite=bool(all(torch.isfinite(v).all() for v in model.flat.values())))
     if eval_episodes:
         out["eval_episodes"] = eval_episodes
@@ -121,8 +183,14 @@ def main():
     ap.add_argument("--kernels", action="store_true"); ap.add_argument("--wall", action="store_true"); ap.add_argument("--train", action="store_true")
     ap.add_argument("--calls", type=int, default=200); ap.add_argument("--envs", type=int, default=16384); ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--train-envs", type=int, default=256); ap.add_argument("--train-steps", type=int, default=2000)
+    ap.add_argument("--archs", action="store_true"); ap.add_argument("--net-arch", choices=("reference", "sb3"), default="reference")
     ap.add_argument("--out", default="", help="JSON file to add this mode's section to")
     a = ap.parse_args()
+    NET_ARCH[0] = a.net_arch
+    if a.kernels and a.net_arch != "reference":
+        ap.error("--kernels compares with the DDPG and TD3 calls, which exist on the reference widths only; use --archs")
+    if a.archs:
+        _emit("archs", archs(a.calls), a.out)
     if a.kernels:
         _emit("kernels", kernels(a.calls), a.out)
     if a.wall:

@@ -2,7 +2,8 @@
 """Minimal SAC on the batched simulator: SB3's SAC.train and SACPolicy with SB3's defaults (ent_coef="auto" from 1.0,
 target_entropy = -2, tau 0.005, gamma 0.99, lr 3e-4, batch 256, learning_starts 100, one update per step, no action noise, no gSDE;
 the reference's CLI offers `-a SAC` next to DDPG and TD3, src/sb_rl.py:565) on the widths of tools/train_ddpg_torch.py and
-tools/train_td3_torch.py, pi=[300, 200], qf=[200, 150] -- not SB3's own [256, 256].  Three paths, as in the two siblings:
+tools/train_td3_torch.py, pi=[300, 200], qf=[200, 150], or with --net-arch sb3 on SB3's own [256, 256] for the actor and both
+critics (what `sb_rl.py -a SAC` trains).  Three paths, as in the two siblings:
 
   default           everything in torch (the A/B baseline): buffer, sampling, target and `gradient_step`, written from SB3's rule.
   --device-data     collection (DeviceSACNets.act), buffer, sampling and the SAC target (DeviceSACNets.sac_target) by the HIP kernels;
@@ -30,15 +31,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from train_ddpg_torch import CRITIC_SIZES, DeviceData, TorchData, flatten_module_, mlp  # noqa: E402
 
 LOG_STD_MIN, LOG_STD_MAX, EPS = -20.0, 2.0, 1e-6
+# --net-arch: the hidden widths of the actor and of the critics
+NET_ARCHS = {"reference": ((300, 200), CRITIC_SIZES), "sb3": ((256, 256), (8, 256, 256, 1))}
 
 
 class Actor(nn.Module):
     """SB3's SAC Actor: latent_pi (here `body`), then the two heads"""
 
-    def __init__(self):
+    def __init__(self, hidden=(300, 200)):
         super().__init__()
-        self.body = nn.Sequential(nn.Linear(6, 300), nn.ReLU(), nn.Linear(300, 200), nn.ReLU())
-        self.mu, self.log_std = nn.Linear(200, 2), nn.Linear(200, 2)
+        h1, h2 = hidden
+        self.body = nn.Sequential(nn.Linear(6, h1), nn.ReLU(), nn.Linear(h1, h2), nn.ReLU())
+        self.mu, self.log_std = nn.Linear(h2, 2), nn.Linear(h2, 2)
 
     def forward(self, obs):
         h = self.body(obs)
@@ -58,17 +62,19 @@ class SAC:
     """the five networks (state_dict keys actor.body.N / actor.mu / actor.log_std, critic.K.N, critic_target.K.N, log_ent_coef), their
     three flat vectors (actor [SAC_NACTOR + 1] with log_ent_coef last, critics, critics_target), the optimisers and the Polyak update"""
 
-    def __init__(self, device, lr=3e-4, tau=0.005, seed=0, ent_coef="auto", target_entropy=-2.0):
+    def __init__(self, device, lr=3e-4, tau=0.005, seed=0, ent_coef="auto", target_entropy=-2.0, net_arch="reference"):
         torch.manual_seed(seed)
+        self.net_arch = net_arch
+        pi_hidden, critic_sizes = NET_ARCHS[net_arch]
         self.device, self.tau, self.target_entropy = torch.device(device), tau, float(target_entropy)
         self.learn_alpha = ent_coef == "auto"
-        twin = lambda: nn.ModuleList([mlp(CRITIC_SIZES, False), mlp(CRITIC_SIZES, False)])
-        self.actor, self.critic, self.critic_target = Actor(), twin(), twin()
+        twin = lambda: nn.ModuleList([mlp(critic_sizes, False), mlp(critic_sizes, False)])
+        self.actor, self.critic, self.critic_target = Actor(pi_hidden), twin(), twin()
         self.critic_target.load_state_dict(self.critic.state_dict())
         self.log_ent_coef = nn.Parameter(torch.tensor([0.0 if self.learn_alpha else math.log(float(ent_coef))]), requires_grad=self.learn_alpha)
         a = self.actor
         ordered = [a.body[0].weight, a.body[0].bias, a.body[2].weight, a.body[2].bias, a.mu.weight, a.log_std.weight, a.mu.bias, a.log_std.bias,
-                   self.log_ent_coef]   # W3[4][200] = mu's rows, then log_std's; b3[4] likewise
+                   self.log_ent_coef]   # W3[4][H2] = mu's rows, then log_std's; b3[4] likewise
         flat = torch.cat([p.detach().reshape(-1) for p in ordered]).to(device=self.device, dtype=torch.float32).contiguous()
         at = 0
         for p in ordered:
@@ -140,7 +146,7 @@ class SACDeviceData(DeviceData):
     def __init__(self, sim, model, cap, seed, monitor=None):
         from balance_robot_mujoco_rl_amd.offpolicy import DeviceOffPolicyCollector, DeviceReplayBuffer, DeviceSACNets
         self.sim, self.model = sim, model
-        self.nets = DeviceSACNets(device=sim.device, seed=seed)
+        self.nets = DeviceSACNets(device=sim.device, seed=seed, net_arch=model.net_arch)
         self.replay = DeviceReplayBuffer(sim.n, cap, device=sim.device, seed=seed)
         self.collector = DeviceOffPolicyCollector(sim, self.nets, model.flat["actor"], self.replay, sigma=0.0, monitor=monitor)
         self.target_draw = 0
@@ -188,7 +194,7 @@ def evaluate(env_id, model, episodes, envs, device_data, device=0, seed=123):
     mon = EpisodeMonitor(envs, device=sim.device, max_len=max(1, int(sim.max_episode_steps)), log_capacity=episodes)
     if device_data:
         from balance_robot_mujoco_rl_amd.offpolicy import DeviceSACNets
-        nets = DeviceSACNets(device=sim.device, seed=seed)
+        nets = DeviceSACNets(device=sim.device, seed=seed, net_arch=model.net_arch)
         act = lambda obs, t: nets.act(model.flat["actor"], obs, t, deterministic=True)
     else:
         def act(obs, t):
@@ -212,6 +218,8 @@ def main(argv=None):
     ap.add_argument("--gradient-steps", type=int, default=1)
     ap.add_argument("--train-freq", type=int, default=1, help="env steps between two rounds of updates")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--net-arch", choices=sorted(NET_ARCHS), default="reference",
+                    help="reference: pi=[300, 200], qf=[200, 150] (the reference's DDPG widths); sb3: SB3's default [256, 256]")
     ap.add_argument("--device-data", action="store_true", help="collection, buffer, sampling and SAC targets by the HIP kernels")
     ap.add_argument("--device-learner", action="store_true", help="the update by the HIP kernels too (needs --device-data)")
     ap.add_argument("--eval-episodes", type=int, default=0); ap.add_argument("--eval-envs", type=int, default=256)
@@ -233,7 +241,7 @@ def main(argv=None):
     from balance_robot_mujoco_rl_amd import BatchedSim, EpisodeMonitor, _lib
     sim = BatchedSim(a.env, a.envs, device=0, seed=a.seed, auto_reset=True)
     cap = a.capacity_steps or max(1, 1_000_000 // a.envs)
-    model = SAC(sim.device, lr=a.lr, tau=a.tau, seed=a.seed, ent_coef=a.ent_coef, target_entropy=a.target_entropy)
+    model = SAC(sim.device, lr=a.lr, tau=a.tau, seed=a.seed, ent_coef=a.ent_coef, target_entropy=a.target_entropy, net_arch=a.net_arch)
     start = {k: v.clone() for k, v in model.flat.items()}
     monitor = EpisodeMonitor(a.envs, device=sim.device, max_len=max(1, int(sim.max_episode_steps)))
     data = SACDeviceData(sim, model, cap, a.seed) if a.device_data else SACTorchData(sim, model, cap, 0.0, a.seed)
@@ -242,7 +250,7 @@ def main(argv=None):
     if a.device_learner:
         from balance_robot_mujoco_rl_amd.offpolicy import DeviceSACLearner
         learner = DeviceSACLearner(device=sim.device, max_batch=a.batch, lr=a.lr, tau=a.tau, target_entropy=a.target_entropy,
-                                   learn_alpha=model.learn_alpha, seed=a.seed)
+                                   learn_alpha=model.learn_alpha, seed=a.seed, net_arch=a.net_arch)
         log["learner"] = "device"
     torch.cuda.synchronize(); t0 = time.perf_counter()
     log["updates"] = train(sim, model, data, a.steps, a.batch, a.learning_starts, a.gamma, a.gradient_steps, a.train_freq, monitor, log, learner=learner)
