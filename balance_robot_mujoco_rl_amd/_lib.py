@@ -246,6 +246,8 @@ SIGNATURES = {
         "brs_qpolicy_actor_last_error": (C.c_char_p, [_vp]),
         "brs_qpolicy_actor_set_model": (C.c_int, [_vp, C.POINTER(BrsQActorModel)]),
         "brs_qpolicy_actor_act": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
+        "brs_qpolicy_actor_create_arch": (C.c_int, [_i32, _i32, C.POINTER(_vp)]),
+        "brs_qpolicy_actor_check_model": (C.c_int, [_i32, C.POINTER(BrsQActorModel)]),
     },
 }
 SYMBOLS = list(SIGNATURES["brs.h"]) + list(SIGNATURES["brs_policy.h"])

@@ -15,13 +15,21 @@
 //   * layer 2 (2 x 200) on the vector ALU, one cross-half shuffle, then the tanh table: one LDS read per action component.
 // The image (85 KB: 74 KB of it the bank-padded layer-1 weights) is staged in LDS once per 256-env workgroup; a CDNA4 CU has
 // 160 KiB and this kernel keeps one workgroup = one wave per SIMD on it.
+//
+// The kernel is a template over the hidden widths (brs_qactor.hpp: WidthsReference, Widths256) and is instantiated once per
+// architecture a handle can have; the numbers above are the reference widths'.  SB3's [256, 256] is eight whole tiles per layer:
+// no pad unit, 16 + 128 matrix instructions, 64 registers of packed activations, an 80 KB image (17 groups of 16 bytes per row).
 #include <hip/hip_runtime.h>
 
 #include <memory>
 #include <string>
 
+#include "../../include/brs_policy.h"
 #include "brs_host.hpp"
 #include "brs_qactor.hpp"
+
+static_assert(BRS_QACTOR_ARCH_REFERENCE == BRS_ARCH_REFERENCE && BRS_QACTOR_ARCH_SAC_DEFAULT == BRS_ARCH_SAC_DEFAULT,
+              "brs_qpolicy.h restates the architecture ids of brs_policy.h");
 
 namespace {
 
@@ -32,8 +40,15 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int QACTOR_THREADS = 256;  // 4 waves x 64 envs share one staged image
 
-__global__ void __launch_bounds__(QACTOR_THREADS) qactor_act_kernel(const Image* __restrict__ image, const int n, const float* __restrict__ obs,
-                                                                    float* __restrict__ action, int8_t* __restrict__ action_q) {
+// One wave per SIMD, said to the compiler: two [256, 256] images (2 x 80,208 B) would fit a CU's LDS, so left alone it plans for two
+// waves per SIMD, caps the registers at 256 and puts 32 bytes per lane in scratch; at one wave it needs 211 + 32 registers and no
+// scratch.  The reference widths' image never allowed a second workgroup: that instantiation compiles to what it was without this.
+template <class A>
+__global__ void __launch_bounds__(QACTOR_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
+qactor_act_kernel(const ImageT<A>* __restrict__ image, const int n, const float* __restrict__ obs, float* __restrict__ action,
+                  int8_t* __restrict__ action_q) {
+  using Image = ImageT<A>;
+  constexpr int MT0 = Dims<A>::MT0, MT1 = Dims<A>::MT1, W1_LD = Dims<A>::W1_LD;
   __shared__ Image im;
   {
     const i32x4* src = reinterpret_cast<const i32x4*>(image);
@@ -83,7 +98,7 @@ __global__ void __launch_bounds__(QACTOR_THREADS) qactor_act_kernel(const Image*
     for (int nt = 0; nt < 2; nt++) h0[mt][nt] = i32x4{(int)w[nt][0], (int)w[nt][1], (int)w[nt][2], (int)w[nt][3]};
   }
 
-  // layers 1 and 2: an M-tile of layer 1 over its ten K-steps, then its 16 units of each env into layer 2's partial sums
+  // layers 1 and 2: an M-tile of layer 1 over its MT0 K-steps, then its 16 units of each env into layer 2's partial sums
   int p[2][ACT] = {{0, 0}, {0, 0}};
 #pragma unroll 1
   for (int mt = 0; mt < MT1; mt++) {
@@ -128,30 +143,66 @@ __global__ void __launch_bounds__(QACTOR_THREADS) qactor_act_kernel(const Image*
 
 struct brs_qactor {
   int device = 0;
-  brs::qactor::Image* image_dev = nullptr;
+  int arch = BRS_QACTOR_ARCH_REFERENCE;  // whose widths set_model takes and act runs, fixed at create
+  void* image_dev = nullptr;             // an ImageT of that architecture
   bool has_model = false;
   std::string err;
 };
 
 using brs::host::DeviceGuard, brs::host::fail;
 
+namespace {
+
+template <class A> size_t image_bytes() { return sizeof(ImageT<A>); }
+
+// build_image for the widths of A, then (with a handle) the copy to the device
+template <class A> int set_model_as(brs_qactor* p, const brs_qactor_model* model) {
+  const std::unique_ptr<ImageT<A>> im(new ImageT<A>);
+  std::string why;
+  const int rc = build_image(model, im.get(), &why);  // before the handle: a model can be checked without a device
+  if (rc != BRS_OK) return fail(p, rc, why);
+  if (!p) return BRS_ERR_STATE;
+  DeviceGuard g(p->device);
+  if (!g.ok) return fail(p, BRS_ERR_HIP, "brs_qpolicy_actor_set_model: hipSetDevice failed");
+  // kernels enqueued earlier on any stream may still be reading the image: drain the device before overwriting it
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(p->image_dev, im.get(), sizeof(ImageT<A>), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(p, BRS_ERR_HIP, std::string("brs_qpolicy_actor_set_model: ") + hipGetErrorString(e));
+  p->has_model = true;
+  return BRS_OK;
+}
+
+template <class A> void launch_as(brs_qactor* p, int32_t n, const float* obs_dev, float* action_dev, int8_t* action_q_dev, void* stream) {
+  hipLaunchKernelGGL(qactor_act_kernel<A>, dim3((n + QACTOR_THREADS - 1) / QACTOR_THREADS), dim3(QACTOR_THREADS), 0, (hipStream_t)stream,
+                     static_cast<const ImageT<A>*>(p->image_dev), n, obs_dev, action_dev, action_q_dev);
+}
+
+}  // namespace
+
 extern "C" {
 
-int brs_qpolicy_actor_create(int32_t device, brs_qactor** out) {
-  if (!out) return fail<brs_qactor>(nullptr, BRS_ERR_ARG, "brs_qpolicy_actor_create: null argument");
+int brs_qpolicy_actor_create_arch(int32_t device, int32_t arch, brs_qactor** out) {
+  const char* who = arch == BRS_QACTOR_ARCH_REFERENCE ? "brs_qpolicy_actor_create" : "brs_qpolicy_actor_create_arch";
+  if (!out) return fail<brs_qactor>(nullptr, BRS_ERR_ARG, std::string(who) + ": null argument");
   *out = nullptr;
+  if (!known_arch(arch))
+    return fail<brs_qactor>(nullptr, BRS_ERR_ARG, "brs_qpolicy_actor_create_arch: unknown architecture " + std::to_string(arch) +
+                                                      " (0: 6-300-200-2, 1: 6-256-256-2)");
   std::string why;
-  if (const int rc = brs::host::check_device(device, "brs_qpolicy_actor_create", &why)) return fail<brs_qactor>(nullptr, rc, why);
+  if (const int rc = brs::host::check_device(device, who, &why)) return fail<brs_qactor>(nullptr, rc, why);
   brs_qactor* p = new brs_qactor();
   p->device = device;
+  p->arch = arch;
   DeviceGuard g(device);
-  if (!g.ok || hipMalloc(&p->image_dev, sizeof(brs::qactor::Image)) != hipSuccess) {
+  if (!g.ok || hipMalloc(&p->image_dev, arch == Widths256::ID ? image_bytes<Widths256>() : image_bytes<WidthsReference>()) != hipSuccess) {
     delete p;
-    return fail<brs_qactor>(nullptr, BRS_ERR_HIP, "brs_qpolicy_actor_create: device allocation failed");
+    return fail<brs_qactor>(nullptr, BRS_ERR_HIP, std::string(who) + ": device allocation failed");
   }
   *out = p;
   return BRS_OK;
 }
+
+int brs_qpolicy_actor_create(int32_t device, brs_qactor** out) { return brs_qpolicy_actor_create_arch(device, BRS_QACTOR_ARCH_REFERENCE, out); }
 
 int brs_qpolicy_actor_destroy(brs_qactor* p) {
   if (!p) return BRS_ERR_STATE;
@@ -166,19 +217,16 @@ int brs_qpolicy_actor_destroy(brs_qactor* p) {
 const char* brs_qpolicy_actor_last_error(const brs_qactor* p) { return brs::host::last_error(p); }
 
 int brs_qpolicy_actor_set_model(brs_qactor* p, const brs_qactor_model* model) {
-  const std::unique_ptr<brs::qactor::Image> im(new brs::qactor::Image);
-  std::string why;
-  const int rc = brs::qactor::build_image(model, im.get(), &why);  // before the handle: a model can be checked without a device
-  if (rc != BRS_OK) return fail(p, rc, why);
-  if (!p) return BRS_ERR_STATE;
-  DeviceGuard g(p->device);
-  if (!g.ok) return fail(p, BRS_ERR_HIP, "brs_qpolicy_actor_set_model: hipSetDevice failed");
-  // kernels enqueued earlier on any stream may still be reading the image: drain the device before overwriting it
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(p->image_dev, im.get(), sizeof(brs::qactor::Image), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return fail(p, BRS_ERR_HIP, std::string("brs_qpolicy_actor_set_model: ") + hipGetErrorString(e));
-  p->has_model = true;
-  return BRS_OK;
+  // without a handle the model is held against the reference widths
+  return p && p->arch == Widths256::ID ? set_model_as<Widths256>(p, model) : set_model_as<WidthsReference>(p, model);
+}
+
+int brs_qpolicy_actor_check_model(int32_t arch, const brs_qactor_model* model) {
+  if (!known_arch(arch))
+    return fail<brs_qactor>(nullptr, BRS_ERR_ARG, "brs_qpolicy_actor_check_model: unknown architecture " + std::to_string(arch) +
+                                                      " (0: 6-300-200-2, 1: 6-256-256-2)");
+  const int rc = arch == Widths256::ID ? set_model_as<Widths256>(nullptr, model) : set_model_as<WidthsReference>(nullptr, model);
+  return rc == BRS_ERR_STATE ? BRS_OK : rc;  // a good model and no handle
 }
 
 int brs_qpolicy_actor_act(brs_qactor* p, int32_t n, const float* obs_dev, float* action_dev, int8_t* action_q_dev, void* stream) {
@@ -187,8 +235,8 @@ int brs_qpolicy_actor_act(brs_qactor* p, int32_t n, const float* obs_dev, float*
   if (!p->has_model) return fail(p, BRS_ERR_STATE, "brs_qpolicy_actor_act: no model has been set");
   DeviceGuard g(p->device);
   if (!g.ok) return fail(p, BRS_ERR_HIP, "brs_qpolicy_actor_act: hipSetDevice failed");
-  hipLaunchKernelGGL(qactor_act_kernel, dim3((n + QACTOR_THREADS - 1) / QACTOR_THREADS), dim3(QACTOR_THREADS), 0, (hipStream_t)stream,
-                     p->image_dev, n, obs_dev, action_dev, action_q_dev);
+  if (p->arch == Widths256::ID) launch_as<Widths256>(p, n, obs_dev, action_dev, action_q_dev, stream);
+  else launch_as<WidthsReference>(p, n, obs_dev, action_dev, action_q_dev, stream);
   if (hipGetLastError() != hipSuccess) return fail(p, BRS_ERR_HIP, "brs_qpolicy_actor_act: kernel launch failed");
   return BRS_OK;
 }

@@ -1,7 +1,9 @@
 // brs_qactor.hpp -- the int8 off-policy actor of include/brs_qpolicy.h (6 -> 300 -> ReLU -> 200 -> ReLU -> 2 -> tanh), the part
 // shared by the HIP kernel (brs_qactor.hip) and the host build the CPU tests compare with the numpy reference
 // (tests/qactorhost): the device image of a model, the per-env scalar form of steps 1-6, and (host only) the checks and the
-// zero-point fold of brs_qpolicy_actor_set_model.  The arithmetic of single steps is brs_qpolicy.hpp's.
+// zero-point fold of brs_qpolicy_actor_set_model.  The arithmetic of single steps is brs_qpolicy.hpp's.  Image, act_env and
+// build_image are templates over the hidden widths (WidthsReference, Widths256: SB3's SAC default 6 -> 256 -> 256 -> 2); the names
+// without a parameter (Image, H0, H1, ...) are the reference widths'.
 #pragma once
 #include <stddef.h>
 
@@ -17,12 +19,32 @@ using qpolicy::requantize;
 using qpolicy::unit_of;
 using qpolicy::w1_pos;
 
-constexpr int OBS = BRS_QACTOR_OBS, H0 = BRS_QACTOR_H0, H1 = BRS_QACTOR_H1, ACT = BRS_QACTOR_ACT;
-constexpr int H0P = 320, H1P = 224;  // the hidden widths padded to whole 32-unit tiles: 10 and 7
-constexpr int MT0 = H0P / 32, MT1 = H1P / 32;
-constexpr int W0_LD = 8;             // bytes per row of the first layer's weights: inputs 0..5, two zeros
-constexpr int W1_LD = H0P + 16;      // bytes per row of the second layer's weights: 21 groups of 16 bytes, an odd number, so
-                                     // that the 32 rows a half-wave reads 16 bytes of fall into different groups of four LDS banks
+constexpr int OBS = BRS_QACTOR_OBS, H0 = BRS_QACTOR_H0, H1 = BRS_QACTOR_H1, ACT = BRS_QACTOR_ACT;  // the reference widths
+constexpr int W0_LD = 8;  // bytes per row of the first layer's weights: inputs 0..5, two zeros
+
+// The hidden widths a handle can serve, one struct per architecture of include/brs_qpolicy.h (BRS_QACTOR_ARCH_*): H0 / H1 and
+// the same padded to whole 32-unit tiles.  Image, act_env, build_image and the kernel are templates over it, as the SAC kernels
+// are over their networks (brs_sac.hpp); another width set is another struct here and another case where the arch is dispatched.
+struct WidthsReference {  // the reference's DDPG pi=[300, 200]: 10 and 7 tiles, 20 and 24 pad units
+  static constexpr int ID = BRS_QACTOR_ARCH_REFERENCE, H0 = BRS_QACTOR_H0, H1 = BRS_QACTOR_H1, H0P = 320, H1P = 224;
+  static constexpr const char* NETWORK = "6-300-200-2";
+};
+struct Widths256 {  // SB3's default [256, 256]: 8 and 8 tiles, no pad unit
+  static constexpr int ID = BRS_QACTOR_ARCH_SAC_DEFAULT, H0 = BRS_QACTOR256_H0, H1 = BRS_QACTOR256_H1, H0P = 256, H1P = 256;
+  static constexpr const char* NETWORK = "6-256-256-2";
+};
+inline bool known_arch(int32_t arch) { return arch == WidthsReference::ID || arch == Widths256::ID; }
+
+template <class A> struct Dims {
+  static_assert(A::H0P % 32 == 0 && A::H1P % 32 == 0 && A::H0P >= A::H0 && A::H1P >= A::H1 && A::H0P - A::H0 < 32 && A::H1P - A::H1 < 32, "whole tiles");
+  static constexpr int MT0 = A::H0P / 32, MT1 = A::H1P / 32;
+  // bytes per row of the second layer's weights: 21 (reference) or 17 ([256, 256]) groups of 16 bytes, an odd number, so that the
+  // 32 rows a half-wave reads 16 bytes of fall into different groups of four LDS banks
+  static constexpr int W1_LD = A::H0P + 16;
+  static_assert((W1_LD / 16) % 2 == 1, "an odd number of 16-byte groups per row");
+};
+constexpr int H0P = WidthsReference::H0P, H1P = WidthsReference::H1P, MT0 = Dims<WidthsReference>::MT0, MT1 = Dims<WidthsReference>::MT1,
+              W1_LD = Dims<WidthsReference>::W1_LD;
 
 // Byte of a w1 row that multiplies unit k of the first hidden layer: K-step k / 32, inside it w1_pos, so that byte j of half
 // h in step s is unit_of(s, j, h) and a layer's requantised accumulators ARE the next B operand.
@@ -30,20 +52,27 @@ BRS_HD int w1_at(int k) { return (k & ~31) + w1_pos(k & 31); }
 
 // What the kernel reads: one block of plain data, copied to the device by set_model and to LDS by every workgroup.  Biases
 // have the input zero point folded in; w1 is stored in the order the matrix cores consume it (w1_at).
-struct Image {
+template <class A> struct ImageT {
   double input_scale, action_scale;
   int32_t input_zero, action_zero, oz[3], pad0;
   int32_t b2[ACT], m2[ACT], t2[ACT], pad1[4];
-  int32_t b0[H0P], m0[H0P], t0[H0P];
-  int32_t b1[H1P], m1[H1P], t1[H1P];
-  int32_t w2[ACT][H1P];
+  int32_t b0[A::H0P], m0[A::H0P], t0[A::H0P];
+  int32_t b1[A::H1P], m1[A::H1P], t1[A::H1P];
+  int32_t w2[ACT][A::H1P];
   int8_t lut[256];
-  alignas(16) int8_t w0[H0P * W0_LD];
-  alignas(16) int8_t w1[H1P * W1_LD];
+  alignas(16) int8_t w0[A::H0P * W0_LD];
+  alignas(16) int8_t w1[A::H1P * Dims<A>::W1_LD];
 };
-static_assert(sizeof(Image) % 16 == 0, "the image is copied to LDS 16 bytes at a time");
-static_assert(offsetof(Image, w1) % 16 == 0 && offsetof(Image, b0) % 16 == 0, "16-byte reads");
-static_assert(sizeof(Image) <= 160 * 1024, "one workgroup stages the whole image in the 160 KiB of LDS of a CDNA4 CU");
+using Image = ImageT<WidthsReference>;
+using Image256 = ImageT<Widths256>;
+template <class A> constexpr bool image_fits() {
+  static_assert(sizeof(ImageT<A>) % 16 == 0, "the image is copied to LDS 16 bytes at a time");
+  static_assert(offsetof(ImageT<A>, w1) % 16 == 0 && offsetof(ImageT<A>, w0) % 16 == 0 && offsetof(ImageT<A>, b0) % 16 == 0, "16-byte reads");
+  static_assert(sizeof(ImageT<A>) <= 160 * 1024, "one workgroup stages the whole image in the 160 KiB of LDS of a CDNA4 CU");
+  return true;
+}
+static_assert(image_fits<WidthsReference>() && image_fits<Widths256>(), "both instantiations");
+static_assert(sizeof(Image) == 86480 && sizeof(Image256) == 80208, "the sizes DESIGN.md 7.11 states");
 
 // steps 3 and 4 of a hidden layer
 BRS_HD int32_t requantize_relu(int32_t acc, int32_t m, int32_t t, int32_t oz) {
@@ -52,7 +81,8 @@ BRS_HD int32_t requantize_relu(int32_t acc, int32_t m, int32_t t, int32_t oz) {
 }
 
 // steps 1-6 for one env, one unit at a time (the kernel does the two wide layers on the matrix cores instead)
-BRS_HD void act_env(const Image& im, const float* obs, float* action, int8_t* action_q) {
+template <class A> BRS_HD void act_env(const ImageT<A>& im, const float* obs, float* action, int8_t* action_q) {
+  constexpr int H0 = A::H0, H1 = A::H1, W1_LD = Dims<A>::W1_LD;
   int32_t q0[OBS], h0[H0], h1[H1];
   for (int i = 0; i < OBS; i++) q0[i] = quantize_input(obs[i], im.input_scale, im.input_zero);
   for (int c = 0; c < H0; c++) {
@@ -75,8 +105,9 @@ BRS_HD void act_env(const Image& im, const float* obs, float* action, int8_t* ac
 }
 
 // ------------------------------------------------------------------------------------------------------------ host only
-// The checks of brs_qpolicy_actor_set_model and the image it copies to the device.
-inline int build_image(const brs_qactor_model* q, Image* im, std::string* err) {
+// The checks of brs_qpolicy_actor_set_model and the image it copies to the device, for the widths of A (deduced from the image).
+template <class A> int build_image(const brs_qactor_model* q, ImageT<A>* im, std::string* err) {
+  constexpr int H0 = A::H0, H1 = A::H1, H0P = A::H0P, H1P = A::H1P, W1_LD = Dims<A>::W1_LD;
   auto bad = [&](const std::string& m) { if (err) *err = "brs_qpolicy_actor_set_model: " + m; return (int)BRS_ERR_ARG; };
   if (!q || !im) return bad("null argument");
   static const int NIN[3] = {OBS, H0, H1}, NOUT[3] = {H0, H1, ACT}, NOUTP[3] = {H0P, H1P, ACT};
@@ -84,10 +115,10 @@ inline int build_image(const brs_qactor_model* q, Image* im, std::string* err) {
   if (q->input_zero < -128 || q->input_zero > 127) return bad("input_zero outside [-128, 127]");
   if (!(q->action_scale > 0.0) || !isfinite(q->action_scale)) return bad("action_scale must be positive and finite");
   if (q->action_zero < -128 || q->action_zero > 127) return bad("action_zero outside [-128, 127]");
-  // PADDING.  Everything starts as zero: the pad channels (units 300..319 and 200..223) have zero weights and a zero bias,
-  // and every weight that READS a pad unit (bytes w1_at(300..319) of a w1 row, w2[.][200..223]) is zero.  So whatever code a
+  // PADDING.  Everything starts as zero: the pad channels (at the reference widths units 300..319 and 200..223; [256, 256] has none)
+  // have zero weights and a zero bias, and every weight that READS a pad unit (bytes w1_at(300..319) of a w1 row, w2[.][200..223]) is zero.  So whatever code a
   // pad unit holds cannot reach an output; it only has to be computable, hence the valid multiplier (1/2) given to it below.
-  *im = Image{};
+  *im = ImageT<A>{};
   im->input_scale = q->input_scale;
   im->input_zero = q->input_zero;
   im->action_scale = q->action_scale;
@@ -96,7 +127,7 @@ inline int build_image(const brs_qactor_model* q, Image* im, std::string* err) {
   for (int k = 0; k < 3; k++) {
     const brs_qlayer& L = q->layer[k];
     const std::string name = "layer " + std::to_string(k);
-    if (L.n_in != NIN[k] || L.n_out != NOUT[k]) return bad(name + ": the network must be 6-300-200-2");
+    if (L.n_in != NIN[k] || L.n_out != NOUT[k]) return bad(name + ": the network must be " + A::NETWORK);
     if (!L.weight || !L.bias || !L.bias_scale) return bad(name + ": null pointer");
     if ((k == 2) != (L.tanh_table != nullptr)) return bad(name + (k == 2 ? ": the output layer needs a tanh table" : ": a hidden layer takes no table"));
     if (!(L.out_scale > 0.0) || !isfinite(L.out_scale)) return bad(name + ": out_scale must be positive and finite");

@@ -9,7 +9,8 @@ the int8 network in closed loop in the simulator (src/sb_rl.py:285-364, `test-tf
     QuantPolicy       the int8 network for n envs as a HIP kernel (brs_qpolicy_act), bit-exact integer arithmetic
     QuantActorModel, quantize_actor, QuantActor
                       the same three for the off-policy actor 6 -> 300 -> ReLU -> 200 -> ReLU -> 2 -> tanh of DDPG, TD3 and SAC
-                      (brs_qpolicy_actor_act)
+                      (brs_qpolicy_actor_act), and for SAC's actor at SB3's default widths, 6 -> 256 -> 256 -> 2
+                      (net_arch="sb3")
 
 PyTorch only owns the buffers and the stream.  There is no CPU fallback."""
 import ctypes as C
@@ -249,10 +250,20 @@ class QuantPolicy:
 
 # ------------------------------------------------------------------- the off-policy actor, 6 -> 300 -> ReLU -> 200 -> ReLU -> 2 -> tanh
 _ACTOR_SIZES = ((6, 300), (300, 200), (200, 2))
+# net_arch -> the hidden widths the int8 actor kernel is built for, and the architecture id of include/brs_qpolicy.h
+_ACTOR_WIDTHS = {"reference": (300, 200), "sb3": (256, 256)}
+_ACTOR_ARCH_ID = {"reference": _lib.ARCH_REFERENCE, "sb3": _lib.ARCH_SAC_DEFAULT}
+
+
+def _actor_sizes(net_arch):
+    h0, h1 = _ACTOR_WIDTHS[net_arch]
+    return ((6, h0), (h0, h1), (h1, 2))
 
 
 class QuantActorModel:
-    """An int8 actor 6 -> 300 -> ReLU -> 200 -> ReLU -> 2 -> tanh, the network DDPG, TD3 and SAC train.
+    """An int8 actor 6 -> 300 -> ReLU -> 200 -> ReLU -> 2 -> tanh, the network DDPG, TD3 and SAC train, or
+    6 -> 256 -> ReLU -> 256 -> ReLU -> 2 -> tanh, SAC's at SB3's default widths: the widths are read off the tensors, and
+    `net_arch` says which they are ("reference" or "sb3").
     `layers[k]` is a dict: W int8 [out][in], b int32 [out], ws float64 [out] (weight scale per output channel), bs float64 [out]
     (bias scale = input scale x ws), os / oz (scale and zero point of the layer's output; on a hidden layer oz is the code of
     real 0, below which ReLU clamps).  `action_scale` / `action_zero`: of the output tanh table's result."""
@@ -263,10 +274,16 @@ class QuantActorModel:
         if len(layers) != 3:
             raise ValueError(f"expected three layers, got {len(layers)}")
         self.layers = []
-        for k, (L, (n_in, n_out)) in enumerate(zip(layers, _ACTOR_SIZES)):
+        shape0 = np.asarray(layers[0]["W"]).shape
+        self.net_arch = next((name for name, (h0, _) in _ACTOR_WIDTHS.items() if shape0 == (h0, 6)), None)
+        if self.net_arch is None:
+            raise ValueError(f"layer 0: expected weights (300, 6) (net_arch 'reference') or (256, 6) ('sb3'), got {shape0}")
+        other = "sb3" if self.net_arch == "reference" else "reference"
+        for k, (L, (n_in, n_out), (o_in, o_out)) in enumerate(zip(layers, _actor_sizes(self.net_arch), _actor_sizes(other))):
             W, b = np.asarray(L["W"]), np.asarray(L["b"])
             if W.shape != (n_out, n_in) or b.shape != (n_out,):
-                raise ValueError(f"layer {k}: expected weights {(n_out, n_in)} and bias {(n_out,)}, got {W.shape} and {b.shape}")
+                raise ValueError(f"layer {k}: expected weights {(n_out, n_in)} and bias {(n_out,)} (net_arch {self.net_arch!r}; {other!r} has "
+                                 f"{(o_out, o_in)} and {(o_out,)}), got {W.shape} and {b.shape}")
             if np.abs(W).max(initial=0) > 128 or np.abs(b.astype(np.int64)).max(initial=0) > 2 ** 31 - 1:
                 raise ValueError(f"layer {k}: weights must fit int8 and biases int32")
             self.layers.append(dict(W=np.ascontiguousarray(W, np.int8), b=np.ascontiguousarray(b, np.int32),
@@ -304,12 +321,13 @@ class QuantActorModel:
         return tanh_table(L["os"], L["oz"], self.action_scale, self.action_zero)
 
     def float_params(self):
-        """the same network with DEQUANTISED weights as the flat float32 DDPG actor vector (what DeviceDDPGNets.act takes)"""
+        """the same network with DEQUANTISED weights as the flat float32 vector in the DDPG actor's layout, W b W b W b, at the
+        model's own widths (62,702 elements: what DeviceDDPGNets.act takes; 68,098 at [256, 256])"""
         parts = []
         for L in self.layers:
             parts += [(L["W"].astype(np.float64) * L["ws"][:, None]).ravel(), L["b"].astype(np.float64) * L["bs"]]
         flat = np.concatenate(parts).astype(np.float32)
-        assert flat.size == _lib.DDPG_NACTOR
+        assert flat.size == sum(n_in * n_out + n_out for n_in, n_out in _actor_sizes(self.net_arch))
         return flat
 
     def c_model(self):
@@ -329,12 +347,26 @@ class QuantActorModel:
         return m, keep
 
 
-def _actor_flat(params, head):
-    """-> the fp64 DDPG-layout actor vector [DDPG_NACTOR]; with head = "sac" the mu head of a SAC actor (log_std dropped)"""
+def _actor_flat(params, head, net_arch="reference"):
+    """-> the fp64 DDPG-layout actor vector of `net_arch`'s widths; with head = "sac" the mu head of a SAC actor (log_std dropped)"""
     from .offpolicy import flatten_ddpg_state_dict, flatten_sac_actor
     if head not in ("ddpg", "sac"):
         raise ValueError(f"head must be 'ddpg' or 'sac', got {head!r}")
-    n01 = 300 * 6 + 300 + 200 * 300 + 200
+    if net_arch not in _ACTOR_WIDTHS:
+        raise ValueError(f"net_arch must be 'reference' or 'sb3', got {net_arch!r}")
+    h0, h1 = _ACTOR_WIDTHS[net_arch]
+    n01 = h0 * 6 + h0 + h1 * h0 + h1
+    if net_arch == "sb3":
+        if head != "sac":
+            raise ValueError("net_arch='sb3' is SAC's [256, 256] actor: pass head='sac' (SB3 has no DDPG or TD3 at these widths)")
+        flat = flatten_sac_actor(params) if isinstance(params, dict) else np.asarray(params)
+        if flat.size in (_lib.SAC_NACTOR, _lib.SAC_NACTOR + 1):
+            raise ValueError("this is a SAC actor of the reference widths pi=[300, 200]: pass net_arch='reference'")
+        if flat.size not in (_lib.SAC256_NACTOR, _lib.SAC256_NACTOR + 1):
+            raise ValueError(f"expected {_lib.SAC256_NACTOR} (+ 1) parameters, got {flat.size}")
+        flat = flat.astype(np.float64).ravel()
+        # the SAC vector stacks the heads into one [4][256] layer: mu's weights, log_std's weights, mu's bias, log_std's bias
+        return np.concatenate([flat[:n01], flat[n01:n01 + 2 * h1], flat[n01 + 4 * h1:n01 + 4 * h1 + 2]])
     if head == "ddpg":
         flat = flatten_ddpg_state_dict(params) if isinstance(params, dict) else np.asarray(params)
         if flat.size != _lib.DDPG_NACTOR:
@@ -342,8 +374,8 @@ def _actor_flat(params, head):
         return flat.astype(np.float64).ravel()
     flat = flatten_sac_actor(params) if isinstance(params, dict) else np.asarray(params)
     if flat.size in (_lib.SAC256_NACTOR, _lib.SAC256_NACTOR + 1):
-        raise ValueError("this is a [256, 256] SAC actor (net_arch='sb3'): the int8 actor kernel has the reference widths pi=[300, 200] "
-                         "only and cannot run it")
+        raise ValueError("this is a [256, 256] SAC actor (net_arch='sb3'): with the default net_arch the int8 actor is built at the "
+                         "reference widths pi=[300, 200]; pass net_arch='sb3' to quantize_actor")
     if flat.size not in (_lib.SAC_NACTOR, _lib.SAC_NACTOR + 1):
         raise ValueError(f"expected {_lib.SAC_NACTOR} (+ 1) parameters, got {flat.size}")
     flat = flat.astype(np.float64).ravel()
@@ -351,15 +383,18 @@ def _actor_flat(params, head):
     return np.concatenate([flat[:n01], flat[n01:n01 + 400], flat[n01 + 800:n01 + 802]])
 
 
-def quantize_actor(params, calibration_obs=None, head="ddpg"):
+def quantize_actor(params, calibration_obs=None, head="ddpg", net_arch="reference"):
     """Post-training int8 quantisation of the off-policy actor -> QuantActorModel.  `params`: the flat DDPG_NACTOR vector
     (DeviceDDPGNets) or an SB3 / train-tool state_dict; with head = "sac" a SAC actor (flat SAC_NACTOR (+ 1) or a state_dict), of
     which the deterministic action tanh(mu(s)) is quantised and the log_std head dropped.  `calibration_obs` [k, 6] as in
     quantize_policy, whose rules hold here too: half away from zero, symmetric weights per output channel, bias_scale = input
     scale x ws, ranges from the FLOAT network in fp64 on the calibration rows.  A hidden layer's output is the POST-ReLU
     activation: range [0, max], so its zero point is always -128 (the code of real 0; a degenerate range gets scale 1).  The
-    output pre-activation gets an asymmetric range; the tanh table's result has scale 1 / 128 and zero point 0."""
-    flat = _actor_flat(params, head)
+    output pre-activation gets an asymmetric range; the tanh table's result has scale 1 / 128 and zero point 0.
+
+    net_arch = "sb3" (with head = "sac"): a SAC actor at SB3's default widths [256, 256] -- flat SAC256_NACTOR (+ 1) or a state_dict
+    in either naming; the rules are the same.  With the default, "reference", such an actor is refused."""
+    flat = _actor_flat(params, head, net_arch)
     cal = np.asarray(REFERENCE_CALIBRATION if calibration_obs is None else calibration_obs, np.float64)
     if cal.ndim != 2 or cal.shape[1] != 6 or cal.shape[0] < 1 or not np.isfinite(cal).all():
         raise ValueError("calibration_obs: expected finite [k, 6]")
@@ -368,7 +403,7 @@ def quantize_actor(params, calibration_obs=None, head="ddpg"):
     in_scale, in_zero = _activation_qparams(cal.min(), cal.max())
     input_scale, input_zero = in_scale, in_zero
     x, off, layers = cal, 0, []
-    for k, (n_in, n_out) in enumerate(_ACTOR_SIZES):
+    for k, (n_in, n_out) in enumerate(_actor_sizes(net_arch)):
         W = flat[off:off + n_in * n_out].reshape(n_out, n_in); off += n_in * n_out
         b = flat[off:off + n_out]; off += n_out
         amax = np.abs(W).max(axis=1)
@@ -391,7 +426,8 @@ def quantize_actor(params, calibration_obs=None, head="ddpg"):
 
 
 class QuantActor:
-    """The int8 off-policy actor evaluated by the HIP kernel: obs [n, 6] -> action [n, 2], with integer arithmetic only"""
+    """The int8 off-policy actor evaluated by the HIP kernel: obs [n, 6] -> action [n, 2], with integer arithmetic only.  The
+    handle is created for the widths of `model` (model.net_arch) and serves models of those widths only."""
 
     def __init__(self, model, device=0):
         if not torch.cuda.is_available():
@@ -399,9 +435,10 @@ class QuantActor:
         self.L = _lib.lib()
         self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
         h = C.c_void_p()
-        rc = self.L.brs_qpolicy_actor_create(self.device.index, C.byref(h))
+        self.net_arch = model.net_arch
+        rc = self.L.brs_qpolicy_actor_create_arch(self.device.index, _ACTOR_ARCH_ID[self.net_arch], C.byref(h))
         if rc != 0:
-            raise BrsError(f"brs_qpolicy_actor_create failed ({rc}): {self.L.brs_qpolicy_actor_last_error(None).decode()}")
+            raise BrsError(f"brs_qpolicy_actor_create_arch failed ({rc}): {self.L.brs_qpolicy_actor_last_error(None).decode()}")
         self.h = h
         self.set_model(model)
 
@@ -421,7 +458,7 @@ class QuantActor:
             raise BrsError(f"{what} failed ({rc}): {self.L.brs_qpolicy_actor_last_error(self.h).decode()}")
 
     def set_model(self, model):
-        """load another QuantActorModel (synchronous; takes effect on the next act)"""
+        """load another QuantActorModel of the handle's widths (synchronous; takes effect on the next act)"""
         m, keep = model.c_model()
         self._check(self.L.brs_qpolicy_actor_set_model(self.h, C.byref(m)), "brs_qpolicy_actor_set_model")
         del keep

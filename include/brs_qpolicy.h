@@ -96,6 +96,14 @@ int brs_qpolicy_act(brs_qpolicy*, int32_t n, const float* obs_dev, float* action
  *   5. tanh         output layer only: q <- table[q + 128], made by the caller; no transcendental on the device
  *   6. output       action = (float)((double)(q - action_zero) action_scale), not clipped; the code q is available too
  *
+ * A SECOND NETWORK, the same six steps at other hidden widths: SB3's default net_arch = [256, 256], what its SAC trains,
+ *
+ *     obs[6] -> 256 -> ReLU -> 256 -> ReLU -> 2 -> tanh
+ *
+ * (the deterministic action tanh(mu) of a BRS_ARCH_SAC_DEFAULT actor of include/brs_policy.h).  A handle serves ONE of the two
+ * networks, fixed when it is created (brs_qpolicy_actor_create_arch); the model struct is the same, its sizes are the network's.
+ * Step 2's int32 bound at these widths: K = 256, |sum| <= 256 x 128 x 255 < 2^23, next to the bias.
+ *
  * The entry points are named brs_qpolicy_actor_... because every function this header declares belongs to the
  * brs_qpolicy_ family of the library's symbol table.
  */
@@ -103,19 +111,28 @@ int brs_qpolicy_act(brs_qpolicy*, int32_t n, const float* obs_dev, float* action
 #define BRS_QACTOR_H0 300
 #define BRS_QACTOR_H1 200
 #define BRS_QACTOR_ACT 2
+#define BRS_QACTOR256_H0 256
+#define BRS_QACTOR256_H1 256
+/* the architecture of a handle: the values of BRS_ARCH_REFERENCE and BRS_ARCH_SAC_DEFAULT of include/brs_policy.h, which this
+ * header does not include (the library asserts that they are equal) */
+#define BRS_QACTOR_ARCH_REFERENCE 0
+#define BRS_QACTOR_ARCH_SAC_DEFAULT 1
 
 typedef struct brs_qactor_model {
   double input_scale;  /* of the observation */
   int32_t input_zero;
   int32_t action_zero; /* zero point of the output table's result */
   double action_scale; /* its scale */
-  brs_qlayer layer[3]; /* 6/300, 300/200, 200/2; only layer[2] has a table */
+  brs_qlayer layer[3]; /* 6/300, 300/200, 200/2 (or 6/256, 256/256, 256/2); only layer[2] has a table */
 } brs_qactor_model;
 
 typedef struct brs_qactor brs_qactor;
 
-/* needs a HIP device */
+/* needs a HIP device; a handle for the 6-300-200-2 network (BRS_QACTOR_ARCH_REFERENCE) */
 int brs_qpolicy_actor_create(int32_t device, brs_qactor** out);
+/* the same for the network of `arch`: BRS_QACTOR_ARCH_REFERENCE (6-300-200-2) or BRS_QACTOR_ARCH_SAC_DEFAULT (6-256-256-2).  The
+ * handle remembers it.  An unknown arch or a NULL `out` is BRS_ERR_ARG. */
+int brs_qpolicy_actor_create_arch(int32_t device, int32_t arch, brs_qactor** out);
 int brs_qpolicy_actor_destroy(brs_qactor*);
 const char* brs_qpolicy_actor_last_error(const brs_qactor*);
 
@@ -124,12 +141,18 @@ const char* brs_qpolicy_actor_last_error(const brs_qactor*);
  * zero point is in [-128, 127], every scale is positive and finite, every multiplier is valid, and no int8 input can
  * take an accumulator (with or without the folded zero point) out of int32.  The model is checked BEFORE the handle is
  * looked at: with a NULL handle a bad model gives BRS_ERR_ARG and a good one BRS_ERR_STATE.  Synchronous: it drains the
- * device, then copies. */
+ * device, then copies.  The sizes are those of the HANDLE's network (with a NULL handle: 6/300/200/2); a model of the other
+ * network is BRS_ERR_ARG, and the message names the network the handle serves. */
 int brs_qpolicy_actor_set_model(brs_qactor*, const brs_qactor_model*);
+
+/* the checks of brs_qpolicy_actor_set_model for the network of `arch`, and nothing else: host only, no device and no handle.
+ * BRS_OK for a model that set_model would load on a handle of that arch; otherwise BRS_ERR_ARG and set_model's message in
+ * brs_qpolicy_actor_last_error(NULL).  An unknown arch is BRS_ERR_ARG. */
+int brs_qpolicy_actor_check_model(int32_t arch, const brs_qactor_model*);
 
 /* one step of the int8 actor for n envs: obs[n][6] floats -> action[n][2] floats, and the int8 codes action_q[n][2]
  * (may be NULL).  Device pointers; only enqueues on `stream`: no synchronisation, no allocation, capturable into a
- * graph.  Rows beyond n - 1 are never written. */
+ * graph.  Rows beyond n - 1 are never written.  The kernel is the one of the handle's network. */
 int brs_qpolicy_actor_act(brs_qactor*, int32_t n, const float* obs_dev, float* action_dev, int8_t* action_q_dev, void* stream);
 
 #ifdef __cplusplus

@@ -13,10 +13,13 @@ output, unclipped, as the reference does (envs/RobotMoveBaseEnv.py:178-208).
                its dequantised weights
 --params PATH  a float parameter vector (.npy, the order of include/brs_policy.h): quantised here with quantize_policy and
                the reference's calibration rows; the float run uses the vector itself
---actor PATH   an OFF-POLICY actor, 6-300-200-2: the flat vector (.npy) or the state_dict (.pt) that
+--actor PATH   an OFF-POLICY actor, 6-300-200-2 or (SAC) 6-256-256-2: the flat vector (.npy) or the state_dict (.pt) that
                tools/train_ddpg_torch.py, train_td3_torch.py or train_sac_torch.py write with --save-actor; --algo ddpg|td3|sac
                says how to read it.  Quantised here with quantize_actor; the float run is DeviceDDPGNets.act with sigma 0, or
-               DeviceSACNets.act deterministic, and the int8 run QuantActor (for SAC: the deterministic action tanh(mu))
+               DeviceSACNets.act deterministic, and the int8 run QuantActor (for SAC: the deterministic action tanh(mu)).
+               With --algo sac the widths are read off the file: the reference's pi=[300, 200], or SB3's default [256, 256] --
+               what tools/train_sac_torch.py --net-arch sb3 --save-actor writes, or an SB3 SAC state_dict (INTEGRATION.md 1d);
+               both runs then use that architecture, and the JSON lines name it (net_arch)
 
     python tools/eval_quant_policy.py --env Env01-v1 --actor actor.npy --algo td3 --save actor_int8.npz
 """
@@ -46,18 +49,37 @@ def evaluate(env, n, steps, act, seed=123):
                 mean_ep_len=s.mean_len, median_ep_len=median, mean_reward_per_step=(s.sum_ret + s.running_ret) / (n * steps))
 
 
+def read_actor(path):
+    """a .pt state_dict or a .npy flat vector, as the train tools' --save-actor writes them"""
+    return torch.load(path, map_location="cpu", weights_only=True) if path.endswith(".pt") else np.load(path).astype(np.float32).ravel()
+
+
+def read_sac_actor(path):
+    """-> (what the file holds, the flat SAC actor vector with log_ent_coef [nactor + 1], net_arch): the widths are those of the
+    tensors' shapes (flatten_sac_actor) or of the vector's length"""
+    from balance_robot_mujoco_rl_amd import flatten_sac_actor
+    params = read_actor(path)
+    flat = flatten_sac_actor(params) if isinstance(params, dict) else params
+    net_arch = {_lib.SAC_NACTOR: "reference", _lib.SAC256_NACTOR: "sb3"}.get(flat.size, None) or \
+               {_lib.SAC_NACTOR + 1: "reference", _lib.SAC256_NACTOR + 1: "sb3"}.get(flat.size, None)
+    if net_arch is None:
+        raise ValueError(f"{path}: a SAC actor has {_lib.SAC_NACTOR} (+ 1) elements at pi=[300, 200] or {_lib.SAC256_NACTOR} (+ 1) at [256, 256], "
+                         f"this one {flat.size}")
+    if flat.size in (_lib.SAC_NACTOR, _lib.SAC256_NACTOR):
+        flat = np.concatenate([flat, np.zeros(1, np.float32)])   # log_ent_coef: unused by act
+    return params, np.ascontiguousarray(flat, np.float32), net_arch
+
+
 def evaluate_actor(a):
     """--actor: the same three lines for the off-policy actor"""
-    from balance_robot_mujoco_rl_amd import DeviceDDPGNets, DeviceSACNets, QuantActor, flatten_sac_actor, quantize_actor
+    from balance_robot_mujoco_rl_amd import DeviceDDPGNets, DeviceSACNets, QuantActor, quantize_actor
     sac = a.algo == "sac"
-    params = torch.load(a.actor, map_location="cpu", weights_only=True) if a.actor.endswith(".pt") else np.load(a.actor).astype(np.float32).ravel()
-    qm = quantize_actor(params, head="sac" if sac else "ddpg")
+    params, flat, net_arch = read_sac_actor(a.actor) if sac else (read_actor(a.actor), None, "reference")
+    qm = quantize_actor(params, head="sac" if sac else "ddpg", net_arch=net_arch)
     if a.save:
         qm.save(a.save)
     if sac:
-        flat = flatten_sac_actor(params) if isinstance(params, dict) else params
-        flat = np.concatenate([flat, np.zeros(1, np.float32)]) if flat.size == _lib.SAC_NACTOR else flat   # log_ent_coef: unused by act
-        nets = DeviceSACNets(device=0)
+        nets = DeviceSACNets(device=0, net_arch=net_arch)
         weights = torch.from_numpy(np.ascontiguousarray(flat, np.float32)).cuda()
         float_act, name = (lambda obs, t: nets.act(weights, obs, t, deterministic=True)), "float (DeviceSACNets, deterministic)"
     else:
@@ -65,7 +87,8 @@ def evaluate_actor(a):
         weights = torch.from_numpy(ddpg_flat(params)).cuda()
         float_act, name = (lambda obs, t: nets.act(weights, obs, t, 0.0)), "float (DeviceDDPGNets, sigma 0)"
     qact = QuantActor(qm, device=0)
-    common = dict(env=a.env, envs=a.envs, steps=a.steps, policy=f"{os.path.basename(a.actor)} ({a.algo} actor, quantised here)", build_id=_lib.build_id())
+    common = dict(env=a.env, envs=a.envs, steps=a.steps, policy=f"{os.path.basename(a.actor)} ({a.algo} actor, quantised here)",
+                  net_arch=net_arch, build_id=_lib.build_id())
     f = evaluate(a.env, a.envs, a.steps, float_act)
     print(json.dumps(dict(common, network=name, **f)))
     q = evaluate(a.env, a.envs, a.steps, lambda obs, t: qact.act(obs))
