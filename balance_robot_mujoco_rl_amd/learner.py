@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .policy import SB3_LAYOUT, _need, _p
-from .sim import BrsError
+from ._handle import Handle, _need, _numpy, _p
+from .policy import SB3_LAYOUT
 
 NPARAM, NSTAT = _lib.POLICY_NPARAM, _lib.LEARNER_NSTAT
 # tools/train_ppo_torch.py's ActorCritic, in the order of the flat parameter vector (same shapes as SB3_LAYOUT)
@@ -39,8 +39,7 @@ def flatten_state_dict(sd):
     taken as it is: in units of `ret_scale` (the tool's buffer of that name; 1 for SB3)"""
     parts = []
     for name, shape in zip(NAMINGS[naming_of(sd)], _SHAPES):
-        a = sd[name]
-        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = _numpy(sd[name])
         if tuple(a.shape) != shape:
             raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
         parts.append(a.astype(np.float32).ravel())
@@ -79,42 +78,18 @@ class LearnerStats:
     grad_norm_vf: float
 
 
-class _DeviceLearner:
+class _DeviceLearner(Handle):
     """what the learners on a brs_learner handle share: the handle, the flat parameter vector and its conversions, the stats"""
+    _FAMILY, _WHAT = "brs_learner", "the on-device learner has"
 
-    def _create(self, device, max_workgroups):
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the on-device learner has no CPU fallback")
-        self.L = _lib.lib()
-        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
-        h = C.c_void_p()
-        rc = self.L.brs_learner_create(self.device.index, int(max_workgroups), C.byref(h))
-        if rc != 0:
-            raise BrsError(f"brs_learner_create failed ({rc}): {self.L.brs_learner_last_error(None).decode()}")
-        self.h = h
+    def _open(self, device, max_workgroups):
+        self._attach(device)
+        self._create("brs_learner_create", self.device.index, int(max_workgroups))
         self.ret_scale, self.actor_on = 1.0, True
         self.params, self.grad_buf, self._rollout = self._zeros(NPARAM), self._zeros(NPARAM + NSTAT), self._zeros(NPARAM)
 
     def _zeros(self, n):
         return torch.zeros(n, dtype=torch.float32, device=self.device)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.brs_learner_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise BrsError(f"{what} failed ({rc}): {self.L.brs_learner_last_error(self.h).decode()}")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---- parameters
     def load(self, state_dict):
@@ -150,7 +125,7 @@ class DevicePPOLearner(_DeviceLearner):
 
     def __init__(self, device=0, lr=3e-4, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, separate_clip=False, target_kl=None,
                  normalize_advantage=True, max_workgroups=0, betas=(0.9, 0.999), eps=1e-8):
-        self._create(device, max_workgroups)
+        self._open(device, max_workgroups)
         self.lr, self.clip_range, self.vf_coef, self.ent_coef = float(lr), float(clip_range), float(vf_coef), float(ent_coef)
         self.max_grad_norm, self.separate_clip, self.target_kl = float(max_grad_norm), bool(separate_clip), target_kl
         self.normalize_advantage, self.betas, self.eps = bool(normalize_advantage), (float(betas[0]), float(betas[1])), float(eps)
@@ -205,7 +180,7 @@ class DeviceA2CLearner(_DeviceLearner):
 
     def __init__(self, device=0, lr=7e-4, alpha=0.99, eps=1e-5, vf_coef=1.0, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=False,
                  separate_clip=False, ret_scale=1.0, actor_on=True, max_workgroups=0):
-        self._create(device, max_workgroups)
+        self._open(device, max_workgroups)
         self.lr, self.alpha, self.eps, self.vf_coef, self.ent_coef = float(lr), float(alpha), float(eps), float(vf_coef), float(ent_coef)
         self.max_grad_norm, self.normalize_advantage, self.separate_clip = float(max_grad_norm), bool(normalize_advantage), bool(separate_clip)
         self.ret_scale, self.actor_on = float(ret_scale), bool(actor_on)

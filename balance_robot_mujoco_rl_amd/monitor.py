@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .sim import BrsError
+from ._handle import BrsError, Handle, _need, _p
 
 
 def episode_count_targets(n_eval_episodes, n_envs):
@@ -82,50 +82,16 @@ def median_from_histogram(hist, lower=False):
     return None if lo is None or hi is None else 0.5 * (lo + hi)
 
 
-def _need(t, name, dtype, shape, device):
-    """the C ABI takes raw pointers: a sliced, float64 or host tensor would be read as garbage without any error"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
-        raise ValueError(f"{name}: expected a tensor on {device}, got {getattr(t, 'device', type(t))}")
-    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: expected contiguous {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)} "
-                         f"(contiguous: {t.is_contiguous()})")
-    return t
-
-
-class EpisodeMonitor:
+class EpisodeMonitor(Handle):
     """SB3's Monitor / VecMonitor for the n envs of a BatchedSim, on the device.  update() only enqueues a kernel; stats(),
     histogram() and episodes() wait for the stream and copy a few numbers out."""
+    _FAMILY, _WHAT = "brs_monitor", "the episode monitor has"
 
     def __init__(self, n, device=0, max_len=6000, log_capacity=0):
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the episode monitor has no CPU fallback")
-        self.L = _lib.lib()
-        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+        self._attach(device)
         self.n, self.max_len, self.log_capacity = int(n), int(max_len), int(log_capacity)
-        h = C.c_void_p()
-        rc = self.L.brs_monitor_create(self.device.index, self.n, self.max_len, self.log_capacity, C.byref(h))
-        if rc != 0:
-            raise BrsError(f"brs_monitor_create failed ({rc}): {self.L.brs_monitor_last_error(None).decode()}")
-        self.h = h
+        self._create("brs_monitor_create", self.device.index, self.n, self.max_len, self.log_capacity)
         self._rows = 0
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.brs_monitor_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise BrsError(f"{what} failed ({rc}): {self.L.brs_monitor_last_error(self.h).decode()}")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def reset(self, targets=None):
         """zero everything, running episodes included; `targets`: episodes of each env that count (None: all of them)"""
@@ -143,8 +109,7 @@ class EpisodeMonitor:
         n, d = self.n, self.device
         _need(reward, "reward", torch.float32, (n,), d); _need(terminated, "terminated", torch.uint8, (n,), d)
         _need(truncated, "truncated", torch.uint8, (n,), d)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        self._check(self.L.brs_monitor_update(self.h, p(reward), p(terminated), p(truncated), self._stream()), "brs_monitor_update")
+        self._check(self.L.brs_monitor_update(self.h, _p(reward), _p(terminated), _p(truncated), self._stream()), "brs_monitor_update")
 
     def stats(self):
         s = _lib.BrsEpisodeStats()

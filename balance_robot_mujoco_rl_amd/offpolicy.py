@@ -10,22 +10,32 @@ DESIGN.md 7.6), or the caller's (tools/train_ddpg_torch.py does it in torch by d
 stream."""
 import ctypes as C
 
-import numpy as np
 import torch
 
-from . import _lib
-from .policy import _need, _p
-from .sim import BrsError
+from . import _lib, nets
+from ._handle import BrsError, DeviceObject, Handle, _need, _p
+from .nets import ARCHS, REFERENCE
 
-NACTOR, NCRITIC = _lib.DDPG_NACTOR, _lib.DDPG_NCRITIC
-# (layer, shape) of the two networks in the order of their flat parameter vectors
-ACTOR_SHAPES = [((300, 6), (300,)), ((200, 300), (200,)), ((2, 200), (2,))]
-CRITIC_SHAPES = [((200, 8), (200,)), ((150, 200), (150,)), ((1, 150), (1,))]
+# the lengths and (weight, bias) shapes of the flat parameter vectors, all from the table of nets.py: the reference's widths ...
+NACTOR, NCRITIC = REFERENCE.actor.count, REFERENCE.critic.count
+ACTOR_SHAPES, CRITIC_SHAPES = REFERENCE.actor.shapes, REFERENCE.critic.shapes
+SAC_NACTOR, SAC_GRAD_LEN = REFERENCE.nactor, REFERENCE.grad_len
+# ... and SB3's default net_arch = [256, 256] (BRS_ARCH_SAC_DEFAULT; DESIGN.md 7.12)
+NCRITIC256, SAC256_NACTOR = ARCHS["sb3"].ncritic, ARCHS["sb3"].nactor
+# net_arch -> architecture, for the SAC path
+SacArch, SAC_ARCHS, sac_arch = nets.Arch, ARCHS, nets.arch
 # state_dict prefixes of the three Linear layers: SB3's TD3Policy and tools/train_ddpg_torch.py
 NAMINGS = {"sb3": {"actor": "actor.mu.{}.", "critic": "critic.qf0.{}.", "actor_target": "actor_target.mu.{}.",
                    "critic_target": "critic_target.qf0.{}."},
            "tool": {"actor": "actor.{}.", "critic": "critic.{}.", "actor_target": "actor_target.{}.", "critic_target": "critic_target.{}."}}
-_LAYER_INDEX = (0, 2, 4)   # Linear, ReLU, Linear, ReLU, Linear in an nn.Sequential
+# the two critics of TD3 inside one state_dict: SB3's ContinuousCritic (critic.qf0.0.weight, critic.qf1.0.weight) and
+# tools/train_td3_torch.py, which holds them as an nn.ModuleList of two nn.Sequential (critic.0.0.weight, critic.1.0.weight)
+TD3_CRITIC_NAMINGS = {"sb3": "{net}.qf{k}.{i}.", "tool": "{net}.{k}.{i}."}
+# the SAC actor VECTOR [SAC_NACTOR + 1]: latent_pi's two layers, the mu and log_std heads stacked into one [4][200] layer, then
+# log_ent_coef.  SB3's SACPolicy (actor.latent_pi.{0,2}, actor.mu, actor.log_std; log_ent_coef is the algorithm's, not the policy's,
+# and is looked up under that name) and tools/train_sac_torch.py (actor.body.{0,2}, actor.mu, actor.log_std, log_ent_coef)
+SAC_ACTOR_NAMINGS = {"sb3": ("actor.latent_pi.0.", "actor.latent_pi.2.", "actor.mu.", "actor.log_std."),
+                     "tool": ("actor.body.0.", "actor.body.2.", "actor.mu.", "actor.log_std.")}
 
 
 def naming_of(sd):
@@ -39,76 +49,29 @@ def naming_of(sd):
 
 
 def _layout(net, naming):
-    shapes = ACTOR_SHAPES if net.startswith("actor") else CRITIC_SHAPES
-    prefix = NAMINGS[naming][net]
-    return [(prefix.format(i) + kind, shape) for i, pair in zip(_LAYER_INDEX, shapes) for kind, shape in zip(("weight", "bias"), pair)]
+    return (REFERENCE.actor if net.startswith("actor") else REFERENCE.critic).layout(NAMINGS[naming][net])
 
 
 def flatten_ddpg_state_dict(sd, net="actor"):
     """state_dict in either naming -> the flat float32 vector of `net` ('actor', 'critic', 'actor_target', 'critic_target')"""
-    parts = []
-    for name, shape in _layout(net, naming_of(sd)):
-        if name not in sd:
-            raise ValueError(f"{name}: missing")
-        a = sd[name]
-        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-        if tuple(a.shape) != shape:
-            raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
-        parts.append(a.astype(np.float32).ravel())
-    flat = np.concatenate(parts)
-    assert flat.size == (NACTOR if net.startswith("actor") else NCRITIC)
-    return flat
+    return nets.pack(sd, _layout(net, naming_of(sd)))
 
 
 def unflatten_ddpg_state_dict(flat, net="actor", naming="sb3"):
     """the flat vector of `net` -> {name: tensor} in `naming`"""
-    flat = np.ascontiguousarray(flat.detach().cpu().numpy() if hasattr(flat, "detach") else flat, dtype=np.float32)
+    flat = nets.flat_array(flat)
     want = NACTOR if net.startswith("actor") else NCRITIC
     if flat.shape != (want,):
         raise ValueError(f"{net}: expected {want} parameters, got shape {flat.shape}")
-    out, at = {}, 0
-    for name, shape in _layout(net, naming):
-        k = int(np.prod(shape))
-        out[name] = torch.from_numpy(flat[at:at + k].reshape(shape).copy())
-        at += k
-    return out
+    return nets.unpack(flat, _layout(net, naming))
 
 
-# the two critics of TD3 inside one state_dict: SB3's ContinuousCritic (critic.qf0.0.weight, critic.qf1.0.weight) and
-# tools/train_td3_torch.py, which holds them as an nn.ModuleList of two nn.Sequential (critic.0.0.weight, critic.1.0.weight)
-TD3_CRITIC_NAMINGS = {"sb3": "{net}.qf{k}.{i}.", "tool": "{net}.{k}.{i}."}
-
-
-# SB3's default net_arch = [256, 256] (BRS_ARCH_SAC_DEFAULT; DESIGN.md 7.12) next to the reference's widths
-CRITIC256_SHAPES = [((256, 8), (256,)), ((256, 256), (256,)), ((1, 256), (1,))]
-NCRITIC256 = _lib.SAC256_NCRITIC
-_CRITIC_WIDTHS = ((NCRITIC, CRITIC_SHAPES), (NCRITIC256, CRITIC256_SHAPES))
-
-
-def _td3_layout(net, naming, shapes=None):
+def _td3_layout(net, naming, arch):
     if net not in ("critic", "critic_target"):
         raise ValueError(f"net must be 'critic' or 'critic_target', got {net!r}")
     if naming not in TD3_CRITIC_NAMINGS:
         raise ValueError(f"naming must be 'sb3' or 'tool', got {naming!r}")
-    return [(TD3_CRITIC_NAMINGS[naming].format(net=net, k=k, i=i) + kind, shape) for k in (0, 1)
-            for i, pair in zip(_LAYER_INDEX, CRITIC_SHAPES if shapes is None else shapes) for kind, shape in zip(("weight", "bias"), pair)]
-
-
-def _widths_of(sd, layouts, what):
-    """the first of `layouts` (lists of (name, shape)) whose every tensor is in `sd` with its shape; ValueError naming the first
-    tensor that is missing or fits none of them"""
-    for name, _ in layouts[0]:
-        if name not in sd:
-            raise ValueError(f"{name}: missing")
-    for layout in layouts:
-        if all(tuple(sd[name].shape) == shape for name, shape in layout):
-            return layout
-    for i, (name, shape) in enumerate(layouts[0]):
-        if not any(tuple(sd[name].shape) == layout[i][1] for layout in layouts):
-            expected = " or ".join(str(layout[i][1]) for layout in layouts)
-            raise ValueError(f"{name}: expected shape {expected}, got {tuple(sd[name].shape)}")
-    name = next(name for i, (name, shape) in enumerate(layouts[0]) if tuple(sd[name].shape) != shape)
-    raise ValueError(f"{name}: shape {tuple(sd[name].shape)} mixes the widths of two architectures of {what}")
+    return [entry for k in (0, 1) for entry in arch.critic.layout(TD3_CRITIC_NAMINGS[naming].format(net=net, k=k, i="{}"))]
 
 
 def _td3_naming_of(sd, net):
@@ -126,69 +89,60 @@ def flatten_td3_critics(sd, net="critic"):
     critic.qf1.*) and tools/train_td3_torch.py's, an nn.ModuleList of two nn.Sequential (critic.0.{0,2,4}.{weight,bias} and
     critic.1.*).  The widths are read off the shapes: qf=[200, 150], or SB3's default [256, 256] -> [2 NCRITIC256]."""
     naming = _td3_naming_of(sd, net)
-    layout = _widths_of(sd, [_td3_layout(net, naming, shapes) for _, shapes in _CRITIC_WIDTHS], "the critics")
-    parts = []
-    for name, shape in layout:
-        a = sd[name]
-        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-        parts.append(a.astype(np.float32).ravel())
-    flat = np.concatenate(parts)
-    assert flat.size in (2 * NCRITIC, 2 * NCRITIC256)
-    return flat
+    return nets.pack(sd, nets.widths_of(sd, [_td3_layout(net, naming, arch) for arch in ARCHS.values()], "the critics"))
 
 
 def unflatten_td3_critics(flat, net="critic", naming="sb3"):
     """the flat vector [2 NCRITIC] (or [2 NCRITIC256]: the widths follow the length) of the two critics -> {name: tensor} in
     `naming` ('sb3' or 'tool', as flatten_td3_critics)"""
-    flat = np.ascontiguousarray(flat.detach().cpu().numpy() if hasattr(flat, "detach") else flat, dtype=np.float32)
-    shapes = next((shapes for n, shapes in _CRITIC_WIDTHS if flat.shape == (2 * n,)), None)
-    if shapes is None:
-        raise ValueError(f"{net}: expected {2 * NCRITIC} or {2 * NCRITIC256} parameters, got shape {flat.shape}")
-    out, at = {}, 0
-    for name, shape in _td3_layout(net, naming, shapes):
-        k = int(np.prod(shape))
-        out[name] = torch.from_numpy(flat[at:at + k].reshape(shape).copy())
-        at += k
-    return out
+    flat = nets.flat_array(flat)
+    arch = next((arch for arch in ARCHS.values() if flat.shape == (2 * arch.ncritic,)), None)
+    if arch is None:
+        raise ValueError(f"{net}: expected {' or '.join(str(2 * a.ncritic) for a in ARCHS.values())} parameters, got shape {flat.shape}")
+    return nets.unpack(flat, _td3_layout(net, naming, arch))
 
 
-def _device(device):
-    return torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+def _sac_naming_of(sd):
+    for naming, prefixes in SAC_ACTOR_NAMINGS.items():
+        if prefixes[0] + "weight" in sd:
+            return naming
+    raise ValueError("neither SB3's SACPolicy naming (actor.latent_pi.0.weight) nor the SAC tool's (actor.body.0.weight)")
 
 
-class DeviceDDPGNets:
+def flatten_sac_actor(sd):
+    """state_dict in either naming, with a scalar `log_ent_coef` in it -> the flat float32 actor vector [SAC_NACTOR + 1], or
+    [SAC256_NACTOR + 1] for SB3's default [256, 256]: the widths are read off the shapes"""
+    prefixes = SAC_ACTOR_NAMINGS[_sac_naming_of(sd)]
+    layout = nets.widths_of(sd, [arch.sac_actor_layout(prefixes) for arch in ARCHS.values()], "the SAC actor")
+    if "log_ent_coef" not in sd:
+        raise ValueError("log_ent_coef: missing")
+    t = nets.flat_array(sd["log_ent_coef"])
+    if t.size != 1:
+        raise ValueError(f"log_ent_coef: expected one element, got shape {tuple(t.shape)}")
+    return nets.pack({**sd, "log_ent_coef": t.reshape(1)}, layout + [("log_ent_coef", (1,))])
+
+
+def unflatten_sac_actor(flat, naming="sb3"):
+    """the actor vector [SAC_NACTOR + 1] (or [SAC256_NACTOR + 1]: the widths follow the length) -> {name: tensor} in `naming`
+    ('sb3' or 'tool'), log_ent_coef as a tensor of shape (1,)"""
+    flat = nets.flat_array(flat)
+    arch = next((arch for arch in ARCHS.values() if flat.shape == (arch.nactor + 1,)), None)
+    if arch is None:
+        raise ValueError(f"expected {' or '.join(str(a.nactor + 1) for a in ARCHS.values())} elements, got shape {flat.shape}")
+    if naming not in SAC_ACTOR_NAMINGS:
+        raise ValueError(f"naming must be 'sb3' or 'tool', got {naming!r}")
+    return nets.unpack(flat, arch.sac_actor_layout(SAC_ACTOR_NAMINGS[naming]) + [("log_ent_coef", (1,))])
+
+
+class DeviceDDPGNets(Handle):
     """SB3's TD3Policy networks with the reference's widths, evaluated by the HIP kernels.  The parameter vectors are arguments of
     every call (flat float32 device tensors, read in place): the caller's optimiser and Polyak update write them."""
+    _FAMILY, _WHAT, arch = "brs_ddpg", "the on-device DDPG networks have", REFERENCE
 
     def __init__(self, device=0, seed=0, env_index_base=0):
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the on-device DDPG networks have no CPU fallback")
-        self.L = _lib.lib()
-        self.device = _device(device)
-        h = C.c_void_p()
-        rc = self.L.brs_ddpg_create(self.device.index, C.byref(h))
-        if rc != 0:
-            raise BrsError(f"brs_ddpg_create failed ({rc}): {self.L.brs_ddpg_last_error(None).decode()}")
-        self.h = h
+        self._attach(device)
+        self._create("brs_ddpg_create", self.device.index)
         self.seed, self.env_index_base = int(seed), int(env_index_base)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.brs_ddpg_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise BrsError(f"{what} failed ({rc}): {self.L.brs_ddpg_last_error(self.h).decode()}")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def act(self, actor_params, obs, step, sigma, random=False, out=None, mean=None, noise=None):
         """SB3 _sample_action: obs [n,6] -> action [n,2] = clip(mean + sigma z); `random`: the learning_starts phase (uniform mean,
@@ -209,9 +163,9 @@ class DeviceDDPGNets:
         return out
 
     def q(self, critic_params, obs, action, out=None):
-        """Q(s, a): obs [n,6], action [n,2] -> [n]"""
+        """Q(s, a) of one critic of this object's architecture: obs [n,6], action [n,2] -> [n]"""
         d, f32, n = self.device, torch.float32, obs.shape[0]
-        _need(critic_params, "critic_params", f32, (NCRITIC,), d); _need(obs, "obs", f32, (n, 6), d); _need(action, "action", f32, (n, 2), d)
+        _need(critic_params, "critic_params", f32, (self.arch.ncritic,), d); _need(obs, "obs", f32, (n, 6), d); _need(action, "action", f32, (n, 2), d)
         if out is None:
             out = torch.empty(n, dtype=f32, device=d)
         _need(out, "q", f32, (n,), d)
@@ -255,15 +209,14 @@ def _storage(obs, next_obs, action, reward, done):
     return _lib.BrsReplayStorage(obs.data_ptr(), next_obs.data_ptr(), action.data_ptr(), reward.data_ptr(), done.data_ptr())
 
 
-class DeviceReplayBuffer:
+class DeviceReplayBuffer(DeviceObject):
     """SB3's ReplayBuffer for the n envs of a BatchedSim, resident in HBM, time-major: obs / next_obs [cap][n][6], action
     [cap][n][2], reward / done [cap][n].  add() and sample() each enqueue one kernel; `pos` and `full` are host integers."""
 
+    _WHAT = "the on-device replay buffer has"
+
     def __init__(self, n_envs, capacity_steps, device=0, seed=0):
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the on-device replay buffer has no CPU fallback")
-        self.L = _lib.lib()
-        self.device = _device(device)
+        self._attach(device)
         self.n, self.cap = int(n_envs), int(capacity_steps)
         if self.n < 1 or self.cap < 1 or self.n * self.cap > 2 ** 31 - 1:
             raise ValueError(f"need n_envs >= 1, capacity_steps >= 1 and their product <= 2^31 - 1, got {n_envs}, {capacity_steps}")
@@ -287,10 +240,7 @@ class DeviceReplayBuffer:
     def __len__(self):
         return self.size
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _check(self, rc, what):
+    def _check(self, rc, what):   # the replay calls take no handle: one error slot for the family
         if rc != 0:
             raise BrsError(f"{what} failed ({rc}): {self.L.brs_replay_last_error().decode()}")
 
@@ -360,53 +310,65 @@ class DeviceOffPolicyCollector:
         return self
 
 
-class DeviceDDPGLearner:
-    """SB3's TD3.train as DDPG uses it (one critic, no delay, no target noise) by the HIP kernels of brs_ddpg_learner_*: the
-    gradient of mse(Q(s, a), y) w.r.t. the critic, the gradient of -mean Q(s, pi(s)) w.r.t. the actor, torch.optim.Adam's step and
-    the Polyak update.  The four networks are the caller's flat float32 device tensors, updated in place; this object owns the two
-    gradient buffers, the four moment vectors and the two step counters.  grad and apply are separate calls: a data-parallel
-    caller all-reduces-and-divides `grad_critic` / `grad_actor` in between."""
+class _OffPolicyLearner(Handle):
+    """what the learners on a brs_ddpg_learner handle share: its creation, Adam's settings, the one apply call, and the optimiser
+    state as a state_dict.  `_TENSORS` / `_COUNTERS` name the attributes that state is made of."""
+    _FAMILY = "brs_ddpg_learner"
+    _TENSORS = _COUNTERS = ()
 
-    def __init__(self, device=0, max_batch=256, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, tau=0.005):
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the on-device DDPG learner has no CPU fallback")
-        self.L = _lib.lib()
-        self.device = _device(device)
+    def _create_learner(self, create, max_batch, lr, betas, eps, tau, *args):
         self.max_batch, self.tau = int(max_batch), float(tau)
         self.cfg = _lib.BrsAdamConfig(float(lr), float(betas[0]), float(betas[1]), float(eps))
-        h = C.c_void_p()
-        rc = self.L.brs_ddpg_learner_create(self.device.index, self.max_batch, C.byref(h))
-        if rc != 0:
-            raise BrsError(f"brs_ddpg_learner_create failed ({rc}): {self.L.brs_ddpg_learner_last_error(None).decode()}")
-        self.h = h
-        z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.grad_critic, self.grad_actor = z(NCRITIC + _lib.DDPG_NSTAT), z(NACTOR + _lib.DDPG_NSTAT)
-        self.m_critic, self.v_critic, self.m_actor, self.v_actor = z(NCRITIC), z(NCRITIC), z(NACTOR), z(NACTOR)
-        self.steps_critic = self.steps_actor = 0
+        self._create(create, self.device.index, self.max_batch, *args)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.brs_ddpg_learner_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise BrsError(f"{what} failed ({rc}): {self.L.brs_ddpg_learner_last_error(self.h).decode()}")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _zeros(self, n):
+        return torch.zeros(n, dtype=torch.float32, device=self.device)
 
     def scratch(self):
         """(device address, bytes) of the handle's one allocation"""
         ptr, size = C.c_void_p(), C.c_int64()
         self._check(self.L.brs_ddpg_learner_scratch(self.h, C.byref(ptr), C.byref(size)), "brs_ddpg_learner_scratch")
         return ptr.value, size.value
+
+    def _apply(self, n, params, grad, grad_len, mom, vel, target, step, name):
+        d, f32 = self.device, torch.float32
+        _need(params, name, f32, (n,), d); _need(grad, "grad", f32, (grad_len,), d)
+        _need(mom, "m_" + name, f32, (n,), d); _need(vel, "v_" + name, f32, (n,), d)
+        if target is not None:
+            _need(target, name + "_target", f32, (n,), d)
+        self._check(self.L.brs_ddpg_learner_apply(self.h, n, _p(params), _p(grad), _p(mom), _p(vel), _p(target), C.byref(self.cfg), step,
+                                                  self.tau, self._stream()), "brs_ddpg_learner_apply")
+
+    def state_dict(self):
+        return {**{k: getattr(self, k).clone() for k in self._TENSORS}, **{k: getattr(self, k) for k in self._COUNTERS}}
+
+    def load_state_dict(self, sd):
+        for k in self._TENSORS:
+            t = getattr(self, k)
+            src = torch.as_tensor(sd[k])
+            if tuple(src.shape) != tuple(t.shape):
+                raise ValueError(f"{k}: expected shape {tuple(t.shape)}, got {tuple(src.shape)}")
+            t.copy_(src.to(device=self.device, dtype=torch.float32))
+        for k in self._COUNTERS:
+            setattr(self, k, int(sd[k]))
+
+
+class DeviceDDPGLearner(_OffPolicyLearner):
+    """SB3's TD3.train as DDPG uses it (one critic, no delay, no target noise) by the HIP kernels of brs_ddpg_learner_*: the
+    gradient of mse(Q(s, a), y) w.r.t. the critic, the gradient of -mean Q(s, pi(s)) w.r.t. the actor, torch.optim.Adam's step and
+    the Polyak update.  The four networks are the caller's flat float32 device tensors, updated in place; this object owns the two
+    gradient buffers, the four moment vectors and the two step counters.  grad and apply are separate calls: a data-parallel
+    caller all-reduces-and-divides `grad_critic` / `grad_actor` in between."""
+    _WHAT = "the on-device DDPG learner has"
+    _TENSORS, _COUNTERS = ("m_critic", "v_critic", "m_actor", "v_actor"), ("steps_critic", "steps_actor")
+
+    def __init__(self, device=0, max_batch=256, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, tau=0.005):
+        self._attach(device)
+        self._create_learner("brs_ddpg_learner_create", max_batch, lr, betas, eps, tau)
+        z = self._zeros
+        self.grad_critic, self.grad_actor = z(NCRITIC + _lib.DDPG_NSTAT), z(NACTOR + _lib.DDPG_NSTAT)
+        self.m_critic, self.v_critic, self.m_actor, self.v_actor = z(NCRITIC), z(NCRITIC), z(NACTOR), z(NACTOR)
+        self.steps_critic = self.steps_actor = 0
 
     def critic_grad(self, critic, obs, action, y, out=None):
         """-> [NCRITIC + 2]: the gradient of Lc = mean (Q(s, a) - y)^2 in the critic's flat order, then Lc and mean Q"""
@@ -429,24 +391,15 @@ class DeviceDDPGLearner:
                     "brs_ddpg_learner_actor_grad")
         return out
 
-    def _apply(self, n, params, grad, mom, vel, target, step, name):
-        d, f32 = self.device, torch.float32
-        _need(params, name, f32, (n,), d); _need(grad, "grad", f32, (n + _lib.DDPG_NSTAT,), d)
-        _need(mom, "m_" + name, f32, (n,), d); _need(vel, "v_" + name, f32, (n,), d)
-        if target is not None:
-            _need(target, name + "_target", f32, (n,), d)
-        self._check(self.L.brs_ddpg_learner_apply(self.h, n, _p(params), _p(grad), _p(mom), _p(vel), _p(target), C.byref(self.cfg), step,
-                                                  self.tau, self._stream()), "brs_ddpg_learner_apply")
-
     def apply_critic(self, critic, critic_target=None, grad=None):
         """Adam's step on `critic` from grad_critic (or `grad`), then critic_target += tau (critic - critic_target)"""
-        self._apply(NCRITIC, critic, self.grad_critic if grad is None else grad, self.m_critic, self.v_critic, critic_target,
-                    self.steps_critic + 1, "critic")
+        self._apply(NCRITIC, critic, self.grad_critic if grad is None else grad, NCRITIC + _lib.DDPG_NSTAT, self.m_critic, self.v_critic,
+                    critic_target, self.steps_critic + 1, "critic")
         self.steps_critic += 1
 
     def apply_actor(self, actor, actor_target=None, grad=None):
-        self._apply(NACTOR, actor, self.grad_actor if grad is None else grad, self.m_actor, self.v_actor, actor_target,
-                    self.steps_actor + 1, "actor")
+        self._apply(NACTOR, actor, self.grad_actor if grad is None else grad, NACTOR + _lib.DDPG_NSTAT, self.m_actor, self.v_actor,
+                    actor_target, self.steps_actor + 1, "actor")
         self.steps_actor += 1
 
     def step(self, flat, obs, action, y):
@@ -462,60 +415,56 @@ class DeviceDDPGLearner:
         s = torch.cat([self.grad_critic[NCRITIC:], self.grad_actor[NACTOR:]]).cpu().tolist()
         return dict(zip(("critic_loss", "mean_q", "actor_loss", "mean_action_sq"), s))
 
-    def state_dict(self):
-        return {"m_critic": self.m_critic.clone(), "v_critic": self.v_critic.clone(), "m_actor": self.m_actor.clone(),
-                "v_actor": self.v_actor.clone(), "steps_critic": self.steps_critic, "steps_actor": self.steps_actor}
 
-    def load_state_dict(self, sd):
-        for k in ("m_critic", "v_critic", "m_actor", "v_actor"):
-            t = getattr(self, k)
-            src = torch.as_tensor(sd[k])
-            if tuple(src.shape) != tuple(t.shape):
-                raise ValueError(f"{k}: expected shape {tuple(t.shape)}, got {tuple(src.shape)}")
-            t.copy_(src.to(device=self.device, dtype=torch.float32))
-        self.steps_critic, self.steps_actor = int(sd["steps_critic"]), int(sd["steps_actor"])
+class _TwinCriticLearner(_OffPolicyLearner):
+    """TD3's and SAC's side of it: two critics in one [2 NCRITIC] vector with one gradient buffer and one Adam, at the widths of
+    `self.arch`.  `_TWIN_GRAD` is the C entry point of the twin critic gradient; the two differ only in the loss's factor."""
+    arch, _TWIN_GRAD = REFERENCE, None
+    _TENSORS = ("m_critics", "v_critics", "m_actor", "v_actor")
+
+    def _twin_buffers(self):
+        n = 2 * self.arch.ncritic
+        self.grad_critics, self.m_critics, self.v_critics, self.steps_critics = self._zeros(n + _lib.TD3_NSTAT), self._zeros(n), self._zeros(n), 0
+
+    def twin_critic_grad(self, critics, obs, action, y, out=None):
+        """-> [2 NCRITIC + 4]: the gradient of c mse(Q1(s, a), y) w.r.t. critic 0, of c mse(Q2(s, a), y) w.r.t. critic 1, then c mse
+        and the mean Q of critic 0 and of critic 1.  c = 1 for TD3, whose loss is mse(Q1, y) + mse(Q2, y); c = 0.5 for SAC, whose loss
+        is SB3's 0.5 (mse(Q1, y) + mse(Q2, y))"""
+        d, f32, m, n = self.device, torch.float32, obs.shape[0], 2 * self.arch.ncritic
+        out = self.grad_critics if out is None else out
+        _need(critics, "critics", f32, (n,), d); _need(obs, "obs", f32, (m, 6), d); _need(action, "action", f32, (m, 2), d)
+        _need(y, "y", f32, (m,), d); _need(out, "grad", f32, (n + _lib.TD3_NSTAT,), d)
+        self._check(getattr(self.L, self._TWIN_GRAD)(self.h, _p(critics), m, _p(obs), _p(action), _p(y), _p(out), self._stream()), self._TWIN_GRAD)
+        return out
+
+    def apply_critics(self, critics, critics_target=None, grad=None):
+        """one Adam step over both critics from grad_critics (or `grad`); with critics_target, also its Polyak update (TD3 passes it
+        on the delayed steps only: the critics do not change between their Adam step and the end of the update)"""
+        n = 2 * self.arch.ncritic
+        self._apply(n, critics, self.grad_critics if grad is None else grad, n + _lib.TD3_NSTAT, self.m_critics, self.v_critics,
+                    critics_target, self.steps_critics + 1, "critics")
+        self.steps_critics += 1
 
 
-class DeviceTD3Learner:
+class DeviceTD3Learner(_TwinCriticLearner):
     """SB3's TD3.train by the HIP kernels, on the reference's DDPG widths (pi=[300, 200], qf=[200, 150]): the gradient of
     mse(Q1(s, a), y) + mse(Q2(s, a), y) w.r.t. both critics in one set of launches (brs_ddpg_learner_twin_critic_grad), one Adam
     over the [2 NCRITIC] vector, and every `policy_delay`-th update the actor's gradient through the first, updated critic, its
     Adam step and the Polyak update of all three targets.  The networks are the caller's flat float32 device tensors (actor
     [NACTOR], critics [2 NCRITIC] and their targets), updated in place; this object owns the twin gradient buffer, the actor's, the
     moment vectors, the step counters and n_updates."""
+    _WHAT, _TWIN_GRAD = "the on-device TD3 learner has", "brs_ddpg_learner_twin_critic_grad"
+    _COUNTERS = ("steps_critics", "steps_actor", "n_updates")
 
     def __init__(self, device=0, max_batch=256, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, tau=0.005, policy_delay=2):
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the on-device TD3 learner has no CPU fallback")
+        self._attach(device)
         if int(policy_delay) < 1:
             raise ValueError(f"policy_delay must be at least 1, got {policy_delay}")
-        self.L = _lib.lib()
-        self.device = _device(device)
-        self.max_batch, self.tau, self.policy_delay = int(max_batch), float(tau), int(policy_delay)
-        self.cfg = _lib.BrsAdamConfig(float(lr), float(betas[0]), float(betas[1]), float(eps))
-        h = C.c_void_p()
-        rc = self.L.brs_ddpg_learner_create_twin(self.device.index, self.max_batch, C.byref(h))
-        if rc != 0:
-            raise BrsError(f"brs_ddpg_learner_create_twin failed ({rc}): {self.L.brs_ddpg_learner_last_error(None).decode()}")
-        self.h = h
-        z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.grad_critics, self.grad_actor = z(2 * NCRITIC + _lib.TD3_NSTAT), z(NACTOR + _lib.DDPG_NSTAT)
-        self.m_critics, self.v_critics, self.m_actor, self.v_actor = z(2 * NCRITIC), z(2 * NCRITIC), z(NACTOR), z(NACTOR)
-        self.steps_critics = self.steps_actor = self.n_updates = 0
-
-    close, __del__, _check, _stream, scratch = (DeviceDDPGLearner.close, DeviceDDPGLearner.__del__, DeviceDDPGLearner._check,
-                                                DeviceDDPGLearner._stream, DeviceDDPGLearner.scratch)
-
-    def twin_critic_grad(self, critics, obs, action, y, out=None):
-        """-> [2 NCRITIC + 4]: the gradient of mse(Q1(s, a), y) w.r.t. critic 0, of mse(Q2(s, a), y) w.r.t. critic 1, then the loss
-        and the mean Q of critic 0 and of critic 1"""
-        d, f32, m = self.device, torch.float32, obs.shape[0]
-        out = self.grad_critics if out is None else out
-        _need(critics, "critics", f32, (2 * NCRITIC,), d); _need(obs, "obs", f32, (m, 6), d); _need(action, "action", f32, (m, 2), d)
-        _need(y, "y", f32, (m,), d); _need(out, "grad", f32, (2 * NCRITIC + _lib.TD3_NSTAT,), d)
-        self._check(self.L.brs_ddpg_learner_twin_critic_grad(self.h, _p(critics), m, _p(obs), _p(action), _p(y), _p(out), self._stream()),
-                    "brs_ddpg_learner_twin_critic_grad")
-        return out
+        self.policy_delay = int(policy_delay)
+        self._create_learner("brs_ddpg_learner_create_twin", max_batch, lr, betas, eps, tau)
+        self._twin_buffers()
+        self.grad_actor, self.m_actor, self.v_actor = self._zeros(NACTOR + _lib.DDPG_NSTAT), self._zeros(NACTOR), self._zeros(NACTOR)
+        self.steps_actor = self.n_updates = 0
 
     def actor_grad(self, actor, critics, obs, out=None):
         """-> [NACTOR + 2]: the gradient of La = -mean Q1(s, pi(s)) through the FIRST critic of `critics` [2 NCRITIC], then La and
@@ -528,25 +477,9 @@ class DeviceTD3Learner:
                     "brs_ddpg_learner_actor_grad")
         return out
 
-    def _apply(self, n, nstat, params, grad, mom, vel, target, step, name):
-        d, f32 = self.device, torch.float32
-        _need(params, name, f32, (n,), d); _need(grad, "grad", f32, (n + nstat,), d)
-        _need(mom, "m_" + name, f32, (n,), d); _need(vel, "v_" + name, f32, (n,), d)
-        if target is not None:
-            _need(target, name + "_target", f32, (n,), d)
-        self._check(self.L.brs_ddpg_learner_apply(self.h, n, _p(params), _p(grad), _p(mom), _p(vel), _p(target), C.byref(self.cfg), step,
-                                                  self.tau, self._stream()), "brs_ddpg_learner_apply")
-
-    def apply_critics(self, critics, critics_target=None, grad=None):
-        """one Adam step over both critics from grad_critics (or `grad`); with critics_target, also its Polyak update (the delayed
-        steps: the critics do not change between their Adam step and the end of the update)"""
-        self._apply(2 * NCRITIC, _lib.TD3_NSTAT, critics, self.grad_critics if grad is None else grad, self.m_critics, self.v_critics,
-                    critics_target, self.steps_critics + 1, "critics")
-        self.steps_critics += 1
-
     def apply_actor(self, actor, actor_target=None, grad=None):
-        self._apply(NACTOR, _lib.DDPG_NSTAT, actor, self.grad_actor if grad is None else grad, self.m_actor, self.v_actor, actor_target,
-                    self.steps_actor + 1, "actor")
+        self._apply(NACTOR, actor, self.grad_actor if grad is None else grad, NACTOR + _lib.DDPG_NSTAT, self.m_actor, self.v_actor,
+                    actor_target, self.steps_actor + 1, "actor")
         self.steps_actor += 1
 
     def step(self, flat, obs, action, y):
@@ -569,145 +502,20 @@ class DeviceTD3Learner:
         c0, q0, c1, q1, la, sq = torch.cat([self.grad_critics[2 * NCRITIC:], self.grad_actor[NACTOR:]]).cpu().tolist()
         return {"critic_loss": c0 + c1, "mean_q1": q0, "mean_q2": q1, "actor_loss": la, "mean_action_sq": sq}
 
-    _TENSORS = ("m_critics", "v_critics", "m_actor", "v_actor")
-    _COUNTERS = ("steps_critics", "steps_actor", "n_updates")
-
-    def state_dict(self):
-        return {**{k: getattr(self, k).clone() for k in self._TENSORS}, **{k: getattr(self, k) for k in self._COUNTERS}}
-
-    def load_state_dict(self, sd):
-        for k in self._TENSORS:
-            t = getattr(self, k)
-            src = torch.as_tensor(sd[k])
-            if tuple(src.shape) != tuple(t.shape):
-                raise ValueError(f"{k}: expected shape {tuple(t.shape)}, got {tuple(src.shape)}")
-            t.copy_(src.to(device=self.device, dtype=torch.float32))
-        for k in self._COUNTERS:
-            setattr(self, k, int(sd[k]))
-
 
 # ------------------------------------------------------------------------------------------------ SAC
-SAC_NACTOR = _lib.SAC_NACTOR
-SAC_GRAD_LEN = SAC_NACTOR + 1 + _lib.SAC_NSTAT
-# the SAC actor VECTOR [SAC_NACTOR + 1]: latent_pi's two layers, the mu and log_std heads stacked into one [4][200] layer, then
-# log_ent_coef.  SB3's SACPolicy (actor.latent_pi.{0,2}, actor.mu, actor.log_std; log_ent_coef is the algorithm's, not the policy's,
-# and is looked up under that name) and tools/train_sac_torch.py (actor.body.{0,2}, actor.mu, actor.log_std, log_ent_coef)
-SAC_ACTOR_NAMINGS = {"sb3": ("actor.latent_pi.0.", "actor.latent_pi.2.", "actor.mu.", "actor.log_std."),
-                     "tool": ("actor.body.0.", "actor.body.2.", "actor.mu.", "actor.log_std.")}
-_SAC_LAYER_SHAPES = (((300, 6), (300,)), ((200, 300), (200,)), ((2, 200), (2,)), ((2, 200), (2,)))
-_SAC256_LAYER_SHAPES = (((256, 6), (256,)), ((256, 256), (256,)), ((2, 256), (2,)), ((2, 256), (2,)))
-SAC256_NACTOR = _lib.SAC256_NACTOR
-_SAC_ACTOR_WIDTHS = ((SAC_NACTOR, _SAC_LAYER_SHAPES), (SAC256_NACTOR, _SAC256_LAYER_SHAPES))
-
-
-class SacArch:
-    """one network architecture of the SAC path (include/brs_policy.h: BRS_ARCH_*): its id and the lengths of its vectors"""
-
-    def __init__(self, name, arch_id, nactor, ncritic):
-        self.name, self.id, self.nactor, self.ncritic = name, arch_id, nactor, ncritic
-        self.grad_len = nactor + 1 + _lib.SAC_NSTAT
-
-
-# net_arch -> architecture: 'reference' is the reference's DDPG widths pi=[300, 200], qf=[200, 150]; 'sb3' is SB3's default
-# [256, 256], what SAC("MlpPolicy", env) builds.  (TD3's default [400, 300] would be a third entry and a third set of kernels.)
-SAC_ARCHS = {"reference": SacArch("reference", _lib.ARCH_REFERENCE, SAC_NACTOR, NCRITIC),
-             "sb3": SacArch("sb3", _lib.ARCH_SAC_DEFAULT, SAC256_NACTOR, NCRITIC256)}
-
-
-def sac_arch(net_arch):
-    if isinstance(net_arch, SacArch):
-        return net_arch
-    if net_arch not in SAC_ARCHS:
-        raise ValueError(f"net_arch must be 'reference' or 'sb3', got {net_arch!r}")
-    return SAC_ARCHS[net_arch]
-
-
-def _sac_naming_of(sd):
-    for naming, prefixes in SAC_ACTOR_NAMINGS.items():
-        if prefixes[0] + "weight" in sd:
-            return naming
-    raise ValueError("neither SB3's SACPolicy naming (actor.latent_pi.0.weight) nor the SAC tool's (actor.body.0.weight)")
-
-
-def flatten_sac_actor(sd):
-    """state_dict in either naming, with a scalar `log_ent_coef` in it -> the flat float32 actor vector [SAC_NACTOR + 1], or
-    [SAC256_NACTOR + 1] for SB3's default [256, 256]: the widths are read off the shapes"""
-    prefixes = SAC_ACTOR_NAMINGS[_sac_naming_of(sd)]
-    layouts = [[(prefix + kind, shape) for prefix, pair in zip(prefixes, shapes) for kind, shape in zip(("weight", "bias"), pair)]
-               for _, shapes in _SAC_ACTOR_WIDTHS]
-    got = {}
-    for name, shape in _widths_of(sd, layouts, "the SAC actor"):
-        a = sd[name]
-        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-        got[name] = a.astype(np.float32)
-    if "log_ent_coef" not in sd:
-        raise ValueError("log_ent_coef: missing")
-    t = sd["log_ent_coef"]
-    t = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
-    if t.size != 1:
-        raise ValueError(f"log_ent_coef: expected one element, got shape {tuple(t.shape)}")
-    p = prefixes
-    flat = np.concatenate([got[p[0] + "weight"].ravel(), got[p[0] + "bias"], got[p[1] + "weight"].ravel(), got[p[1] + "bias"],
-                           got[p[2] + "weight"].ravel(), got[p[3] + "weight"].ravel(), got[p[2] + "bias"], got[p[3] + "bias"],
-                           t.astype(np.float32).ravel()])
-    assert flat.size in (SAC_NACTOR + 1, SAC256_NACTOR + 1)
-    return flat
-
-
-def unflatten_sac_actor(flat, naming="sb3"):
-    """the actor vector [SAC_NACTOR + 1] (or [SAC256_NACTOR + 1]: the widths follow the length) -> {name: tensor} in `naming`
-    ('sb3' or 'tool'), log_ent_coef as a tensor of shape (1,)"""
-    flat = np.ascontiguousarray(flat.detach().cpu().numpy() if hasattr(flat, "detach") else flat, dtype=np.float32)
-    shapes = next((shapes for n, shapes in _SAC_ACTOR_WIDTHS if flat.shape == (n + 1,)), None)
-    if shapes is None:
-        raise ValueError(f"expected {SAC_NACTOR + 1} or {SAC256_NACTOR + 1} elements, got shape {flat.shape}")
-    if naming not in SAC_ACTOR_NAMINGS:
-        raise ValueError(f"naming must be 'sb3' or 'tool', got {naming!r}")
-    p, out, at = SAC_ACTOR_NAMINGS[naming], {}, 0
-
-    def take(shape):
-        nonlocal at
-        k = int(np.prod(shape))
-        t = torch.from_numpy(flat[at:at + k].reshape(shape).copy())
-        at += k
-        return t
-    for prefix, (wshape, bshape) in zip(p[:2], shapes[:2]):
-        out[prefix + "weight"], out[prefix + "bias"] = take(wshape), take(bshape)
-    out[p[2] + "weight"], out[p[3] + "weight"] = take(shapes[2][0]), take(shapes[3][0])
-    out[p[2] + "bias"], out[p[3] + "bias"] = take((2,)), take((2,))
-    out["log_ent_coef"] = take((1,))
-    return out
-
-
 class DeviceSACNets(DeviceDDPGNets):
     """SB3's SACPolicy on the reference's DDPG widths, evaluated by the HIP kernels (brs_sac_act, brs_sac_td_target): the
     squashed-Gaussian actor [SAC_NACTOR + 1] (the last element is log_ent_coef) and the two target critics [2 NCRITIC].  act() has
     DeviceDDPGNets.act's surface, so DeviceOffPolicyCollector drives it unchanged.  net_arch='sb3': SB3's default [256, 256]
     (DESIGN.md 7.12), the vectors then [SAC256_NACTOR + 1] and [2 NCRITIC256]; the DDPG / TD3 calls are refused on such an object."""
+    _WHAT = "the on-device SAC networks have"
 
     def __init__(self, device=0, seed=0, env_index_base=0, net_arch="reference"):
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the on-device SAC networks have no CPU fallback")
+        self._attach(device)
         self.arch = sac_arch(net_arch)
-        self.L = _lib.lib()
-        self.device = _device(device)
-        h = C.c_void_p()
-        rc = self.L.brs_ddpg_create_arch(self.device.index, self.arch.id, C.byref(h))
-        if rc != 0:
-            raise BrsError(f"brs_ddpg_create_arch failed ({rc}): {self.L.brs_ddpg_last_error(None).decode()}")
-        self.h = h
+        self._create("brs_ddpg_create_arch", self.device.index, self.arch.id)
         self.seed, self.env_index_base = int(seed), int(env_index_base)
-
-    def q(self, critic_params, obs, action, out=None):
-        """Q(s, a) of one critic of this architecture: obs [n,6], action [n,2] -> [n]"""
-        d, f32, n = self.device, torch.float32, obs.shape[0]
-        _need(critic_params, "critic_params", f32, (self.arch.ncritic,), d); _need(obs, "obs", f32, (n, 6), d)
-        _need(action, "action", f32, (n, 2), d)
-        if out is None:
-            out = torch.empty(n, dtype=f32, device=d)
-        _need(out, "q", f32, (n,), d)
-        self._check(self.L.brs_ddpg_q(self.h, _p(critic_params), n, _p(obs), _p(action), _p(out), self._stream()), "brs_ddpg_q")
-        return out
 
     def act(self, actor_params, obs, step, sigma=None, random=False, deterministic=False, out=None, mean=None, log_std=None, noise=None):
         """obs [n,6] -> action [n,2] = tanh(mu + exp(clamp(log_std, -20, 2)) z); deterministic: tanh(mu); `random`: the learning_starts
@@ -747,7 +555,7 @@ class DeviceSACNets(DeviceDDPGNets):
         return out
 
 
-class DeviceSACLearner:
+class DeviceSACLearner(_TwinCriticLearner):
     """SB3's SAC.train by the HIP kernels, on the reference's DDPG widths: the gradient of 0.5 (mse(Q1, y) + mse(Q2, y)) w.r.t. both
     critics (brs_sac_twin_critic_grad), one Adam with the Polyak update over the [2 NCRITIC] vector, the actor's gradient through
     both UPDATED critics with the temperature's in the same buffer (brs_sac_actor_grad), and one Adam over the [SAC_NACTOR + 1]
@@ -755,73 +563,34 @@ class DeviceSACLearner:
     caller's flat float32 device tensors, updated in place; this object owns the two gradient buffers, the moment vectors and the
     step counter.  With learn_alpha=False the temperature's gradient is written as 0 and Adam leaves the element as it is.
     net_arch='sb3': SB3's default [256, 256] (DESIGN.md 7.12); every length below is then that architecture's (self.arch)."""
+    _WHAT, _TWIN_GRAD = "the on-device SAC learner has", "brs_sac_twin_critic_grad"
+    _COUNTERS = ("steps_critics", "steps_actor")
 
     def __init__(self, device=0, max_batch=256, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, tau=0.005, target_entropy=-2.0, learn_alpha=True, seed=0,
                  net_arch="reference"):
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the on-device SAC learner has no CPU fallback")
+        self._attach(device)
         self.arch = sac_arch(net_arch)
-        self.L = _lib.lib()
-        self.device = _device(device)
-        self.max_batch, self.tau, self.target_entropy, self.learn_alpha, self.seed = int(max_batch), float(tau), float(target_entropy), bool(learn_alpha), int(seed)
-        self.cfg = _lib.BrsAdamConfig(float(lr), float(betas[0]), float(betas[1]), float(eps))
-        h = C.c_void_p()
-        rc = self.L.brs_ddpg_learner_create_sac_arch(self.device.index, self.max_batch, self.arch.id, C.byref(h))
-        if rc != 0:
-            raise BrsError(f"brs_ddpg_learner_create_sac_arch failed ({rc}): {self.L.brs_ddpg_learner_last_error(None).decode()}")
-        self.h = h
-        NCRITIC, SAC_NACTOR, SAC_GRAD_LEN = self.arch.ncritic, self.arch.nactor, self.arch.grad_len
-        z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.grad_critics, self.grad_actor = z(2 * NCRITIC + _lib.TD3_NSTAT), z(SAC_GRAD_LEN)
-        self.m_critics, self.v_critics, self.m_actor, self.v_actor = z(2 * NCRITIC), z(2 * NCRITIC), z(SAC_NACTOR + 1), z(SAC_NACTOR + 1)
-        self.steps_critics = self.steps_actor = 0
-
-    close, __del__, _check, _stream, scratch = (DeviceDDPGLearner.close, DeviceDDPGLearner.__del__, DeviceDDPGLearner._check,
-                                                DeviceDDPGLearner._stream, DeviceDDPGLearner.scratch)
-
-    def twin_critic_grad(self, critics, obs, action, y, out=None):
-        """-> [2 NCRITIC + 4]: the gradient of 0.5 (mse(Q1(s, a), y) + mse(Q2(s, a), y)) w.r.t. critic 0 and critic 1, then 0.5 mse and
-        the mean Q of critic 0 and of critic 1"""
-        d, f32, m, NCRITIC = self.device, torch.float32, obs.shape[0], self.arch.ncritic
-        out = self.grad_critics if out is None else out
-        _need(critics, "critics", f32, (2 * NCRITIC,), d); _need(obs, "obs", f32, (m, 6), d); _need(action, "action", f32, (m, 2), d)
-        _need(y, "y", f32, (m,), d); _need(out, "grad", f32, (2 * NCRITIC + _lib.TD3_NSTAT,), d)
-        self._check(self.L.brs_sac_twin_critic_grad(self.h, _p(critics), m, _p(obs), _p(action), _p(y), _p(out), self._stream()),
-                    "brs_sac_twin_critic_grad")
-        return out
+        self.target_entropy, self.learn_alpha, self.seed = float(target_entropy), bool(learn_alpha), int(seed)
+        self._create_learner("brs_ddpg_learner_create_sac_arch", max_batch, lr, betas, eps, tau, self.arch.id)
+        self._twin_buffers()
+        n = self.arch.nactor + 1
+        self.grad_actor, self.m_actor, self.v_actor, self.steps_actor = self._zeros(self.arch.grad_len), self._zeros(n), self._zeros(n), 0
 
     def actor_grad(self, actor, critics, obs, draw, out=None):
         """-> [SAC_NACTOR + 1 + 4]: the gradient of La = mean(alpha logp - min(Q1, Q2)(s, a)) in the actor's flat order, the
         temperature's -(mean logp + target_entropy) (0 with learn_alpha=False), then La, mean logp, mean min Q and alpha; `draw`: the
         counter of this call's noise (with the object's seed)"""
-        d, f32, m, NCRITIC, SAC_NACTOR, SAC_GRAD_LEN = self.device, torch.float32, obs.shape[0], self.arch.ncritic, self.arch.nactor, self.arch.grad_len
+        d, f32, m, arch = self.device, torch.float32, obs.shape[0], self.arch
         out = self.grad_actor if out is None else out
-        _need(actor, "actor", f32, (SAC_NACTOR + 1,), d); _need(critics, "critics", f32, (2 * NCRITIC,), d); _need(obs, "obs", f32, (m, 6), d)
-        _need(out, "grad", f32, (SAC_GRAD_LEN,), d)
+        _need(actor, "actor", f32, (arch.nactor + 1,), d); _need(critics, "critics", f32, (2 * arch.ncritic,), d); _need(obs, "obs", f32, (m, 6), d)
+        _need(out, "grad", f32, (arch.grad_len,), d)
         self._check(self.L.brs_sac_actor_grad(self.h, _p(actor), _p(critics), m, _p(obs), self.seed, int(draw) & 0xffffffff, int(self.learn_alpha),
                                               self.target_entropy, _p(out), self._stream()), "brs_sac_actor_grad")
         return out
 
-    def _apply(self, n, params, grad, glen, mom, vel, target, step, name):
-        d, f32 = self.device, torch.float32
-        _need(params, name, f32, (n,), d); _need(grad, "grad", f32, (glen,), d)
-        _need(mom, "m_" + name, f32, (n,), d); _need(vel, "v_" + name, f32, (n,), d)
-        if target is not None:
-            _need(target, name + "_target", f32, (n,), d)
-        self._check(self.L.brs_ddpg_learner_apply(self.h, n, _p(params), _p(grad), _p(mom), _p(vel), _p(target), C.byref(self.cfg), step,
-                                                  self.tau, self._stream()), "brs_ddpg_learner_apply")
-
-    def apply_critics(self, critics, critics_target=None, grad=None):
-        """one Adam step over both critics from grad_critics (or `grad`), then the Polyak update of critics_target"""
-        NCRITIC = self.arch.ncritic
-        self._apply(2 * NCRITIC, critics, self.grad_critics if grad is None else grad, 2 * NCRITIC + _lib.TD3_NSTAT, self.m_critics, self.v_critics,
-                    critics_target, self.steps_critics + 1, "critics")
-        self.steps_critics += 1
-
     def apply_actor(self, actor, grad=None):
         """one Adam step over the actor and log_ent_coef from grad_actor (or `grad`); SAC has no target actor"""
-        SAC_NACTOR, SAC_GRAD_LEN = self.arch.nactor, self.arch.grad_len
-        self._apply(SAC_NACTOR + 1, actor, self.grad_actor if grad is None else grad, SAC_GRAD_LEN, self.m_actor, self.v_actor, None,
+        self._apply(self.arch.nactor + 1, actor, self.grad_actor if grad is None else grad, self.arch.grad_len, self.m_actor, self.v_actor, None,
                     self.steps_actor + 1, "actor")
         self.steps_actor += 1
 
@@ -840,7 +609,3 @@ class DeviceSACLearner:
         c0, q0, c1, q1, ge, la, lp, qm, al = torch.cat([self.grad_critics[2 * self.arch.ncritic:], self.grad_actor[self.arch.nactor:]]).cpu().tolist()
         return {"critic_loss": c0 + c1, "mean_q1": q0, "mean_q2": q1, "actor_loss": la, "mean_logp": lp, "mean_qmin": qm, "ent_coef": al,
                 "ent_coef_grad": ge}
-
-    _TENSORS = ("m_critics", "v_critics", "m_actor", "v_actor")
-    _COUNTERS = ("steps_critics", "steps_actor")
-    state_dict, load_state_dict = DeviceTD3Learner.state_dict, DeviceTD3Learner.load_state_dict

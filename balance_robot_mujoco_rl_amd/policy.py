@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .sim import BrsError
+from ._handle import BrsError, Handle, _need, _numpy, _p  # noqa: F401  (_need and _p are imported from here by tests and tools)
 
 # (name in an SB3 ActorCriticPolicy state_dict, shape) in the order of the flat parameter vector of brs_policy.h
 SB3_LAYOUT = [("mlp_extractor.policy_net.0.weight", (64, 6)), ("mlp_extractor.policy_net.0.bias", (64,)),
@@ -27,8 +27,7 @@ def flatten_sb3_state_dict(sd):
     """SB3 MlpPolicy state_dict (tensors or arrays) -> flat float32 vector in brs_policy.h order"""
     parts = []
     for name, shape in SB3_LAYOUT:
-        a = sd[name]
-        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = _numpy(sd[name])
         if tuple(a.shape) != shape:
             raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
         parts.append(a.astype(np.float32).ravel())
@@ -37,53 +36,15 @@ def flatten_sb3_state_dict(sd):
     return flat
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _need(t, name, dtype, shape, device):
-    """the C ABI takes raw pointers: a sliced, float64 or host tensor would be read as garbage without any error"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
-        raise ValueError(f"{name}: expected a tensor on {device}, got {getattr(t, 'device', type(t))}")
-    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: expected contiguous {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)} "
-                         f"(contiguous: {t.is_contiguous()})")
-    return t
-
-
-class DevicePolicy:
+class DevicePolicy(Handle):
     """SB3's MlpPolicy (6-64-64 tanh actor and critic, state-independent log-std) evaluated by the HIP kernels"""
+    _FAMILY, _WHAT = "brs_policy", "the on-device policy has"
 
     def __init__(self, device=0, seed=0, env_index_base=0):
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the on-device policy has no CPU fallback")
-        self.L = _lib.lib()
-        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
-        h = C.c_void_p()
-        rc = self.L.brs_policy_create(self.device.index, C.byref(h))
-        if rc != 0:
-            raise BrsError(f"brs_policy_create failed ({rc}): {self.L.brs_policy_last_error(None).decode()}")
-        self.h = h
+        self._attach(device)
+        self._create("brs_policy_create", self.device.index)
         self.seed, self.env_index_base = int(seed), int(env_index_base)
         self._dev_params = None
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.brs_policy_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise BrsError(f"{what} failed ({rc}): {self.L.brs_policy_last_error(self.h).decode()}")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def set_weights(self, params):
         """flat float32 vector (host), or an SB3 state_dict"""

@@ -19,8 +19,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .policy import NPARAM, _need, _p, flatten_sb3_state_dict
-from .sim import BrsError
+from ._handle import Handle, _need, _p
+from .nets import ARCH_NAMES, ARCHS
+from .policy import NPARAM, flatten_sb3_state_dict
 
 REFERENCE_CALIBRATION = np.array([[-3.14 / 2, -6.28, -4.0, -4.0, -4.0, -4.0],
                                   [0.0, 0.0, 0.0, 0.0, 0.0, 0.0],
@@ -196,35 +197,14 @@ def quantize_policy(params, calibration_obs=None):
     return QuantModel(input_scale, input_zero, layers)
 
 
-class QuantPolicy:
+class QuantPolicy(Handle):
     """The int8 actor evaluated by the HIP kernel: obs [n, 6] -> action [n, 2], with integer arithmetic only"""
+    _FAMILY, _WHAT = "brs_qpolicy", "the int8 policy has"
 
     def __init__(self, model, device=0):
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the int8 policy has no CPU fallback")
-        self.L = _lib.lib()
-        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
-        h = C.c_void_p()
-        rc = self.L.brs_qpolicy_create(self.device.index, C.byref(h))
-        if rc != 0:
-            raise BrsError(f"brs_qpolicy_create failed ({rc}): {self.L.brs_qpolicy_last_error(None).decode()}")
-        self.h = h
+        self._attach(device)
+        self._create("brs_qpolicy_create", self.device.index)
         self.set_model(model)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.brs_qpolicy_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise BrsError(f"{what} failed ({rc}): {self.L.brs_qpolicy_last_error(self.h).decode()}")
 
     def set_model(self, model):
         """load another QuantModel (synchronous; takes effect on the next act)"""
@@ -243,21 +223,14 @@ class QuantPolicy:
         _need(out, "out", torch.float32, (n, 2), d)
         if out_q is not None:
             _need(out_q, "out_q", torch.int8, (n, 2), d)
-        self._check(self.L.brs_qpolicy_act(self.h, n, _p(obs), _p(out), _p(out_q),
-                                           C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "brs_qpolicy_act")
+        self._check(self.L.brs_qpolicy_act(self.h, n, _p(obs), _p(out), _p(out_q), self._stream()), "brs_qpolicy_act")
         return out
 
 
 # ------------------------------------------------------------------- the off-policy actor, 6 -> 300 -> ReLU -> 200 -> ReLU -> 2 -> tanh
-_ACTOR_SIZES = ((6, 300), (300, 200), (200, 2))
-# net_arch -> the hidden widths the int8 actor kernel is built for, and the architecture id of include/brs_qpolicy.h
-_ACTOR_WIDTHS = {"reference": (300, 200), "sb3": (256, 256)}
-_ACTOR_ARCH_ID = {"reference": _lib.ARCH_REFERENCE, "sb3": _lib.ARCH_SAC_DEFAULT}
-
-
 def _actor_sizes(net_arch):
-    h0, h1 = _ACTOR_WIDTHS[net_arch]
-    return ((6, h0), (h0, h1), (h1, 2))
+    """(in, out) of the three layers the int8 actor kernel of `net_arch` is built for (nets.py's table)"""
+    return ARCHS[net_arch].actor.sizes
 
 
 class QuantActorModel:
@@ -275,7 +248,7 @@ class QuantActorModel:
             raise ValueError(f"expected three layers, got {len(layers)}")
         self.layers = []
         shape0 = np.asarray(layers[0]["W"]).shape
-        self.net_arch = next((name for name, (h0, _) in _ACTOR_WIDTHS.items() if shape0 == (h0, 6)), None)
+        self.net_arch = next((name for name, arch in ARCHS.items() if shape0 == arch.actor.shapes[0][0]), None)
         if self.net_arch is None:
             raise ValueError(f"layer 0: expected weights (300, 6) (net_arch 'reference') or (256, 6) ('sb3'), got {shape0}")
         other = "sb3" if self.net_arch == "reference" else "reference"
@@ -327,7 +300,7 @@ class QuantActorModel:
         for L in self.layers:
             parts += [(L["W"].astype(np.float64) * L["ws"][:, None]).ravel(), L["b"].astype(np.float64) * L["bs"]]
         flat = np.concatenate(parts).astype(np.float32)
-        assert flat.size == sum(n_in * n_out + n_out for n_in, n_out in _actor_sizes(self.net_arch))
+        assert flat.size == ARCHS[self.net_arch].actor.count
         return flat
 
     def c_model(self):
@@ -347,40 +320,35 @@ class QuantActorModel:
         return m, keep
 
 
+# what a SAC actor of another architecture's length is told, by the net_arch that was asked for
+_OTHER_WIDTHS = {"reference": "this is a [256, 256] SAC actor (net_arch='sb3'): with the default net_arch the int8 actor is built at the "
+                              "reference widths pi=[300, 200]; pass net_arch='sb3' to quantize_actor",
+                 "sb3": "this is a SAC actor of the reference widths pi=[300, 200]: pass net_arch='reference'"}
+
+
 def _actor_flat(params, head, net_arch="reference"):
     """-> the fp64 DDPG-layout actor vector of `net_arch`'s widths; with head = "sac" the mu head of a SAC actor (log_std dropped)"""
     from .offpolicy import flatten_ddpg_state_dict, flatten_sac_actor
     if head not in ("ddpg", "sac"):
         raise ValueError(f"head must be 'ddpg' or 'sac', got {head!r}")
-    if net_arch not in _ACTOR_WIDTHS:
-        raise ValueError(f"net_arch must be 'reference' or 'sb3', got {net_arch!r}")
-    h0, h1 = _ACTOR_WIDTHS[net_arch]
-    n01 = h0 * 6 + h0 + h1 * h0 + h1
-    if net_arch == "sb3":
-        if head != "sac":
-            raise ValueError("net_arch='sb3' is SAC's [256, 256] actor: pass head='sac' (SB3 has no DDPG or TD3 at these widths)")
-        flat = flatten_sac_actor(params) if isinstance(params, dict) else np.asarray(params)
-        if flat.size in (_lib.SAC_NACTOR, _lib.SAC_NACTOR + 1):
-            raise ValueError("this is a SAC actor of the reference widths pi=[300, 200]: pass net_arch='reference'")
-        if flat.size not in (_lib.SAC256_NACTOR, _lib.SAC256_NACTOR + 1):
-            raise ValueError(f"expected {_lib.SAC256_NACTOR} (+ 1) parameters, got {flat.size}")
-        flat = flat.astype(np.float64).ravel()
-        # the SAC vector stacks the heads into one [4][256] layer: mu's weights, log_std's weights, mu's bias, log_std's bias
-        return np.concatenate([flat[:n01], flat[n01:n01 + 2 * h1], flat[n01 + 4 * h1:n01 + 4 * h1 + 2]])
+    if net_arch not in ARCHS:
+        raise ValueError(f"net_arch must be {ARCH_NAMES}, got {net_arch!r}")
+    arch = ARCHS[net_arch]
     if head == "ddpg":
+        if net_arch != "reference":
+            raise ValueError("net_arch='sb3' is SAC's [256, 256] actor: pass head='sac' (SB3 has no DDPG or TD3 at these widths)")
         flat = flatten_ddpg_state_dict(params) if isinstance(params, dict) else np.asarray(params)
-        if flat.size != _lib.DDPG_NACTOR:
-            raise ValueError(f"expected {_lib.DDPG_NACTOR} parameters, got {flat.size}")
+        if flat.size != arch.actor.count:
+            raise ValueError(f"expected {arch.actor.count} parameters, got {flat.size}")
         return flat.astype(np.float64).ravel()
     flat = flatten_sac_actor(params) if isinstance(params, dict) else np.asarray(params)
-    if flat.size in (_lib.SAC256_NACTOR, _lib.SAC256_NACTOR + 1):
-        raise ValueError("this is a [256, 256] SAC actor (net_arch='sb3'): with the default net_arch the int8 actor is built at the "
-                         "reference widths pi=[300, 200]; pass net_arch='sb3' to quantize_actor")
-    if flat.size not in (_lib.SAC_NACTOR, _lib.SAC_NACTOR + 1):
-        raise ValueError(f"expected {_lib.SAC_NACTOR} (+ 1) parameters, got {flat.size}")
+    if any(flat.size in (other.nactor, other.nactor + 1) for other in ARCHS.values() if other is not arch):
+        raise ValueError(_OTHER_WIDTHS[net_arch])
+    if flat.size not in (arch.nactor, arch.nactor + 1):
+        raise ValueError(f"expected {arch.nactor} (+ 1) parameters, got {flat.size}")
     flat = flat.astype(np.float64).ravel()
-    # the SAC vector stacks the heads into one [4][200] layer: mu's weights, log_std's weights, mu's bias, log_std's bias
-    return np.concatenate([flat[:n01], flat[n01:n01 + 400], flat[n01 + 800:n01 + 802]])
+    # the SAC vector stacks the heads into one [4][h1] layer: mu's weights, log_std's weights, mu's bias, log_std's bias
+    return np.concatenate([flat[s] for s in arch.sac_mu_slices()])
 
 
 def quantize_actor(params, calibration_obs=None, head="ddpg", net_arch="reference"):
@@ -425,37 +393,16 @@ def quantize_actor(params, calibration_obs=None, head="ddpg", net_arch="referenc
     return QuantActorModel(input_scale, input_zero, layers, 1.0 / 128.0, 0)
 
 
-class QuantActor:
+class QuantActor(Handle):
     """The int8 off-policy actor evaluated by the HIP kernel: obs [n, 6] -> action [n, 2], with integer arithmetic only.  The
     handle is created for the widths of `model` (model.net_arch) and serves models of those widths only."""
+    _FAMILY, _WHAT = "brs_qpolicy_actor", "the int8 actor has"
 
     def __init__(self, model, device=0):
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the int8 actor has no CPU fallback")
-        self.L = _lib.lib()
-        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
-        h = C.c_void_p()
+        self._attach(device)
         self.net_arch = model.net_arch
-        rc = self.L.brs_qpolicy_actor_create_arch(self.device.index, _ACTOR_ARCH_ID[self.net_arch], C.byref(h))
-        if rc != 0:
-            raise BrsError(f"brs_qpolicy_actor_create_arch failed ({rc}): {self.L.brs_qpolicy_actor_last_error(None).decode()}")
-        self.h = h
+        self._create("brs_qpolicy_actor_create_arch", self.device.index, ARCHS[self.net_arch].id)
         self.set_model(model)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.brs_qpolicy_actor_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise BrsError(f"{what} failed ({rc}): {self.L.brs_qpolicy_actor_last_error(self.h).decode()}")
 
     def set_model(self, model):
         """load another QuantActorModel of the handle's widths (synchronous; takes effect on the next act)"""
@@ -474,6 +421,5 @@ class QuantActor:
         _need(out, "out", torch.float32, (n, 2), d)
         if out_q is not None:
             _need(out_q, "out_q", torch.int8, (n, 2), d)
-        self._check(self.L.brs_qpolicy_actor_act(self.h, n, _p(obs), _p(out), _p(out_q),
-                                                 C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "brs_qpolicy_actor_act")
+        self._check(self.L.brs_qpolicy_actor_act(self.h, n, _p(obs), _p(out), _p(out_q), self._stream()), "brs_qpolicy_actor_act")
         return out

@@ -6,30 +6,25 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import BrsError, Handle
 from .registry import spec
-
-
-class BrsError(RuntimeError):
-    pass
 
 
 def _dp(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-class BatchedSim:
+class BatchedSim(Handle):
     """N independent env instances of one variant on one GPU.
 
     step(actions) -> (obs[N,6] f32, reward[N] f32, terminated[N] bool, truncated[N] bool, terminal_obs[N,6] f32),
     all CUDA(=HIP) tensors owned by this object and overwritten by the next call (no allocation per step)."""
+    _FAMILY, _WHAT = "brs", "the batched simulator has"
 
     def __init__(self, env_id, num_envs, device=0, seed=0, env_index_base=0, auto_reset=True, obs_noise=None,
                  max_episode_steps=0, substeps=0, timestep=0.0, block_threads=0, lane_grouping=True):
         self.spec = spec(env_id)
-        if not torch.cuda.is_available():
-            raise BrsError("no HIP device visible to PyTorch: the batched simulator has no CPU fallback")
-        self.L = _lib.lib()
-        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+        self._attach(device)
         flags = _lib.FLAG_AUTO_RESET if auto_reset else 0
         if obs_noise is True:
             flags |= _lib.FLAG_NOISE_ON
@@ -39,11 +34,7 @@ class BatchedSim:
             flags |= _lib.FLAG_NO_LANE_GROUPING
         cfg = _lib.BrsConfig(self.spec.variant, int(num_envs), self.device.index, flags, int(seed), int(env_index_base),
                              int(max_episode_steps), int(substeps), float(timestep), int(block_threads), 0)
-        h = C.c_void_p()
-        rc = self.L.brs_create(C.byref(cfg), C.byref(h))
-        if rc != 0:
-            raise BrsError(f"brs_create failed ({rc}): {self.L.brs_last_error(None).decode()}")
-        self.h = h
+        self._create("brs_create", C.byref(cfg))
         self.n = int(num_envs)
         nq, nv, no, na = (C.c_int32() for _ in range(4))
         self.L.brs_sizes(self.spec.variant, C.byref(nq), C.byref(nv), C.byref(no), C.byref(na))
@@ -60,25 +51,6 @@ class BatchedSim:
         self.terminated = self._packed[52 * n:53 * n]
         self.truncated = self._packed[53 * n:54 * n]
         self._host = None  # pinned staging, allocated on first host-side use
-
-    # ------------------------------------------------------------------ lifecycle
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.brs_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise BrsError(f"{what} failed ({rc}): {self.L.brs_last_error(self.h).decode()}")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ------------------------------------------------------------------ hot path
     def reset(self, mask=None):
