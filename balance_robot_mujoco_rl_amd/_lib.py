@@ -170,6 +170,7 @@ SIGNATURES = {
         "brs_set_aux": (C.c_int, [_vp, _dp]),
         "brs_get_xpose": (C.c_int, [_vp, _dp, _dp]),
         "brs_set_xpose": (C.c_int, [_vp, _dp, _dp]),
+        "brs_get_lane_map": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
         "brs_step_bytes_per_env": (C.c_int64, [_vp]),
         "brs_step_kernel_name": (C.c_char_p, [_vp]),
         "brs_build_id": (C.c_char_p, []),

@@ -933,6 +933,7 @@ template <typename R, bool BLK> struct Sim {
     R cg[3] = {cB[0], cB[1], cB[2] - P.torso_cz};  // block centre relative to the torso geom centre
     R dd2 = dot_(cg, cg), rr0 = P.torso_brad + P.block_brad + c.margin;
     if (dd2 <= rr0 * rr0) {
+      BRS_STAT(stats().cp_torso++);
       BRS_MARK("cc_sat");
       const R sT[3] = {P.torso_sx, P.torso_sy, P.torso_sz};
       R Q[9];
@@ -1320,6 +1321,7 @@ template <typename R, bool BLK> struct Sim {
       R d[3] = {cB[0] - wp[0], cB[1] - wp[1], cB[2] - wp[2]};
       R rr = P.wheel_brad + P.block_brad + c.margin;
       if (dot_(d, d) > rr * rr) { BRS_TOC(11); return; }
+      BRS_STAT(stats().cp_wheel++);
       // candidates within 2 um BEYOND the margin are still tracked: whether the contact exists is then decided below on the
       // distance taken from the fp64 poses (wheel_block_dist_f64), like every other contact-existence test
       const R wband = sizeof(R) == 4 ? (R)2e-6 : (R)0;

@@ -511,6 +511,20 @@ int brs_set_xpose(brs_handle* h, const double* xquat, const double* xpos) {
   return state_roundtrip(h, "brs_set_xpose", true, [&](double* d, float*, int*, size_t N) { h->ops->set_xpose(d, N, xquat, xpos); });
 }
 
+int brs_get_lane_map(brs_handle* h, int32_t* perm, uint8_t* keys, uint32_t* counters, uint32_t* wheel_cap) {
+  if (!h) return BRS_ERR_STATE;
+  if (!h->blk) return fail(h, BRS_ERR_ARG, "brs_get_lane_map: the Env01 family has no lane map");
+  DeviceGuard g(h->device);
+  if (!g.ok) return fail(h, BRS_ERR_HIP, "brs_get_lane_map: hipSetDevice failed");
+  BRS_HIP_TRY(h, hipDeviceSynchronize());
+  const size_t N = (size_t)h->N;
+  if (perm) BRS_HIP_TRY(h, hipMemcpy(perm, h->perm(), N * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (keys) BRS_HIP_TRY(h, hipMemcpy(keys, h->keys(), N * sizeof(uint8_t), hipMemcpyDeviceToHost));
+  if (counters) BRS_HIP_TRY(h, hipMemcpy(counters, h->counters(), (2 * NBUCKET + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (wheel_cap) *wheel_cap = h->wheel_cap;  // the value brs_step passes to brs_group_kernel
+  return BRS_OK;
+}
+
 int64_t brs_step_bytes_per_env(const brs_handle* h) {
   if (!h) return 0;
   // state read + state written + action (8) + obs (24) + terminal obs (24) + reward (4) + two flags (2)

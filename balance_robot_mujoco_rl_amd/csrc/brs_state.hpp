@@ -150,7 +150,9 @@ template <bool BLK, typename FT> BRS_HD bool stored_state_bad(const double* d, c
 // slowest wave: brs_step therefore groups envs of one class into the same waves (a permutation env <-> lane, recomputed
 // after every step from these keys).  Purely a scheduling hint: an env's arithmetic does not depend on its lane, a wrong
 // guess only costs time.  Conservative reach tests: speed x step time + 3 mm.
-template <typename R, bool BLK> BRS_HD int cost_class(const Params<R>& P, const EnvState<R, BLK>& S) {
+// cmp (host test builds only, tests/hostsim: hs_cost_class): both sides of the three comparisons, (lhs, rhs) per bit; the wheel
+// bit's lhs is the nearer wheel's.  The step kernels pass none and the stores fold away.
+template <typename R, bool BLK> BRS_HD int cost_class(const Params<R>& P, const EnvState<R, BLK>& S, R* cmp = nullptr) {
   if constexpr (!BLK) return 0;
   else {
     const R T = (R)P.nsub * P.h, slack = (R)0.003;
@@ -160,7 +162,8 @@ template <typename R, bool BLK> BRS_HD int cost_class(const Params<R>& P, const 
     int key = 0;
     const R low = (R)(S.bp[2] - P.floor_z_d) - P.block_brad - P.cc[CC_BLOCK_FLOOR].margin;
     // only the block's DOWNWARD speed brings it to the floor (its orientation is covered by the bounding radius)
-    key |= low < max_(-S.bv[2], (R)0) * T + (R)0.5 * P.g * T * T + slack ? 1 : 0;
+    const R fall = max_(-S.bv[2], (R)0) * T + (R)0.5 * P.g * T * T + slack;
+    key |= low < fall ? 1 : 0;
     R qf[4] = {(R)S.q[0], (R)S.q[1], (R)S.q[2], (R)S.q[3]}, RT[9];
     quat2mat_(qf, RT);
     const R d[3] = {(R)(S.bp[0] - S.p[0]), (R)(S.bp[1] - S.p[1]), (R)(S.bp[2] - S.p[2])};
@@ -169,11 +172,14 @@ template <typename R, bool BLK> BRS_HD int cost_class(const Params<R>& P, const 
     const R rr = P.wheel_brad + P.block_brad + P.cc[CC_BLOCK_ROBOT].margin + reach;
     const R dz = dl[2] - P.wheel_pz, dxl = dl[0] + P.wheel_px, dxr = dl[0] - P.wheel_px;
     const R base = dl[1] * dl[1] + dz * dz;
-    key |= (base + dxl * dxl < rr * rr || base + dxr * dxr < rr * rr) ? 2 : 0;
+    const R wl = base + dxl * dxl, wr = base + dxr * dxr;  // squared distance to the left / right wheel centre
+    key |= (wl < rr * rr || wr < rr * rr) ? 2 : 0;
     // bit 2: the block cannot reach the torso box either (no block<->robot path at all this step): such lanes are cheap and
     // serve as SEPARATORS between the classes along the lane axis (brs_kernels.hip: brs_group_kernel)
     const R dzt = dl[2] - P.torso_cz, rt = P.torso_brad + P.block_brad + P.cc[CC_BLOCK_ROBOT].margin + reach;
-    key |= (dl[0] * dl[0] + dl[1] * dl[1] + dzt * dzt > rt * rt) ? 4 : 0;
+    const R dt2 = dl[0] * dl[0] + dl[1] * dl[1] + dzt * dzt;
+    key |= (dt2 > rt * rt) ? 4 : 0;
+    if (cmp) { cmp[0] = low; cmp[1] = fall; cmp[2] = min_(wl, wr); cmp[3] = rr * rr; cmp[4] = dt2; cmp[5] = rt * rt; }
     return key;
   }
 }

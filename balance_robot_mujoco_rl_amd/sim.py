@@ -152,6 +152,15 @@ class BatchedSim(Handle):
         xquat, xpos = c(xquat, 4), c(xpos, 3)
         self._check(self.L.brs_set_xpose(self.h, _dp(xquat), _dp(xpos)), "brs_set_xpose")
 
+    def get_lane_map(self):
+        """Env03 family: the lane map brs_step left for the next step (include/brs.h: brs_get_lane_map) -> dict of numpy
+        arrays perm [N] i32 (lane slot -> env), keys [N] u8 (cost class per env), counters [17] u32, wheel_cap (int)"""
+        perm, keys = np.zeros(self.n, np.int32), np.zeros(self.n, np.uint8)
+        counters, cap = np.zeros(17, np.uint32), np.zeros(1, np.uint32)
+        self._check(self.L.brs_get_lane_map(self.h, *(C.c_void_p(a.ctypes.data) for a in (perm, keys, counters, cap))),
+                    "brs_get_lane_map")
+        return dict(perm=perm, keys=keys, counters=counters, wheel_cap=int(cap[0]))
+
     def step_bytes_per_env(self):
         return int(self.L.brs_step_bytes_per_env(self.h))
 

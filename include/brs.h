@@ -108,6 +108,16 @@ int brs_set_aux(brs_handle* h, const double* aux);
 int brs_get_xpose(brs_handle* h, double* xquat, double* xpos);
 int brs_set_xpose(brs_handle* h, const double* xquat, const double* xpos);
 
+/* Env03 family, inspection only (tests, diagnostics): the lane map brs_step left for the NEXT step.  HOST pointers, any may be
+ * NULL; synchronises like brs_get_aux and changes no device state.
+ *   perm      [N]  i32  lane slot -> env
+ *   keys      [N]  u8   cost class (0-7) of every env for its next step
+ *   counters  [17] u32  8 bucket counts, 8 bucket cursors, the ticket (all 0 between steps)
+ *   wheel_cap [1]  u32  wheel lanes per wave the grouping kernel is given: BRS_RARE_CAP while the launch fits one wave per
+ *                       SIMD, 64 above that
+ * Env01 family: BRS_ERR_ARG (there is no lane map). */
+int brs_get_lane_map(brs_handle* h, int32_t* perm, uint8_t* keys, uint32_t* counters, uint32_t* wheel_cap);
+
 /* algorithmic HBM bytes one brs_step moves per env (state in + state out + action + outputs), for rooflines */
 int64_t brs_step_bytes_per_env(const brs_handle* h);
 /* name of the step kernel (for matching rocprof rows) */

@@ -29,6 +29,7 @@ struct IHost {
                          float* obs, float* rew, uint8_t* term, uint8_t* trunc, double* ctrl) = 0;
   virtual void script(int env, const double* u, int n) = 0;
   virtual int script_remaining(int env) const = 0;
+  virtual void cost_class(int* key, double* cmp) const = 0;
 };
 
 template <typename R, bool BLK> struct HostSim : IHost {
@@ -140,6 +141,17 @@ template <typename R, bool BLK> struct HostSim : IHost {
   }
   void script(int env, const double* u, int n) override { scripts[env].assign(u, u + n); spos[env] = 0; }
   int script_remaining(int env) const override { return (int)scripts[env].size() - spos[env]; }
+  // brs_state.hpp: cost_class on the state as it is stored (what the step kernel leaves as the env's key for its next step);
+  // cmp [N][6]: (lhs, rhs) of the floor, wheel and far comparisons
+  void cost_class(int* key, double* cmp) const override {
+    for (size_t i = 0; i < N; i++) {
+      ES S;
+      load_state<R, BLK>(S, d.data(), f.data(), ii.data(), N, i);
+      R c[6] = {0, 0, 0, 0, 0, 0};
+      key[i] = brs::cost_class<R, BLK>(P, S, c);
+      for (int k = 0; k < 6; k++) cmp[6 * i + k] = (double)c[k];
+    }
+  }
 };
 
 extern "C" {
@@ -170,6 +182,7 @@ void hs_step_stub(void* h, int e, const float* a, const double* qp, const double
                   uint8_t* te, uint8_t* tr, double* ctrl) { ((IHost*)h)->step_stub(e, a, qp, qv, xq, xp, o, r, te, tr, ctrl); }
 void hs_script(void* h, int e, const double* u, int n) { ((IHost*)h)->script(e, u, n); }
 int hs_script_remaining(void* h, int e) { return ((IHost*)h)->script_remaining(e); }
+void hs_cost_class(void* h, int* key, double* cmp) { ((IHost*)h)->cost_class(key, cmp); }
 // the kernel source's get_pitch / get_yaw core on one accessor quaternion (float or double instantiation)
 void hs_pitch_yaw(const double* xq, int use_double, double* pitch, double* yaw) {
   if (use_double) { double p, y; Sim<double, false>::pitch_yaw(xq, p, y); *pitch = p; *yaw = y; }

@@ -36,6 +36,7 @@ def lib():
                                hs_script=[vp, C.c_int, dp, C.c_int], hs_step_stub=[vp, C.c_int, fp, dp, dp, dp, dp, fp, fp, u8p, u8p, dp], hs_script_remaining=[vp, C.c_int]).items():
             getattr(L, name).argtypes = args
         L.hs_pitch_yaw.argtypes = [dp, C.c_int, dp, dp]
+        L.hs_cost_class.argtypes = [vp, C.POINTER(C.c_int), dp]
         _lib = L
     return _lib
 
@@ -129,6 +130,13 @@ class HostSim:
 
     def script_remaining(self, env):
         return self.L.hs_script_remaining(self.h, env)
+
+    def cost_class(self):
+        """brs_state.hpp: cost_class of every env's stored state -> keys [N], and [N, 3, 2]: (lhs, rhs) of the floor, wheel
+        and far comparisons"""
+        key = np.zeros(self.n, np.int32); cmp = np.zeros((self.n, 3, 2))
+        self.L.hs_cost_class(self.h, _p(key, C.c_int), _p(cmp, C.c_double))
+        return key, cmp
 
 
 def pitch_yaw(xquat, double=False):

@@ -1,47 +1,19 @@
 """The lane map's slot arithmetic (brs_state.hpp: lane_slot) compiled for the host: it must be a permutation of the lane slots
 for any bucket counts, start every expensive bucket on a wave boundary while there are far lanes to fill the gaps, and fill
 the most expensive buckets first when there are not."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WAVE = 64
+from tests.lane_map_cases import WAVE, compile_lanemap, layout, owner_of
 
 
 def _compile(tmp_path_factory, cap):
-    so = str(tmp_path_factory.mktemp("lanemap") / f"liblanemap{cap}.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-w", f"-DBRS_RARE_CAP={cap}",
-                           "-I" + os.path.join(ROOT, "balance_robot_mujoco_rl_amd", "csrc"), "-o", so,
-                           os.path.join(ROOT, "tests", "lanemap", "lanemap.cpp")])
-    L = C.CDLL(so)
-    L.lm_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]
-    L.lm_slots.restype = None
-    return L
+    return compile_lanemap(tmp_path_factory.mktemp("lanemap"), cap)
 
 
 @pytest.fixture(scope="module", params=[64, 16, 7])
 def lm(request, tmp_path_factory):
     return _compile(tmp_path_factory, request.param)
-
-
-def layout(L, cnt, cap=0):
-    """slot -> bucket for the counts cnt, and the slots of every bucket in rank order (cap 0: the compiled one)"""
-    cnt = np.asarray(cnt, dtype=np.uint32)
-    n = int(cnt.sum())
-    slot = np.zeros(n, dtype=np.uint32)
-    L.lm_slots(cnt.ctypes.data, slot.ctypes.data, cap)
-    assert np.array_equal(np.sort(slot), np.arange(n)), f"not a permutation of the lane slots for counts {cnt.tolist()}"
-    owner = np.empty(n, dtype=np.int64)
-    per, e = [], 0
-    for b, c in enumerate(cnt):
-        per.append(slot[e:e + c].astype(np.int64))
-        owner[slot[e:e + c]] = b
-        e += c
-    return owner, per
 
 
 def expensive_order(L):
@@ -145,3 +117,11 @@ def test_too_few_far_lanes_fills_the_most_expensive_first(lm):
         if cnt[b]:
             assert np.array_equal(np.sort(per[b]), np.arange(pos, pos + cnt[b]))
             pos += cnt[b]
+
+
+def test_owner_of_is_the_layout_at_a_run_time_cap(tmp_path_factory):
+    """lane_map_cases.owner_of (what the GPU tests hold the device map to): the default build at a run-time cap lays the
+    buckets out like a build compiled with that cap"""
+    cnt = np.array([5000, 300, 700, 150, 9000, 900, 3, 60])
+    for cap in (64, 16, 7):
+        assert np.array_equal(owner_of(cnt, cap), layout(_compile(tmp_path_factory, cap), cnt)[0])
