@@ -29,8 +29,10 @@ UNITS = [("brs_kernels.hip", SIM_FLAGS, True), ("brs_policy.hip", [], True), ("b
          ("brs_monitor.hip", [], False), ("brs_learner.hip", [], False), ("brs_offpolicy.hip", [], False),
          ("brs_ddpg_learner.hip", [], False), ("brs_qactor.hip", [], False)]
 SRC = os.path.join(_CSRC, UNITS[0][0])  # the unit that takes the A/B flags and the build id stamp
-# what the build id hashes next to the sources of its units; brs_host.hpp holds no kernel code and stays out of it
-HEADERS = [os.path.join(_CSRC, h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp", "brs_nan.hpp")] + \
+# what the build id hashes next to the sources of its units; brs_host.hpp holds no kernel code and stays out of it.  The policy
+# kernels take their tower tiling from brs_policy_tile.hpp and, through it, the parameter layout from brs_learner.hpp
+HEADERS = [os.path.join(_CSRC, h) for h in ("brs_core.hpp", "brs_model.hpp", "brs_state.hpp", "brs_nan.hpp", "brs_policy_tile.hpp",
+                                            "brs_learner.hpp")] + \
           [os.path.join(_INCLUDE, h) for h in ("brs.h", "brs_policy.h")]
 
 POLICY_NPARAM = (64 * 6 + 64 + 64 * 64 + 64 + 2 * 64 + 2) + (64 * 6 + 64 + 64 * 64 + 64 + 64 + 1) + 2

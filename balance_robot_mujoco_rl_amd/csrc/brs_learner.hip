@@ -4,9 +4,9 @@
 //   learner_adv_kernel     one workgroup of 1,024: mean and unbiased std of the minibatch's advantages, fp64, fixed order.
 //   learner_grad_kernel    a persistent grid of G <= max_workgroups workgroups of 256; workgroup g takes the 256-sample chunks
 //                          g, g + G, ... and writes ONE partial row (gradient sums, stat sums) to the handle's scratch.
-//                          A wave owns 64 samples.  Forward is brs_policy.hip's scheme (fp32 v_mfma_f32_32x32x2_f32, transposed
-//                          product D[unit][sample], padded LDS image of the tower, activations stay in accumulator layout) and
-//                          keeps h1 and h2.  Backward: dz2 = (W3^T dz3) (1 - h2^2) on the vector ALU, dz1 = (W2^T dz2) (1 - h1^2)
+//                          A wave owns 64 samples.  Forward is brs_policy_tile.hpp's tower_forward, the one the rollout kernels
+//                          run (fp32 v_mfma_f32_32x32x2_f32, transposed product D[unit][sample], padded LDS image of the tower,
+//                          activations stay in accumulator layout), with a hook that keeps h1 and h2.  Backward: dz2 = (W3^T dz3) (1 - h2^2) on the vector ALU, dz1 = (W2^T dz2) (1 - h1^2)
 //                          on the matrix cores again -- the SAME LDS image read with the indices swapped gives W2^T as the A operand.
 //                          The weight gradients contract over SAMPLES, and the accumulator layout holds "units of my sample", so
 //                          both operands of dW2 = sum_s dz2 (x) h1 have to be transposed: the four waves take turns to write
@@ -21,6 +21,8 @@
 //   learner_a2c_grad_kernel, learner_rmsprop_apply_kernel   SB3's A2C.train() on the same handle: the gradient kernel
 //                          with -adv log pi in the actor's head and rows 0..m-1 where idx is null; the clip scale, then RMSpropTFLike.
 //                          The value loss keeps critic_head's 0.5 d^2: SB3's vf_coef = 0.5 on mse_loss is vf_coef = 1.0 here.
+// The two gradient kernels are one body, grad_body, over a family (PpoFamily, A2cFamily); the two apply kernels open with the same
+// grad_norms; brs_learner_grad and brs_a2c_grad enqueue through the same launch_grad.
 // Padding: a lane past m (or with an index outside the buffer) feeds zero observations and its dz3 is zero, it is left out of
 // the stats, the advantage statistics and the 1 / m.  No floating-point atomic, no communication between workgroups.
 #include <hip/hip_runtime.h>
@@ -29,110 +31,26 @@
 
 #include "brs_host.hpp"
 #include "brs_learner.hpp"
+#include "brs_policy_tile.hpp"  // the LDS image of a tower, stage_tower, tower_forward, BRS_UNIT
 
 namespace {
 
-using namespace brs::learner;
-static_assert(OBS == 6 && HID == 64 && ACT == 2, "the MFMA tiling below is written for the 6-64-64 MlpPolicy");
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace brs::policy_tile;  // brs::learner's names with it
 
 constexpr int GRAD_THREADS = CHUNK;  // 4 waves x 64 samples
-// LDS image of one tower (floats), as in brs_policy.hip: W2 [64][65], W1 [64][7], b1 [64], b2 [64], W3 [2][64], b3 [2]
-constexpr int W2_LD = 65, W1_LD = 7;
-constexpr int T_W2 = 0, T_W1 = T_W2 + HID * W2_LD, T_B1 = T_W1 + HID * W1_LD, T_B2 = T_B1 + HID, T_W3 = T_B2 + HID, T_B3 = T_W3 + 2 * HID,
-              T_SIZE = T_B3 + 4;
 // transposed images of one wave's 64 samples: P and Q [64 units][TLD], R [8][TLD]: rows 0..5 the observations, 6.. dz3
 constexpr int TLD = 65, PQ_SIZE = HID * TLD, R_ROWS = 8, R_DZ3 = 6, R_SIZE = R_ROWS * TLD;
 constexpr int NACC = ACT + NSTAT + 1;  // per-thread sums carried over the chunks: dlog_std, the stats, bad indices
 static_assert((T_SIZE + 2 * PQ_SIZE + R_SIZE) * sizeof(float) <= 64 * 1024, "static LDS");
 static_assert(GRAD_THREADS * NACC <= PQ_SIZE, "the final tree reuses P");
 
-template <int NOUT> __device__ __forceinline__ void stage_tower(const float* __restrict__ w, float* __restrict__ L) {
-  const float* W1 = w + O_W1;
-  const float* b1 = w + O_B1;
-  const float* W2 = w + O_W2;
-  const float* b2 = w + O_B2;
-  const float* W3 = w + O_W3;
-  const float* b3 = W3 + NOUT * HID;
-  for (int i = threadIdx.x; i < HID * HID; i += GRAD_THREADS) L[T_W2 + (i >> 6) * W2_LD + (i & 63)] = W2[i];
-  for (int i = threadIdx.x; i < HID * OBS; i += GRAD_THREADS) L[T_W1 + (i / OBS) * W1_LD + (i % OBS)] = W1[i];
-  for (int i = threadIdx.x; i < HID; i += GRAD_THREADS) { L[T_B1 + i] = b1[i]; L[T_B2 + i] = b2[i]; }
-  for (int i = threadIdx.x; i < NOUT * HID; i += GRAD_THREADS) L[T_W3 + i] = W3[i];
-  if (threadIdx.x < NOUT) L[T_B3 + threadIdx.x] = b3[threadIdx.x];
-}
-
-__device__ __forceinline__ float fast_tanh(float x) {  // brs_policy.hip's: absolute error ~1e-7
-  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
-  return fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
-}
-
-// unit held by accumulator register r of M-tile mt in half h of the wave
-#define BRS_UNIT(mt, r) (32 * (mt) + 8 * ((r) >> 2) + 4 * h + ((r) & 3))
-
-// Forward of one tower for the wave's 64 samples, keeping the activations.  x[nt][k]: observation k of sample 32 nt + lane % 32
-// (both halves hold the same rows); h1 / h2 [mt][nt][r]: unit BRS_UNIT(mt, r) of that sample; out[nt][k] complete in both halves.
-template <int NOUT>
-__device__ __forceinline__ void tower_forward(const float* __restrict__ L, const float (&x)[2][OBS], f32x16 (&h1)[2][2], f32x16 (&h2)[2][2],
-                                              float (&out)[2][NOUT]) {
-  const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) { const float b = L[T_B1 + BRS_UNIT(mt, r)]; acc[mt][0][r] = b; acc[mt][1][r] = b; }
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float a0 = L[T_W1 + c * W1_LD + 2 * s + h], a1 = L[T_W1 + (32 + c) * W1_LD + 2 * s + h];
-    const float b0 = h ? x[0][2 * s + 1] : x[0][2 * s], b1 = h ? x[1][2 * s + 1] : x[1][2 * s];
-    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-  }
-#pragma unroll
-  for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-    for (int nt = 0; nt < 2; nt++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) h1[mt][nt][r] = fast_tanh(acc[mt][nt][r]);
-#pragma unroll
-  for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) { const float b = L[T_B2 + BRS_UNIT(mt, r)]; acc[mt][0][r] = b; acc[mt][1][r] = b; }
-#pragma unroll
-  for (int mtp = 0; mtp < 2; mtp++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-      const int kin = BRS_UNIT(mtp, r);
-      const float a0 = L[T_W2 + c * W2_LD + kin], a1 = L[T_W2 + (32 + c) * W2_LD + kin];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, h1[mtp][0][r], acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, h1[mtp][1][r], acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, h1[mtp][0][r], acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, h1[mtp][1][r], acc[1][1], 0, 0, 0);
-    }
-  float p[2][NOUT];
-#pragma unroll
-  for (int nt = 0; nt < 2; nt++)
-#pragma unroll
-    for (int k = 0; k < NOUT; k++) p[nt][k] = 0.0f;
-#pragma unroll
-  for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-      const float t0 = fast_tanh(acc[mt][0][r]), t1 = fast_tanh(acc[mt][1][r]);
-      h2[mt][0][r] = t0; h2[mt][1][r] = t1;
-#pragma unroll
-      for (int k = 0; k < NOUT; k++) {
-        const float w3 = L[T_W3 + k * HID + BRS_UNIT(mt, r)];
-        p[0][k] = fmaf(w3, t0, p[0][k]); p[1][k] = fmaf(w3, t1, p[1][k]);
-      }
-    }
-#pragma unroll
-  for (int nt = 0; nt < 2; nt++)
-#pragma unroll
-    for (int k = 0; k < NOUT; k++) out[nt][k] = p[nt][k] + __shfl_xor(p[nt][k], 32, 64) + L[T_B3 + k];
-}
+// tower_forward's hook: the activations of both layers, [mt][nt][r]: unit BRS_UNIT(mt, r) of sample 32 nt + lane % 32
+struct KeepActivations {
+  f32x16 (&a1)[2][2];
+  f32x16 (&a2)[2][2];
+  __device__ __forceinline__ void h1(int mt, int nt, int r, float v) const { a1[mt][nt][r] = v; }
+  __device__ __forceinline__ void h2(int mt, int nt, int r, float v) const { a2[mt][nt][r] = v; }
+};
 
 // dz3[nt][k] (complete in both halves) -> dz2 and dz1 in accumulator layout
 template <int NOUT>
@@ -224,11 +142,11 @@ __device__ __forceinline__ void tower_chunk(const float* __restrict__ w, float* 
                                             float* __restrict__ R, const float (&x)[2][OBS], TowerSums& sums, Head&& head) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, h = lane >> 5;
   __syncthreads();  // the previous tower's image and transposed buffers are no longer read
-  stage_tower<NOUT>(w, Lw);
+  stage_tower<NOUT>(w, Lw, GRAD_THREADS);
   __syncthreads();
   f32x16 h1[2][2], h2[2][2], dz2[2][2], dz1[2][2];
   float out[2][NOUT], own[NOUT], d3own[NOUT], dz3[2][NOUT];
-  tower_forward<NOUT>(Lw, x, h1, h2, out);
+  tower_forward<NOUT>(Lw, x, out, KeepActivations{h1, h2});
 #pragma unroll
   for (int k = 0; k < NOUT; k++) own[k] = h ? out[1][k] : out[0][k];
   head(own, d3own);
@@ -281,14 +199,13 @@ template <int NOUT> __device__ __forceinline__ void store_tower(float* __restric
   else if (tid < 2 * HID + NOUT) row[O_W3 + NOUT * HID + tid - 2 * HID] = a.bias;
   if (tid < NOUT * HID) row[O_W3 + tid] = a.w3;
 }
-#undef BRS_UNIT
 
 __global__ void __launch_bounds__(ADV_THREADS) learner_adv_kernel(const float* __restrict__ adv, const int32_t* __restrict__ idx, const int m,
                                                                   const int n_rows, float* __restrict__ out) {
   __shared__ double S[ADV_THREADS], SS[ADV_THREADS];
   const int t = threadIdx.x;
   double s, ss;
-  fold_adv_rows(adv, idx, m, n_rows, t, s, ss);  // idx null (A2C): the buffer's first m rows
+  fold_adv(adv, idx, m, n_rows, t, s, ss);  // idx null (A2C): the buffer's first m rows
   S[t] = s; SS[t] = ss;
   __syncthreads();
   for (int k = ADV_THREADS / 2; k >= 1; k >>= 1) {
@@ -298,17 +215,42 @@ __global__ void __launch_bounds__(ADV_THREADS) learner_adv_kernel(const float* _
   if (t == 0) adv_mean_denom(S[0], SS[0], m, out);
 }
 
-__global__ void __launch_bounds__(GRAD_THREADS) learner_grad_kernel(const float* __restrict__ w, const int n_rows, const float* __restrict__ obs,
-                                                                    const float* __restrict__ act, const float* __restrict__ logp_old,
-                                                                    const float* __restrict__ adv, const float* __restrict__ ret,
-                                                                    const int32_t* __restrict__ idx, const int m, const brs_ppo_config cfg,
-                                                                    const float* __restrict__ adv_stat, float* __restrict__ partial) {
+// The two families of the gradient kernel: PPO and A2C (7.9: -adv log pi in the actor's head, no logp_old, and the
+// whole buffer in its own order where idx is null).  A family names its config, looks up the row of entry i, calls its actor head
+// and says whether that head feeds the KL and clip-fraction sums.  grad_body takes it by value: it is a pointer at most.
+struct PpoFamily {
+  using Config = brs_ppo_config;
+  static constexpr bool RATIO_STATS = true;
+  const float* __restrict__ logp_old;
+  __device__ __forceinline__ int32_t row(const int32_t* __restrict__ idx, int i) const { return idx[i]; }  // brs_learner_grad refuses a null idx
+  __device__ __forceinline__ ActorHead head(const float (&mean)[ACT], const float (&log_std)[ACT], const float (&a)[ACT], int32_t row,
+                                            float adv_n, const Config& c, float inv_m) const {
+    return actor_head(mean, log_std, a, logp_old[row], adv_n, c, inv_m);
+  }
+};
+struct A2cFamily {
+  using Config = brs_a2c_config;
+  static constexpr bool RATIO_STATS = false;  // the KL and clip-fraction sums stay zero
+  __device__ __forceinline__ int32_t row(const int32_t* __restrict__ idx, int i) const { return row_at(idx, i); }
+  __device__ __forceinline__ ActorHead head(const float (&mean)[ACT], const float (&log_std)[ACT], const float (&a)[ACT], int32_t,
+                                            float adv_n, const Config& c, float inv_m) const {
+    return a2c_actor_head(mean, log_std, a, adv_n, c, inv_m);
+  }
+};
+
+// The gradient kernel of either family: grid, chunks, LDS images, partial row and the final tree are the same.
+template <class Family>
+__device__ __forceinline__ void grad_body(const Family family, const float* __restrict__ w, const int n_rows, const float* __restrict__ obs,
+                                          const float* __restrict__ act, const float* __restrict__ adv, const float* __restrict__ ret,
+                                          const int32_t* __restrict__ idx, const int m, const typename Family::Config& cfg,
+                                          const float* __restrict__ adv_stat, float* __restrict__ partial) {
   __shared__ float Lw[T_SIZE], P[PQ_SIZE], Q[PQ_SIZE], R[R_SIZE];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31;
   const int nchunks = (m + CHUNK - 1) / CHUNK;
   const float inv_m = 1.0f / (float)m;
   const float adv_mean = cfg.normalize_adv ? adv_stat[0] : 0.0f, adv_denom = cfg.normalize_adv ? adv_stat[1] : 1.0f;
   const float log_std[ACT] = {w[OFF_LOGSTD], w[OFF_LOGSTD + 1]};
+  const auto& critic_cfg = shared_fields(cfg);
   TowerSums pi, vf;
   zero(pi); zero(vf);
   float acc[NACC];
@@ -320,28 +262,29 @@ __global__ void __launch_bounds__(GRAD_THREADS) learner_grad_kernel(const float*
 #pragma unroll
     for (int nt = 0; nt < 2; nt++) {
       const int e = base + 32 * nt + c;
-      const int32_t row = e < m ? idx[e] : -1;
+      const int32_t row = e < m ? family.row(idx, e) : -1;
       const bool ok = row >= 0 && row < n_rows;
 #pragma unroll
       for (int k = 0; k < OBS; k++) x[nt][k] = ok ? obs[(size_t)OBS * row + k] : 0.0f;
     }
     const int i = base + lane;
-    const int32_t row = i < m ? idx[i] : -1;
+    const int32_t row = i < m ? family.row(idx, i) : -1;
     const bool valid = row >= 0 && row < n_rows;
     if (i < m && !valid) acc[ACT + NSTAT] += 1.0f;
     tower_chunk<ACT>(w + OFF_PI, Lw, P, Q, R, x, pi, [&](const float (&mean)[ACT], float (&d3)[ACT]) {
       ActorHead hd = zero_actor_head();
       if (valid) {
         const float a[ACT] = {act[(size_t)ACT * row], act[(size_t)ACT * row + 1]};
-        hd = actor_head(mean, log_std, a, logp_old[row], (adv[row] - adv_mean) / adv_denom, cfg, inv_m);
+        hd = family.head(mean, log_std, a, row, (adv[row] - adv_mean) / adv_denom, cfg, inv_m);
       }
       d3[0] = hd.dmean[0]; d3[1] = hd.dmean[1];
       acc[0] += hd.dlog_std[0]; acc[1] += hd.dlog_std[1];
-      acc[ACT + S_PL] += hd.pl; acc[ACT + S_ENT] += hd.ent; acc[ACT + S_KL] += hd.kl; acc[ACT + S_CLIPFRAC] += hd.clipfrac;
+      acc[ACT + S_PL] += hd.pl; acc[ACT + S_ENT] += hd.ent;
+      if constexpr (Family::RATIO_STATS) { acc[ACT + S_KL] += hd.kl; acc[ACT + S_CLIPFRAC] += hd.clipfrac; }
     });
     tower_chunk<1>(w + OFF_VF, Lw, P, Q, R, x, vf, [&](const float (&v)[1], float (&d3)[1]) {
       CriticHead hd = {0.0f, 0.0f};
-      if (valid) hd = critic_head(v[0], ret[row], cfg, inv_m);
+      if (valid) hd = critic_head(v[0], ret[row], critic_cfg, inv_m);
       d3[0] = hd.dvalue;
       acc[ACT + S_VL] += hd.vl;
     });
@@ -363,71 +306,20 @@ __global__ void __launch_bounds__(GRAD_THREADS) learner_grad_kernel(const float*
   if (tid < NACC) row_out[OFF_LOGSTD + tid] = P[tid * GRAD_THREADS];  // log_std[2], then the stats and the bad-index count: ROW's order
 }
 
-// A2C: learner_grad_kernel with a2c_actor_head in the actor's lambda -- no logp_old -- and the rows taken through
-// row_at (idx null: the whole buffer in its own order).  Grid, chunks, LDS images, partial row and the final tree are the same.
+__global__ void __launch_bounds__(GRAD_THREADS) learner_grad_kernel(const float* __restrict__ w, const int n_rows, const float* __restrict__ obs,
+                                                                    const float* __restrict__ act, const float* __restrict__ logp_old,
+                                                                    const float* __restrict__ adv, const float* __restrict__ ret,
+                                                                    const int32_t* __restrict__ idx, const int m, const brs_ppo_config cfg,
+                                                                    const float* __restrict__ adv_stat, float* __restrict__ partial) {
+  grad_body(PpoFamily{logp_old}, w, n_rows, obs, act, adv, ret, idx, m, cfg, adv_stat, partial);
+}
+
 __global__ void __launch_bounds__(GRAD_THREADS) learner_a2c_grad_kernel(const float* __restrict__ w, const int n_rows, const float* __restrict__ obs,
                                                                         const float* __restrict__ act, const float* __restrict__ adv,
                                                                         const float* __restrict__ ret, const int32_t* __restrict__ idx, const int m,
                                                                         const brs_a2c_config cfg, const float* __restrict__ adv_stat,
                                                                         float* __restrict__ partial) {
-  __shared__ float Lw[T_SIZE], P[PQ_SIZE], Q[PQ_SIZE], R[R_SIZE];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31;
-  const int nchunks = (m + CHUNK - 1) / CHUNK;
-  const float inv_m = 1.0f / (float)m;
-  const float adv_mean = cfg.normalize_adv ? adv_stat[0] : 0.0f, adv_denom = cfg.normalize_adv ? adv_stat[1] : 1.0f;
-  const float log_std[ACT] = {w[OFF_LOGSTD], w[OFF_LOGSTD + 1]};
-  const brs_ppo_config critic_cfg = shared_fields(cfg);
-  TowerSums pi, vf;
-  zero(pi); zero(vf);
-  float acc[NACC];
-#pragma unroll
-  for (int k = 0; k < NACC; k++) acc[k] = 0.0f;
-  for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {  // uniform over the workgroup
-    const int base = chunk * CHUNK + wave * 64;
-    float x[2][OBS];
-#pragma unroll
-    for (int nt = 0; nt < 2; nt++) {
-      const int e = base + 32 * nt + c;
-      const int32_t row = e < m ? row_at(idx, e) : -1;
-      const bool ok = row >= 0 && row < n_rows;
-#pragma unroll
-      for (int k = 0; k < OBS; k++) x[nt][k] = ok ? obs[(size_t)OBS * row + k] : 0.0f;
-    }
-    const int i = base + lane;
-    const int32_t row = i < m ? row_at(idx, i) : -1;
-    const bool valid = row >= 0 && row < n_rows;
-    if (i < m && !valid) acc[ACT + NSTAT] += 1.0f;
-    tower_chunk<ACT>(w + OFF_PI, Lw, P, Q, R, x, pi, [&](const float (&mean)[ACT], float (&d3)[ACT]) {
-      ActorHead hd = zero_actor_head();
-      if (valid) {
-        const float a[ACT] = {act[(size_t)ACT * row], act[(size_t)ACT * row + 1]};
-        hd = a2c_actor_head(mean, log_std, a, (adv[row] - adv_mean) / adv_denom, cfg, inv_m);
-      }
-      d3[0] = hd.dmean[0]; d3[1] = hd.dmean[1];
-      acc[0] += hd.dlog_std[0]; acc[1] += hd.dlog_std[1];
-      acc[ACT + S_PL] += hd.pl; acc[ACT + S_ENT] += hd.ent;  // the KL and clip-fraction sums stay zero
-    });
-    tower_chunk<1>(w + OFF_VF, Lw, P, Q, R, x, vf, [&](const float (&v)[1], float (&d3)[1]) {
-      CriticHead hd = {0.0f, 0.0f};
-      if (valid) hd = critic_head(v[0], ret[row], critic_cfg, inv_m);
-      d3[0] = hd.dvalue;
-      acc[ACT + S_VL] += hd.vl;
-    });
-  }
-  float* row_out = partial + (size_t)blockIdx.x * ROW;
-  store_tower<ACT>(row_out + OFF_PI, pi);
-  store_tower<1>(row_out + OFF_VF, vf);
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NACC; k++) P[k * GRAD_THREADS + tid] = acc[k];
-  __syncthreads();
-  for (int s = GRAD_THREADS / 2; s >= 1; s >>= 1) {
-    if (tid < s)
-#pragma unroll
-      for (int k = 0; k < NACC; k++) P[k * GRAD_THREADS + tid] += P[k * GRAD_THREADS + tid + s];
-    __syncthreads();
-  }
-  if (tid < NACC) row_out[OFF_LOGSTD + tid] = P[tid * GRAD_THREADS];
+  grad_body(A2cFamily{}, w, n_rows, obs, act, adv, ret, idx, m, cfg, adv_stat, partial);
 }
 
 __global__ void __launch_bounds__(256) learner_reduce_kernel(const float* __restrict__ partial, const int G, float* __restrict__ grad,
@@ -439,13 +331,11 @@ __global__ void __launch_bounds__(256) learner_reduce_kernel(const float* __rest
   else info->bad_index = (int32_t)s;
 }
 
-__global__ void __launch_bounds__(APPLY_THREADS) learner_apply_kernel(float* __restrict__ params, const float* __restrict__ grad,
-                                                                      float* __restrict__ m, float* __restrict__ v, const brs_ppo_config cfg,
-                                                                      brs_learner_info* __restrict__ info) {
+// The opening of both apply kernels: the two squared norms of grad (fold + tree of fixed pairing, fp64) -> the norms under the
+// config's clip mode, in every thread.  Called by all APPLY_THREADS threads of the one workgroup (barriers inside).
+__device__ __forceinline__ void grad_norms(const float* __restrict__ grad, const brs_ppo_config& clip_cfg, float& norm_pi, float& norm_vf) {
   __shared__ double SP[APPLY_THREADS], SV[APPLY_THREADS];
   const int t = threadIdx.x;
-  const int32_t was_stopped = info->stopped;  // read by everybody before thread 0 writes (the barriers below lie in between)
-  const int64_t steps = info->steps;
   double sp, sv;
   fold_squares(grad, t, sp, sv);
   SP[t] = sp; SV[t] = sv;
@@ -454,8 +344,17 @@ __global__ void __launch_bounds__(APPLY_THREADS) learner_apply_kernel(float* __r
     if (t < k) { SP[t] += SP[t + k]; SV[t] += SV[t + k]; }
     __syncthreads();
   }
+  norms(SP[0], SV[0], clip_cfg, norm_pi, norm_vf);
+}
+
+__global__ void __launch_bounds__(APPLY_THREADS) learner_apply_kernel(float* __restrict__ params, const float* __restrict__ grad,
+                                                                      float* __restrict__ m, float* __restrict__ v, const brs_ppo_config cfg,
+                                                                      brs_learner_info* __restrict__ info) {
+  const int t = threadIdx.x;
+  const int32_t was_stopped = info->stopped;  // read by everybody before thread 0 writes (grad_norms' barriers lie in between)
+  const int64_t steps = info->steps;
   float norm_pi, norm_vf;
-  norms(SP[0], SV[0], cfg, norm_pi, norm_vf);
+  grad_norms(grad, cfg, norm_pi, norm_vf);
   const bool stop = was_stopped || kl_stops(grad[NPARAM + S_KL], cfg);
   if (t == 0) {
     info->stopped = stop ? 1 : 0;
@@ -476,19 +375,10 @@ __global__ void __launch_bounds__(APPLY_THREADS) learner_apply_kernel(float* __r
 __global__ void __launch_bounds__(APPLY_THREADS) learner_rmsprop_apply_kernel(float* __restrict__ params, const float* __restrict__ grad,
                                                                               float* __restrict__ sq, const brs_a2c_config cfg,
                                                                               brs_learner_info* __restrict__ info) {
-  __shared__ double SP[APPLY_THREADS], SV[APPLY_THREADS];
   const int t = threadIdx.x;
-  double sp, sv;
-  fold_squares(grad, t, sp, sv);
-  SP[t] = sp; SV[t] = sv;
-  __syncthreads();
-  for (int k = APPLY_THREADS / 2; k >= 1; k >>= 1) {
-    if (t < k) { SP[t] += SP[t + k]; SV[t] += SV[t + k]; }
-    __syncthreads();
-  }
   const brs_ppo_config clip_cfg = shared_fields(cfg);
   float norm_pi, norm_vf;
-  norms(SP[0], SV[0], clip_cfg, norm_pi, norm_vf);
+  grad_norms(grad, clip_cfg, norm_pi, norm_vf);
   if (t == 0) {
     info->steps = info->steps + 1;
     for (int k = 0; k < NSTAT; k++) info->stat[k] = grad[NPARAM + k];
@@ -514,6 +404,19 @@ struct brs_learner {
 };
 
 using brs::host::DeviceGuard, brs::host::fail;
+
+// What brs_learner_grad and brs_a2c_grad enqueue on `s` once their arguments are checked and the device is set: the advantage
+// statistics where asked for, the family's gradient kernel on G workgroups (`launch_grad_kernel(G, s)`), the reduce kernel.
+template <class Launch>
+static int launch_grad(brs_learner* l, int32_t normalize_adv, int32_t n_rows, const float* adv_dev, const int32_t* idx_dev, int32_t m,
+                       float* grad_dev, hipStream_t s, Launch&& launch_grad_kernel) {
+  const int nchunks = (m + CHUNK - 1) / CHUNK, G = nchunks < l->max_workgroups ? nchunks : l->max_workgroups;
+  if (normalize_adv) hipLaunchKernelGGL(learner_adv_kernel, dim3(1), dim3(ADV_THREADS), 0, s, adv_dev, idx_dev, m, n_rows, l->adv_stat);
+  launch_grad_kernel(G, s);
+  hipLaunchKernelGGL(learner_reduce_kernel, dim3((ROW + 255) / 256), dim3(256), 0, s, l->partial, G, grad_dev, l->info);
+  BRS_HIP_TRY(l, hipGetLastError());
+  return BRS_OK;
+}
 
 extern "C" {
 
@@ -576,14 +479,10 @@ int brs_learner_grad(brs_learner* l, const float* params_dev, int32_t n_rows, co
   if (!(cfg->ret_scale > 0.0f)) return fail(l, BRS_ERR_ARG, "brs_learner_grad: ret_scale must be positive");
   DeviceGuard g(l->device);
   if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_learner_grad: hipSetDevice failed");
-  hipStream_t s = (hipStream_t)stream;
-  const int nchunks = (m + CHUNK - 1) / CHUNK, G = nchunks < l->max_workgroups ? nchunks : l->max_workgroups;
-  if (cfg->normalize_adv) hipLaunchKernelGGL(learner_adv_kernel, dim3(1), dim3(ADV_THREADS), 0, s, adv_dev, idx_dev, m, n_rows, l->adv_stat);
-  hipLaunchKernelGGL(learner_grad_kernel, dim3(G), dim3(GRAD_THREADS), 0, s, params_dev, n_rows, obs_dev, act_dev, logp_old_dev, adv_dev,
-                     ret_dev, idx_dev, m, *cfg, l->adv_stat, l->partial);
-  hipLaunchKernelGGL(learner_reduce_kernel, dim3((ROW + 255) / 256), dim3(256), 0, s, l->partial, G, grad_dev, l->info);
-  BRS_HIP_TRY(l, hipGetLastError());
-  return BRS_OK;
+  return launch_grad(l, cfg->normalize_adv, n_rows, adv_dev, idx_dev, m, grad_dev, (hipStream_t)stream, [&](int G, hipStream_t s) {
+    hipLaunchKernelGGL(learner_grad_kernel, dim3(G), dim3(GRAD_THREADS), 0, s, params_dev, n_rows, obs_dev, act_dev, logp_old_dev, adv_dev,
+                       ret_dev, idx_dev, m, *cfg, l->adv_stat, l->partial);
+  });
 }
 
 int brs_learner_apply(brs_learner* l, float* params_dev, const float* grad_dev, float* m_dev, float* v_dev, const brs_ppo_config* cfg,
@@ -610,14 +509,10 @@ int brs_a2c_grad(brs_learner* l, const float* params_dev, int32_t n_rows, const 
     return fail(l, BRS_ERR_ARG, "brs_a2c_grad: bad argument");
   DeviceGuard g(l->device);
   if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_a2c_grad: hipSetDevice failed");
-  hipStream_t s = (hipStream_t)stream;
-  const int nchunks = (m + CHUNK - 1) / CHUNK, G = nchunks < l->max_workgroups ? nchunks : l->max_workgroups;
-  if (cfg->normalize_adv) hipLaunchKernelGGL(learner_adv_kernel, dim3(1), dim3(ADV_THREADS), 0, s, adv_dev, idx_dev, m, n_rows, l->adv_stat);
-  hipLaunchKernelGGL(learner_a2c_grad_kernel, dim3(G), dim3(GRAD_THREADS), 0, s, params_dev, n_rows, obs_dev, act_dev, adv_dev, ret_dev, idx_dev,
-                     m, *cfg, l->adv_stat, l->partial);
-  hipLaunchKernelGGL(learner_reduce_kernel, dim3((ROW + 255) / 256), dim3(256), 0, s, l->partial, G, grad_dev, l->info);
-  BRS_HIP_TRY(l, hipGetLastError());
-  return BRS_OK;
+  return launch_grad(l, cfg->normalize_adv, n_rows, adv_dev, idx_dev, m, grad_dev, (hipStream_t)stream, [&](int G, hipStream_t s) {
+    hipLaunchKernelGGL(learner_a2c_grad_kernel, dim3(G), dim3(GRAD_THREADS), 0, s, params_dev, n_rows, obs_dev, act_dev, adv_dev, ret_dev, idx_dev,
+                       m, *cfg, l->adv_stat, l->partial);
+  });
 }
 
 int brs_a2c_apply(brs_learner* l, float* params_dev, const float* grad_dev, float* sq_dev, const brs_a2c_config* cfg, void* stream) {

@@ -1,7 +1,8 @@
 // brs_learner.hpp -- the PPO learner of include/brs_policy.h and the A2C learner on the same handle (7.9), the part shared by the HIP kernels
 // (brs_learner.hip) and the host build the CPU tests hold against fp64 torch autograd (tests/learnerhost): everything that is
 // not a matrix product -- the per-sample loss heads, the order in which partial sums are combined, the clip scale and the Adam
-// update.  The towers themselves are MFMA code in the kernels and plain loops in the host build.
+// update.  The towers themselves are MFMA code in the kernels (brs_policy_tile.hpp, which takes the layout of the flat parameter
+// vector from the constants below, as brs_policy.hip does through it) and plain loops in the host build.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -39,36 +40,62 @@ struct ActorHead {
   float pl, ent, kl, clipfrac;
 };
 
-// adv_n: the (normalised) advantage.  loss = -min(ratio adv, clamp(ratio) adv) - ent_coef entropy
-BRS_HD ActorHead actor_head(const float mean[ACT], const float log_std[ACT], const float act[ACT], float logp_old, float adv_n,
-                            const brs_ppo_config& c, float inv_m) {
-  ActorHead o;
-  float z[ACT], inv_sigma[ACT], lp = 0.0f, ent = 0.0f;
+// what both actor heads start from: the standardised action, log pi(a | s) and the entropy of the diagonal Gaussian
+struct GaussianTerms {
+  float z[ACT], inv_sigma[ACT], lp, ent;
+};
+BRS_HD GaussianTerms gaussian_terms(const float mean[ACT], const float log_std[ACT], const float act[ACT]) {
+  GaussianTerms t;
+  t.lp = 0.0f; t.ent = 0.0f;
   for (int k = 0; k < ACT; k++) {
-    inv_sigma[k] = expf(-log_std[k]);
-    z[k] = (act[k] - mean[k]) * inv_sigma[k];
-    lp += -0.5f * z[k] * z[k] - log_std[k] - 0.9189385332046727f;
-    ent += 1.4189385332046727f + log_std[k];  // 0.5 + 0.5 log(2 pi) + log sigma
+    t.inv_sigma[k] = expf(-log_std[k]);
+    t.z[k] = (act[k] - mean[k]) * t.inv_sigma[k];
+    t.lp += -0.5f * t.z[k] * t.z[k] - log_std[k] - 0.9189385332046727f;
+    t.ent += 1.4189385332046727f + log_std[k];  // 0.5 + 0.5 log(2 pi) + log sigma
   }
-  const float lr = lp - logp_old, ratio = expf(lr);
-  const float clamped = fminf(fmaxf(ratio, 1.0f - c.clip_range), 1.0f + c.clip_range);  // of a NaN ratio: a number; s1 keeps the NaN
-  const float s1 = ratio * adv_n, s2 = clamped * adv_n;
-  o.pl = -min_keep_nan(s1, s2) * inv_m;
-  o.ent = ent * inv_m;
-  o.kl = ((ratio - 1.0f) - lr) * inv_m;
-  o.clipfrac = fabsf(ratio - 1.0f) > c.clip_range ? inv_m : 0.0f;
-  // the clamped branch has no gradient where the clamp is active, and where it is not the two branches are the same function;
-  // a NaN on either side leaves the gate open, so that the row's NaN reaches the gradient as it reaches torch.min's
-  const float g_lp = (c.actor_on && !(s1 > s2)) ? -adv_n * ratio * inv_m : 0.0f;
+  return t;
+}
+// z^2 - 1.  The device build has always contracted it to one fma -- but only because the SLP vectoriser happened to keep the square
+// and the difference of the two actions in one packed chain; with the accumulators of the gradient kernel paired another way the
+// square is rounded first and the log_std gradient moves in its last bit.  Written out so that the kernels do not depend on that.
+// The host build is compiled without contraction and rounds the square, as it always has
+BRS_HD float square_minus_one(float z) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return fmaf(z, z, -1.0f);
+#else
+  return z * z - 1.0f;
+#endif
+}
+// ... and end with: dmean and dlog_std from g_lp = d loss / d log pi (zero with the actor off)
+template <class Config>  // anything with actor_on and ent_coef
+BRS_HD void actor_head_gradients(ActorHead& o, const GaussianTerms& t, float g_lp, const Config& c, float inv_m) {
   for (int k = 0; k < ACT; k++) {
     if (c.actor_on) {
-      o.dmean[k] = g_lp * z[k] * inv_sigma[k];
-      o.dlog_std[k] = g_lp * (z[k] * z[k] - 1.0f) - c.ent_coef * inv_m;
+      o.dmean[k] = g_lp * t.z[k] * t.inv_sigma[k];
+      o.dlog_std[k] = g_lp * square_minus_one(t.z[k]) - c.ent_coef * inv_m;
     } else {
       o.dmean[k] = 0.0f;
       o.dlog_std[k] = 0.0f;
     }
   }
+}
+
+// adv_n: the (normalised) advantage.  loss = -min(ratio adv, clamp(ratio) adv) - ent_coef entropy
+BRS_HD ActorHead actor_head(const float mean[ACT], const float log_std[ACT], const float act[ACT], float logp_old, float adv_n,
+                            const brs_ppo_config& c, float inv_m) {
+  ActorHead o;
+  const GaussianTerms t = gaussian_terms(mean, log_std, act);
+  const float lr = t.lp - logp_old, ratio = expf(lr);
+  const float clamped = fminf(fmaxf(ratio, 1.0f - c.clip_range), 1.0f + c.clip_range);  // of a NaN ratio: a number; s1 keeps the NaN
+  const float s1 = ratio * adv_n, s2 = clamped * adv_n;
+  o.pl = -min_keep_nan(s1, s2) * inv_m;
+  o.ent = t.ent * inv_m;
+  o.kl = ((ratio - 1.0f) - lr) * inv_m;
+  o.clipfrac = fabsf(ratio - 1.0f) > c.clip_range ? inv_m : 0.0f;
+  // the clamped branch has no gradient where the clamp is active, and where it is not the two branches are the same function;
+  // a NaN on either side leaves the gate open, so that the row's NaN reaches the gradient as it reaches torch.min's
+  const float g_lp = (c.actor_on && !(s1 > s2)) ? -adv_n * ratio * inv_m : 0.0f;
+  actor_head_gradients(o, t, g_lp, c, inv_m);
   return o;
 }
 
@@ -89,54 +116,33 @@ template <class Config>  // brs_a2c_config: anything with actor_on and ent_coef
 BRS_HD ActorHead a2c_actor_head(const float mean[ACT], const float log_std[ACT], const float act[ACT], float adv_n, const Config& c,
                                 float inv_m) {
   ActorHead o;
-  float z[ACT], inv_sigma[ACT], lp = 0.0f, ent = 0.0f;
-  for (int k = 0; k < ACT; k++) {
-    inv_sigma[k] = expf(-log_std[k]);
-    z[k] = (act[k] - mean[k]) * inv_sigma[k];
-    lp += -0.5f * z[k] * z[k] - log_std[k] - 0.9189385332046727f;
-    ent += 1.4189385332046727f + log_std[k];
-  }
-  o.pl = -adv_n * lp * inv_m;
-  o.ent = ent * inv_m;
+  const GaussianTerms t = gaussian_terms(mean, log_std, act);
+  o.pl = -adv_n * t.lp * inv_m;
+  o.ent = t.ent * inv_m;
   o.kl = 0.0f;
   o.clipfrac = 0.0f;
   const float g_lp = c.actor_on ? -adv_n * inv_m : 0.0f;
-  for (int k = 0; k < ACT; k++) {
-    if (c.actor_on) {
-      o.dmean[k] = g_lp * z[k] * inv_sigma[k];
-      o.dlog_std[k] = g_lp * (z[k] * z[k] - 1.0f) - c.ent_coef * inv_m;
-    } else {
-      o.dmean[k] = 0.0f;
-      o.dlog_std[k] = 0.0f;
-    }
-  }
+  actor_head_gradients(o, t, g_lp, c, inv_m);
   return o;
 }
-// what critic_head, norms and param_scale read of a config, for brs_a2c_config's callers
+// what critic_head, norms and param_scale read of a config, for brs_a2c_config's callers; a brs_ppo_config is its own
 BRS_HD brs_ppo_config shared_fields(const brs_a2c_config& c) {
   brs_ppo_config p = {};
   p.vf_coef = c.vf_coef; p.ent_coef = c.ent_coef; p.max_grad_norm_pi = c.max_grad_norm_pi; p.max_grad_norm_vf = c.max_grad_norm_vf;
   p.ret_scale = c.ret_scale; p.normalize_adv = c.normalize_adv; p.actor_on = c.actor_on; p.joint_norm = c.joint_norm;
   return p;
 }
+BRS_HD const brs_ppo_config& shared_fields(const brs_ppo_config& c) { return c; }
 
 BRS_HD ActorHead zero_actor_head() { return ActorHead{{0.0f, 0.0f}, {0.0f, 0.0f}, 0.0f, 0.0f, 0.0f, 0.0f}; }
+
+// ---- entry i of a minibatch: row idx[i], or row i of the buffer when the minibatch is the whole buffer in its own order (idx
+// null: A2C alone, brs_learner_grad refuses it)
+BRS_HD int32_t row_at(const int32_t* idx, int i) { return idx ? idx[i] : (int32_t)i; }
 
 // ---- advantage mean and std of the minibatch: thread t of ADV_THREADS folds entries t, t + ADV_THREADS, ... in ascending
 // order into (sum, sum of squares) in fp64, the partials are combined by a tree of fixed pairing (tree_pairs below)
 BRS_HD void fold_adv(const float* adv, const int32_t* idx, int m, int n_rows, int t, double& s, double& ss) {
-  s = 0.0; ss = 0.0;
-  for (int i = t; i < m; i += ADV_THREADS) {
-    const int32_t row = idx[i];
-    if (row < 0 || row >= n_rows) continue;
-    const double a = (double)adv[row];
-    s += a; ss += a * a;
-  }
-}
-// entry i of a minibatch: row idx[i], or row i of the buffer when the minibatch is the whole buffer in its own order (idx null)
-BRS_HD int32_t row_at(const int32_t* idx, int i) { return idx ? idx[i] : (int32_t)i; }
-// fold_adv with the rows taken through row_at: the same sums in the same order where idx is not null
-BRS_HD void fold_adv_rows(const float* adv, const int32_t* idx, int m, int n_rows, int t, double& s, double& ss) {
   s = 0.0; ss = 0.0;
   for (int i = t; i < m; i += ADV_THREADS) {
     const int32_t row = row_at(idx, i);
@@ -144,6 +150,10 @@ BRS_HD void fold_adv_rows(const float* adv, const int32_t* idx, int m, int n_row
     const double a = (double)adv[row];
     s += a; ss += a * a;
   }
+}
+// the name the fold through row_at had while there were two; host builds written against that header still compile
+BRS_HD void fold_adv_rows(const float* adv, const int32_t* idx, int m, int n_rows, int t, double& s, double& ss) {
+  fold_adv(adv, idx, m, n_rows, t, s, ss);
 }
 // -> out[0] = mean, out[1] = unbiased std + 1e-8: adv_n = (adv - out[0]) / out[1]
 BRS_HD void adv_mean_denom(double s, double ss, int m, float* out) {

@@ -1,20 +1,12 @@
 // brs_policy.hip -- on-device rollout side of the path (include/brs_policy.h): SB3 MlpPolicy
 // actor/critic forward + diagonal-Gaussian sample, time-limit bootstrap, GAE(lambda), as HIP kernels for gfx950.
 //
-// The 6-64-64 towers are the one dense contraction of the repository (2 x 64 x 64 MACs per env and layer) and run on the
-// MATRIX cores in fp32: v_mfma_f32_32x32x2_f32, exact fp32 products and accumulation (the parity test compares with fp32
-// torch at rtol 1e-5).  Mapping: a wave owns 64 envs = two N-tiles of 32; the 64 units of a layer are two M-tiles; the
-// product is computed TRANSPOSED, D[unit][env] = sum_k W[unit][k] act[k][env], so that
-//   * the A operand is a weight (lane l: W[32 mt + l%32][k(l/32)]), read from a padded LDS copy of the tower (row stride 65 /
-//     7 words: the 32 lanes of a half hit 32 different banks), staged once per 256-env workgroup;
-//   * the B operand is an activation of env l%32 -- and the accumulator layout of this instruction (lane l holds rows
-//     8 (r/4) + 4 (l/32) + r%4 of column l%32) is exactly "16 units of MY env per M-tile": after the tanh the output
-//     registers of one layer ARE the B operands of the next (the K index is walked in accumulator order, the weights are
-//     fetched to match), so activations never leave their registers: no LDS round trip, no shuffle between the layers.
-// The 2- and 1-unit output layers are 32 FMAs per lane plus one cross-half shuffle.  tanh = 1 - 2 / (2^(2 x log2 e) + 1) on
-// v_exp_f32 / v_rcp_f32 (absolute error ~1e-7).  Round 2's kernel walked the towers lane by lane with the weights as scalar
-// operands (2,097 s_load per wave, latency-bound): 115 us per policy step at 65,536 envs = 2.5 % of the env step it feeds
-// (profiles/r03_rollout_kernel_stats_before_mfma.json); this one: profiles/r03_rollout_kernel_stats.json.
+// The 6-64-64 towers run on the matrix cores in fp32 (v_mfma_f32_32x32x2_f32; the parity test compares with fp32 torch at rtol
+// 1e-5): the tiling -- a wave owns 64 envs, the product is computed transposed, the weights sit in a padded LDS image staged once
+// per 256-env workgroup, activations stay in accumulator layout from one layer to the next -- is brs_policy_tile.hpp's, shared
+// with the learners of brs_learner.hip; this file holds the kernels around it.  Round 2's kernel walked the towers lane by lane
+// with the weights as scalar operands (2,097 s_load per wave, latency-bound): 115 us per policy step at 65,536 envs = 2.5 % of the
+// env step it feeds (profiles/r03_rollout_kernel_stats_before_mfma.json); this one: profiles/r03_rollout_kernel_stats.json.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -22,111 +14,14 @@
 #include "../../include/brs.h"
 #include "../../include/brs_policy.h"
 #include "brs_host.hpp"
-#include "brs_core.hpp"  // philox4x32_10 (same generator as the simulator)
-#include "brs_nan.hpp"   // clip_keep_nan
+#include "brs_core.hpp"         // philox4x32_10 (same generator as the simulator)
+#include "brs_nan.hpp"          // clip_keep_nan
+#include "brs_policy_tile.hpp"  // stage_tower, tower_forward, the LDS image of a tower
 
 namespace {
 
-constexpr int OBS = BRS_POLICY_OBS, HID = BRS_POLICY_HID, ACT = BRS_POLICY_ACT;
-constexpr int OFF_PI = 0, OFF_VF = BRS_POLICY_NPI, OFF_LOGSTD = BRS_POLICY_NPI + BRS_POLICY_NVF;
-static_assert(OBS == 6 && HID == 64, "the MFMA tiling below is written for the 6-64-64 MlpPolicy");
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// LDS image of one tower (floats): W2 [64][65], W1 [64][7], b1 [64], b2 [64], W3 [2][64], b3 [2]
-constexpr int W2_LD = 65, W1_LD = 7;
-constexpr int T_W2 = 0, T_W1 = T_W2 + HID * W2_LD, T_B1 = T_W1 + HID * W1_LD, T_B2 = T_B1 + HID, T_W3 = T_B2 + HID, T_B3 = T_W3 + 2 * HID,
-              T_SIZE = T_B3 + 4;
+using namespace brs::policy_tile;
 constexpr int POLICY_THREADS = 256;  // 4 waves x 64 envs share one staged copy of the weights
-
-// global parameter vector of a tower (W1[64][6] b1[64] W2[64][64] b2[64] W3[NOUT][64] b3[NOUT]) -> its LDS image; all threads
-template <int NOUT> __device__ __forceinline__ void stage_tower(const float* __restrict__ w, float* __restrict__ L) {
-  const float* W1 = w;
-  const float* b1 = W1 + HID * OBS;
-  const float* W2 = b1 + HID;
-  const float* b2 = W2 + HID * HID;
-  const float* W3 = b2 + HID;
-  const float* b3 = W3 + NOUT * HID;
-  for (int i = threadIdx.x; i < HID * HID; i += blockDim.x) L[T_W2 + (i >> 6) * W2_LD + (i & 63)] = W2[i];
-  for (int i = threadIdx.x; i < HID * OBS; i += blockDim.x) L[T_W1 + (i / OBS) * W1_LD + (i % OBS)] = W1[i];
-  for (int i = threadIdx.x; i < HID; i += blockDim.x) { L[T_B1 + i] = b1[i]; L[T_B2 + i] = b2[i]; }
-  for (int i = threadIdx.x; i < NOUT * HID; i += blockDim.x) L[T_W3 + i] = W3[i];
-  if (threadIdx.x < NOUT) L[T_B3 + threadIdx.x] = b3[threadIdx.x];
-}
-
-__device__ __forceinline__ float fast_tanh(float x) {
-  // 1 - 2 / (e^(2x) + 1): e = +inf -> 1, e = 0 -> -1; v_exp_f32 and v_rcp_f32 are 1-ulp instructions
-  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
-  return fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
-}
-
-// One tower for the 64 envs of this wave.  x[nt][k]: observation k of env (32 nt + lane % 32) of the wave (both halves of
-// the wave hold the same rows); out[nt][k]: output unit k for that env, complete in both halves.
-template <int NOUT> __device__ __forceinline__ void tower_mfma(const float* __restrict__ L, const float (&x)[2][OBS], float (&out)[2][NOUT]) {
-  const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
-  // unit held by accumulator register r of M-tile mt in this half of the wave: 32 mt + 8 (r / 4) + 4 h + r % 4
-#define BRS_UNIT(mt, r) (32 * (mt) + 8 * ((r) >> 2) + 4 * h + ((r) & 3))
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) { const float b = L[T_B1 + BRS_UNIT(mt, r)]; acc[mt][0][r] = b; acc[mt][1][r] = b; }
-  // layer 1: K = 6 = three steps of two; this half supplies feature 2 s + h
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float a0 = L[T_W1 + c * W1_LD + 2 * s + h], a1 = L[T_W1 + (32 + c) * W1_LD + 2 * s + h];
-    const float b0 = h ? x[0][2 * s + 1] : x[0][2 * s], b1 = h ? x[1][2 * s + 1] : x[1][2 * s];
-    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-  }
-  f32x16 h1[2][2];
-#pragma unroll
-  for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-    for (int nt = 0; nt < 2; nt++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) h1[mt][nt][r] = fast_tanh(acc[mt][nt][r]);
-  // layer 2: K = 64 walked in ACCUMULATOR order: step (mtp, r) contracts the two units BRS_UNIT(mtp, r) of the two halves
-#pragma unroll
-  for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) { const float b = L[T_B2 + BRS_UNIT(mt, r)]; acc[mt][0][r] = b; acc[mt][1][r] = b; }
-#pragma unroll
-  for (int mtp = 0; mtp < 2; mtp++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-      const int kin = BRS_UNIT(mtp, r);
-      const float a0 = L[T_W2 + c * W2_LD + kin], a1 = L[T_W2 + (32 + c) * W2_LD + kin];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, h1[mtp][0][r], acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, h1[mtp][1][r], acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, h1[mtp][0][r], acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, h1[mtp][1][r], acc[1][1], 0, 0, 0);
-    }
-  // output layer on the vector ALU: this half's 32 units of each env, then the other half's partial sum
-  float p[2][NOUT];
-#pragma unroll
-  for (int nt = 0; nt < 2; nt++)
-#pragma unroll
-    for (int k = 0; k < NOUT; k++) p[nt][k] = 0.0f;
-#pragma unroll
-  for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-      const float t0 = fast_tanh(acc[mt][0][r]), t1 = fast_tanh(acc[mt][1][r]);
-#pragma unroll
-      for (int k = 0; k < NOUT; k++) {
-        const float w3 = L[T_W3 + k * HID + BRS_UNIT(mt, r)];
-        p[0][k] = fmaf(w3, t0, p[0][k]); p[1][k] = fmaf(w3, t1, p[1][k]);
-      }
-    }
-#undef BRS_UNIT
-#pragma unroll
-  for (int nt = 0; nt < 2; nt++)
-#pragma unroll
-    for (int k = 0; k < NOUT; k++) out[nt][k] = p[nt][k] + __shfl_xor(p[nt][k], 32, 64) + L[T_B3 + k];
-}
 
 // observations of the two envs (32 nt + lane % 32) this lane feeds into the matrix cores; rows beyond n read as zero
 __device__ __forceinline__ void load_obs_tiles(const float* __restrict__ obs, int n, int wave_base, float (&x)[2][OBS]) {
@@ -145,14 +40,14 @@ __global__ void __launch_bounds__(POLICY_THREADS) policy_act_kernel(const float*
                                                                     float* __restrict__ action_clipped, float* __restrict__ logp,
                                                                     float* __restrict__ value, float* __restrict__ noise) {
   __shared__ float Lpi[T_SIZE], Lvf[T_SIZE];
-  stage_tower<ACT>(w + OFF_PI, Lpi);
-  stage_tower<1>(w + OFF_VF, Lvf);
+  stage_tower<ACT>(w + OFF_PI, Lpi, blockDim.x);
+  stage_tower<1>(w + OFF_VF, Lvf, blockDim.x);
   __syncthreads();
   const int wave_base = blockIdx.x * blockDim.x + (threadIdx.x & ~63), h = (threadIdx.x >> 5) & 1;
   float x[2][OBS], m2[2][ACT], v2[2][1];
   load_obs_tiles(obs, n, wave_base, x);
-  tower_mfma<ACT>(Lpi, x, m2);   // (no lane leaves before the matrix instructions: they need the whole wave)
-  tower_mfma<1>(Lvf, x, v2);
+  tower_forward<ACT>(Lpi, x, m2);   // (no lane leaves before the matrix instructions: they need the whole wave)
+  tower_forward<1>(Lvf, x, v2);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;  // lane l finishes env l of the wave: N-tile h, column l % 32
   if (i >= n) return;
   const float mean[ACT] = {h ? m2[1][0] : m2[0][0], h ? m2[1][1] : m2[0][1]};
@@ -187,12 +82,12 @@ __global__ void __launch_bounds__(POLICY_THREADS) policy_act_kernel(const float*
 __global__ void __launch_bounds__(POLICY_THREADS) policy_value_kernel(const float* __restrict__ w, const int n, const float* __restrict__ obs,
                                                                       float* __restrict__ value) {
   __shared__ float Lvf[T_SIZE];
-  stage_tower<1>(w + OFF_VF, Lvf);
+  stage_tower<1>(w + OFF_VF, Lvf, blockDim.x);
   __syncthreads();
   const int wave_base = blockIdx.x * blockDim.x + (threadIdx.x & ~63), h = (threadIdx.x >> 5) & 1;
   float x[2][OBS], v2[2][1];
   load_obs_tiles(obs, n, wave_base, x);
-  tower_mfma<1>(Lvf, x, v2);
+  tower_forward<1>(Lvf, x, v2);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) value[i] = h ? v2[1][0] : v2[0][0];
 }
@@ -204,12 +99,12 @@ __global__ void __launch_bounds__(POLICY_THREADS) bootstrap_kernel(const float* 
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool need = i < n && trunc[i] && !term[i];
   if (!__syncthreads_or(need)) return;  // a workgroup without a truncated episode leaves at once (the common case)
-  stage_tower<1>(w + OFF_VF, Lvf);
+  stage_tower<1>(w + OFF_VF, Lvf, blockDim.x);
   __syncthreads();
   const int wave_base = blockIdx.x * blockDim.x + (threadIdx.x & ~63), h = (threadIdx.x >> 5) & 1;
   float x[2][OBS], v2[2][1];
   load_obs_tiles(tobs, n, wave_base, x);
-  tower_mfma<1>(Lvf, x, v2);
+  tower_forward<1>(Lvf, x, v2);
   if (need) reward[i] = fmaf(gamma, h ? v2[1][0] : v2[0][0], reward[i]);
 }
 
