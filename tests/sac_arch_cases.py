@@ -125,6 +125,9 @@ def weights(kind):
 C.S, C.R, C.RL, C.NA, C.NC, C.HOST_DIR, C.weights = S, R, RL, NA, NC, HOST_DIR, weights
 C.TC = types.SimpleNamespace(_critic_pre=_critic_pre)
 C._LAYERS = np.cumsum([0, 256, 256, 256, 256, 256, 256])
+# sac_cases.HOST_ROWS_MAX at these widths: one sh_actor_grad / one sh_twin_critic_grad of this host build takes 1.8 s / 1.3 s at 2,049
+# rows and 6.6 s / 5.1 s at 8,193 on a CPU, over the 5 s a comparison may cost: the host build is compared up to 2,049 rows
+C.HOST_ROWS_MAX = 2049
 
 
 # ------------------------------------------------------------------------------------------------ the host build

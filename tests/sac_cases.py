@@ -13,7 +13,11 @@ Conditions of a gradient case, all checked on the fp64 yardstick alone, offendin
 of ddpg_learner_cases: for the actor on obs and both critics on (obs, a(obs)) 25 % to 75 % of every hidden layer active, no
 pre-activation within MARGIN[kind] of 0, fp32 torch's pre-activations within a tenth of that; |Q0 - Q1| >= MARGIN; the raw log_std at
 least MARGIN from -20 and from 2; and no cancellation behind the b3 gradient (|sum t| >= 1/4 sum |t| for the four columns of
-d La / d (actor output)) nor behind the temperature's (the same for logp + target_entropy)."""
+d La / d (actor output)) nor behind the temperature's (the same for logp + target_entropy).
+
+The sample split: the rows, the handle of 8,448 and the sequence are ddpg_learner_cases' (SPLIT_*); which weight set goes to which row,
+the bound of the comparison with the host build, the allocation's arithmetic (partial_storage) and the case with the last row alone
+replaced (changed_last_row) are here, for both widths (tests/sac_arch_cases.py executes this source a second time)."""
 import ctypes as C
 import os
 import subprocess
@@ -26,8 +30,9 @@ import ref_offpolicy as R
 import ref_sac as S
 import td3_cases as TC
 from balance_robot_mujoco_rl_amd import _lib
-from ddpg_learner_cases import GRAD_GATE, _draw, _no_cancellation, block_distances
-from offpolicy_cases import GAMMA, GXX, ROOT, SEED, _active_ok, conditioned
+from ddpg_learner_cases import (GRAD_GATE, SPLIT_BIG, SPLIT_LAST_REAL, SPLIT_ROWS, SPLIT_SEQUENCE, SPLIT_TABLE, SPLIT_X3_ROWS, _draw, _no_cancellation,
+                                block_distances)
+from offpolicy_cases import GAMMA, GATE, GXX, ROOT, SEED, _active_ok, conditioned
 
 HOST_DIR = os.path.join(ROOT, "tests", "sachost")
 NA, NC = S.NACTOR, S.NCRITIC
@@ -41,7 +46,20 @@ ACT_ROWS_CPU = (1, 33, 257)
 GRAD_ROWS_CPU = (1, 33, 257, 1000)
 GPU_ROWS = (1, 31, 32, 33, 127, 128, 129, 257, 1000)
 ACT_ROWS_GPU = (1, 31, 32, 33, 127, 128, 129, 257)
-SPLIT_ROWS = (513, 2049)                   # two split geometries: two uneven partial rows; six, the last shorter
+# The sample-split geometries (ddpg_learner_cases.SPLIT_TABLE: 385 to 8,193 rows, two to eight partial rows) as the SAC calls are taken
+# through them.  `spread` -- the clamped log_std branches -- at 769 (the last split is ONE real row and 127 padding rows) and at 2,049
+# (six splits, the last the short one); at 8,193 its [256, 256] case takes 7 s to condition, so it stops there.
+SPLIT_SPREAD_ROWS = (769, 2049)
+SPLIT_ACTOR_CASES = [(n, "init") for n in SPLIT_ROWS] + [(n, "x3") for n in SPLIT_X3_ROWS] + [(n, "spread") for n in SPLIT_SPREAD_ROWS]
+SPLIT_TWIN_CASES = [(n, "init") for n in SPLIT_ROWS] + [(n, "x3") for n in SPLIT_X3_ROWS]
+SPLIT_STAT_ROWS = (769, 8193)              # the statistics alone: a lone real row in the last of three splits; eight splits, uneven
+MAX_SPLIT = max(nsplit for _, _, nsplit in SPLIT_TABLE.values())
+assert MAX_SPLIT == 8 and SPLIT_LAST_REAL[769] == 1 and set(SPLIT_SPREAD_ROWS) | set(SPLIT_STAT_ROWS) <= set(SPLIT_ROWS)
+# The host build's plain loops are compared at every split row where ONE host gradient takes under 5 s on a CPU.  Measured, one
+# sh_actor_grad / one sh_twin_critic_grad: 1.2 s / 0.6 s at 2,049 rows, 4.7 s / 2.4 s at 8,193 -- every row of SPLIT_ROWS.  (At
+# [256, 256], tests/sac_arch_cases.py: 1.8 s / 1.3 s and 6.6 s / 5.1 s, so the bound there is 2,049.)
+HOST_ROWS_MAX = 8193
+SAC_TAIL = 1 + S.NSTAT                   # what follows the actor's parameters in a row: the temperature's gradient, then the statistics
 SAC_ADAM = dict(lr=3e-4, betas=(0.9, 0.999), eps=1e-8, tau=0.005)
 CHAIN_STEPS, CHAIN_ROWS = 6, 200
 _LAYERS = np.cumsum([0, 300, 200, 200, 150, 200, 150])
@@ -159,6 +177,79 @@ def check_actor_gradient(what, g, g64, g32, stat_gate):
     stat_gate(g[NA + 1:], g64[NA + 1:], what + " statistics")
     assert max(mine.values()) <= GRAD_GATE, (what, mine, t32)
     return max(mine.values()), max(t32.values())
+
+
+_TWIN_REFS = {}
+
+
+def twin_reference(n, kind):
+    """the fp64 twin critic gradient [2 NC + 4] of grad_case(n, kind); computed once"""
+    if (n, kind) not in _TWIN_REFS:
+        c = grad_case(n, kind)
+        _TWIN_REFS[(n, kind)] = S.twin_critic_grad(c["critics"], c["obs"], c["act"], c["y"])
+    return _TWIN_REFS[(n, kind)]
+
+
+# ------------------------------------------------------------------------------------------------ the sample split
+def partial_storage(make):
+    """make(max_batch) -> a learner handle.  -> (scratch rows, floats the handle keeps for partial rows), from the sizes of two
+    allocations and nothing else: a handle's bytes are 4 (rows pad128(max_batch) + partial), so handles of 256 and of 128 rows
+    differ by rows x 128 floats, and what the 128-row handle holds beyond rows x 128 floats is the partial storage.  Launches nothing."""
+    sizes = []
+    for max_batch in (128, 256):
+        lrn = make(max_batch)
+        sizes.append(lrn.scratch()[1])
+        lrn.close()
+    step = sizes[1] - sizes[0]
+    assert step > 0 and step % (4 * 128) == 0 and sizes[0] % 4 == 0, sizes
+    rows = step // (4 * 128)
+    return rows, sizes[0] // 4 - rows * 128
+
+
+def assert_partial_rows_fit(make, longest_row, what):
+    """MAX_SPLIT partial rows of the longest row a call on the handle writes fit what the handle keeps for them (the SAC counterpart
+    of bit 5 of ddpglearnerhost's dh_split_sweep); -> (scratch rows, partial floats)"""
+    rows, partial = partial_storage(make)
+    print(f"{what}: {rows} scratch rows, {partial} floats of partial storage = {partial / longest_row:.4f} rows of {longest_row} floats")
+    assert rows > 0 and partial >= MAX_SPLIT * longest_row, (what, rows, partial, longest_row)
+    return rows, partial
+
+
+def moved(new, old):
+    """|new - old| / max(1, |old|), element by element: the measure of offpolicy_cases.gate"""
+    new, old = np.asarray(new, np.float64), np.asarray(old, np.float64)
+    return np.abs(new - old) / np.maximum(1.0, np.abs(old))
+
+
+ROW_SUMS = 4   # of the SAC_TAIL sums behind the actor's parameters the first four depend on the rows; the fifth, ent_coef, is alpha / m from every row
+_CHANGED = {}
+
+
+def changed_last_row(n, kind="init"):
+    """grad_case(n, kind) with row n - 1 ALONE replaced (another observation, twice as far out, another action, y + 4), and the fp64
+    actor and twin critic gradients of that.  The replacement is drawn until, on the fp64 reference, each of the four row-dependent
+    tail sums and each of the twin call's four statistics has moved by more than 2 GATE in gate's measure: two results that are each
+    within GATE of their reference then cannot be equal.  The changed row is held to no gradient condition: only the statistics of
+    this case are compared.  -> (case, actor64, twin64); computed once"""
+    if (n, kind) in _CHANGED:
+        return _CHANGED[(n, kind)]
+    c = grad_case(n, kind)
+    a64, t64 = references(n, kind)[0], twin_reference(n, kind)
+    rng = np.random.default_rng(9000 + n)
+    for _ in range(50):
+        obs, act, y = c["obs"].copy(), c["act"].copy(), c["y"].copy()
+        o, a = _draw(rng, 1)
+        obs[n - 1], act[n - 1], y[n - 1] = np.float32(2.0) * o[0], a[0], c["y"][n - 1] + np.float32(4.0)
+        b64 = S.actor_grad(c["actor"], c["critics"], obs, SEED, c["draw"], True, TARGET_ENTROPY)
+        u64 = S.twin_critic_grad(c["critics"], obs, act, y)
+        shift = np.concatenate([moved(b64[NA:NA + ROW_SUMS], a64[NA:NA + ROW_SUMS]), moved(u64[2 * NC:], t64[2 * NC:])])
+        if shift.min() > 2 * GATE:
+            break
+    else:
+        raise AssertionError("no replacement of the last row moves every sum")
+    assert np.array_equal(obs[:n - 1], c["obs"][:n - 1]) and np.array_equal(act[:n - 1], c["act"][:n - 1]) and np.array_equal(y[:n - 1], c["y"][:n - 1])
+    _CHANGED[(n, kind)] = ({**c, "obs": obs, "act": act, "y": y}, b64, u64)
+    return _CHANGED[(n, kind)]
 
 
 # ------------------------------------------------------------------------------------------------ act and target cases

@@ -10,10 +10,21 @@ Largest distances reached on an MI355X, next to each gate (fp32 torch on the sam
     logp' 4.2e-6, action 3.1e-6, z 2.8e-6, mu 1.8e-6; against the host build: log_std 6.2e-6, logp' 3.4e-6, y 3.3e-6, a' 2.5e-6, mu 1.7e-6,
     z 2.2e-7; brs_ddpg_q on the [256, 256] critic 3.4e-6 (host build 2.8e-6)
   actor gradient blocks against fp64, gate 1e-5: init 2.5e-7 [fp32 torch 4.0e-7], x3 1.2e-6 [5.4e-3], spread 5.0e-6 [3.3e-1]; against the
-    host build 1.6e-6; statistics 3.5e-7 (host build 8.1e-7); the split geometries 1.5e-7 (513 rows) and 9.0e-8 (2,049)
+    host build 1.6e-6; statistics 3.5e-7 (host build 8.1e-7)
   twin critic gradient blocks against fp64 3.4e-6, against the host build 2.8e-6
   the width-edge models (unit 255 / unit 0 alone behind either hidden layer): critic blocks 4.4e-7, actor blocks 3.8e-7
-  six chained steps: every block at 1.0x fp32 torch's floored distance, kernels and host build (gate 4x)."""
+  six chained steps: every block at 1.0x fp32 torch's floored distance, kernels and host build (gate 4x).
+
+The sample split (ddpg_learner_cases.SPLIT_TABLE; the allocation's arithmetic is asserted first, launching nothing: 2,056 scratch rows
+and 8.0000 partial rows of 136,710 floats).  Largest block distance from fp64 per row, on a fresh handle of max_batch == m and on the
+NaN-filled one of 8,448 rows (identical bytes), gate 1e-5:
+  actor gradient, init: 385 1.3e-7, 513 1.5e-7, 769 1.4e-7, 1,025 1.1e-7, 2,049 9.0e-8, 8,192 1.1e-7, 8,193 1.2e-7 [fp32 torch up to
+    9.9e-7]; x3: 513 2.7e-7, 2,049 1.1e-7, 8,193 1.5e-7 [2.2e-3]; spread: 769 6.5e-7, 2,049 2.5e-7 [6.4e-2]; against the host build (up
+    to 2,049 rows: HOST_ROWS_MAX of sac_arch_cases) 4.0e-7; statistics 1.4e-7
+  twin critic gradient, both critics, init: 385 1.2e-7, 513 1.5e-7, 769 1.4e-7, 1,025 1.1e-7, 2,049 8.5e-8, 8,192 1.2e-7, 8,193 1.3e-7;
+    x3: 513 3.9e-7, 2,049 2.3e-7, 8,193 1.7e-7; against the host build 7.2e-7 (513 x3); statistics 1.2e-7
+  the five tail sums / the twin call's four statistics under `gate`: 769 rows 3.5e-8 / 1.3e-8, 8,193 rows 6.6e-8 / 7.5e-9; with row 768
+    of 769 replaced (the sums move by 9.7e-5 to 2.4e-4, the twin statistics by 2.3e-4 to 1.3e-2) 2.8e-8 / 2.2e-8."""
 import os
 import sys
 
@@ -58,6 +69,18 @@ def big():
     lrn = _sac(1024)
     yield lrn
     lrn.close()
+
+
+# --------------------------------------------------------------------------------------- 0. the allocation, launching nothing
+def _assert_partial_rows_fit():
+    rows, _ = SC.assert_partial_rows_fit(_sac, max(NA + SC.SAC_TAIL, TLEN), "[256, 256] SAC handle")
+    assert rows >= 2 * 512 + 4 + 1 + S.NSTAT   # two critic images side by side, and the actor's
+
+
+def test_eight_partial_rows_fit_the_allocation():
+    """first in the file: the arithmetic of the handle's one allocation is known before any launch with eight workgroup rows"""
+    assert SC.SPLIT_TABLE[8193][2] == SC.SPLIT_TABLE[8192][2] == SC.MAX_SPLIT
+    _assert_partial_rows_fit()
 
 
 # --------------------------------------------------------------------------------------- 1. act
@@ -162,6 +185,48 @@ def test_twin_critic_gradient_against_fp64(host, big, n, kind):
     gate(g[2 * NC:], g64[2 * NC:], "statistics")
 
 
+@pytest.fixture(scope="module")
+def wide():
+    """max_batch = 8,448: ld != mp at every row of ddpg_learner_cases.SPLIT_ROWS; the allocation's arithmetic is asserted first"""
+    _assert_partial_rows_fit()
+    lrn = _sac(SC.SPLIT_BIG)
+    yield lrn
+    lrn.close()
+
+
+def _twin_dev(c):
+    return {k: _cuda(c[k]) for k in ("obs", "act", "y", "critics")}
+
+
+@pytest.mark.parametrize("n,kind", SC.SPLIT_TWIN_CASES)
+def test_twin_critic_gradient_at_every_split_geometry(host, wide, n, kind):
+    """the block gates of test_twin_critic_gradient_against_fp64 on both critics at the rows of ddpg_learner_cases.SPLIT_ROWS: two to
+    eight partial rows of 2 x 68,353 + 4 floats, on a fresh handle of max_batch == m and on the NaN-filled one of 8,448, byte for byte;
+    the host build up to sac_cases.HOST_ROWS_MAX"""
+    c = SC.grad_case(n, kind)
+    dev = _twin_dev(c)
+    own = _sac(n)                           # max_batch == m, fresh
+    g = _twin(own, dev)
+    own.close()
+    _poison(wide)                           # a larger max_batch, every word of its allocation NaN
+    g_big = _twin(wide, dev)
+    assert np.isfinite(g).all() and g.tobytes() == g_big.tobytes()   # nothing stale read, the handle's size does not matter
+    g64 = SC.twin_reference(n, kind)
+    hg = SC.host_twin_critic_grad(host, c["critics"], c["obs"], c["act"], c["y"]) if n <= SC.HOST_ROWS_MAX else None
+    for k in (0, 1):
+        sl = slice(k * NC, (k + 1) * NC)
+        d = SC.block_distances(g[sl], g64[sl], A.CRITIC_SIZES)
+        print(f"n={n} {kind} critic {k}: largest block distance from fp64 {max(d.values()):.3g}")
+        assert max(d.values()) <= GRAD_GATE, d
+        if hg is not None:
+            dh = SC.block_distances(g[sl], hg[sl], A.CRITIC_SIZES)
+            print(f"n={n} {kind} critic {k}: largest block distance from the host build {max(dh.values()):.3g}")
+            assert max(dh.values()) <= GRAD_GATE, dh
+    gate(g[2 * NC:], g64[2 * NC:], f"n={n} {kind} twin statistics")
+    if hg is not None:
+        gate(g[2 * NC:], hg[2 * NC:], f"n={n} {kind} twin statistics against the host build")
+
+
 # --------------------------------------------------------------------------------------- 4. the actor gradient
 def _actor_grad(lrn, dev, draw=0):
     g = Guarded((GLEN,))
@@ -175,7 +240,7 @@ def _dev(c):
     return {k: _cuda(c[k]) for k in ("obs", "actor", "critics")}
 
 
-def _check_actor_gradient(host, big, n, kind):
+def _check_actor_gradient(host, big, n, kind, with_host=True):
     c = SC.grad_case(n, kind)
     g64, g32 = SC.references(n, kind)
     dev = _dev(c)
@@ -186,6 +251,8 @@ def _check_actor_gradient(host, big, n, kind):
     g_big = _actor_grad(big, dev)
     assert np.isfinite(g).all() and g.tobytes() == g_big.tobytes()   # nothing stale read, the handle's size does not matter
     SC.check_actor_gradient(f"n={n} {kind}", g, g64, g32, gate)
+    if not with_host:
+        return
     hg = SC.host_actor_grad(host, c["actor"], c["critics"], c["obs"], SEED, 0)
     d = SC.actor_block_distances(g, hg)
     print(f"n={n} {kind}: largest block distance from the host build {max(d.values()):.3g}")
@@ -199,17 +266,76 @@ def test_actor_gradient_against_fp64_fp32_torch_and_the_host_build(host, big, n,
     _check_actor_gradient(host, big, n, kind)
 
 
-@pytest.fixture(scope="module")
-def wide():
-    lrn = _sac(2304)
-    yield lrn
-    lrn.close()
+@pytest.mark.parametrize("n,kind", SC.SPLIT_ACTOR_CASES)
+def test_actor_gradient_at_every_split_geometry(host, wide, n, kind):
+    """the assertions of test_actor_gradient_against_fp64_fp32_torch_and_the_host_build at the rows of ddpg_learner_cases.SPLIT_ROWS
+    (`init` at all seven, `x3` at 513, 2,049 and 8,193, `spread` at 769 and 2,049): two to eight partial rows of 68,612 + 5 floats
+    behind the two-launch chain, whose padded rows must add exact zeros; a fresh handle of max_batch == m against the NaN-filled one of
+    8,448, byte for byte; the host build up to sac_cases.HOST_ROWS_MAX"""
+    _check_actor_gradient(host, wide, n, kind, with_host=n <= SC.HOST_ROWS_MAX)
 
 
-@pytest.mark.parametrize("n", SC.SPLIT_ROWS)
-def test_actor_gradient_at_two_split_geometries(host, wide, n):
-    """513 rows: two partial rows, 384 + 256 with 129 real rows in the second; 2,049: six, the last shorter; combined in fp64"""
-    _check_actor_gradient(host, wide, n, "init")
+def _full_dev(c):
+    return {k: _cuda(c[k]) for k in ("obs", "act", "y", "actor", "critics")}
+
+
+def _fresh(n, call, dev):
+    own = _sac(n)
+    g = call(own, dev)
+    own.close()
+    return g
+
+
+def test_no_leftover_between_split_geometries_and_calls_on_one_handle(wide):
+    """8,193 -> 513 -> 33 -> 2,049 -> 769 rows on the NaN-filled handle of 8,448 (8 partial rows, then 2, none, 6 and 3), at each m the
+    twin critic gradient and then the actor gradient, whose partial rows lie at different strides in the same storage: every result
+    is what a fresh handle of exactly that size returns, byte for byte; the sequence a second time returns the same bytes; another
+    draw at 2,049 rows changes the actor gradient"""
+    devs = {n: _full_dev(SC.grad_case(n, "init")) for n in SC.SPLIT_SEQUENCE}
+    fresh = {n: (_fresh(n, _twin, devs[n]), _fresh(n, _actor_grad, devs[n])) for n in SC.SPLIT_SEQUENCE}
+    assert all(np.isfinite(t).all() and np.isfinite(a).all() for t, a in fresh.values())
+    _poison(wide)
+    for run in range(2):
+        for n in SC.SPLIT_SEQUENCE:
+            t = _twin(wide, devs[n])
+            a = _actor_grad(wide, devs[n])
+            assert t.tobytes() == fresh[n][0].tobytes(), (run, n, "twin critic gradient")
+            assert a.tobytes() == fresh[n][1].tobytes(), (run, n, "actor gradient")
+    other = _actor_grad(wide, devs[2049], draw=1)
+    assert np.isfinite(other).all() and other[:NA].tobytes() != fresh[2049][1][:NA].tobytes()   # another draw, another sample
+
+
+# --------------------------------------------------------------------------------------- 4b. the statistics at a split
+@pytest.mark.parametrize("n", SC.SPLIT_STAT_ROWS)
+def test_statistics_at_a_split(wide, n):
+    """the five sums behind the actor's parameters and the twin call's four statistics against fp64, each under `gate`, at 769 rows
+    (three splits, the last holds one real row) and 8,193 (eight, the last short)"""
+    c = SC.grad_case(n, "init")
+    dev = _full_dev(c)
+    _poison(wide)
+    a, t = _actor_grad(wide, dev), _twin(wide, dev)
+    gate(a[NA:], SC.references(n, "init")[0][NA:], f"n={n} the actor call's five tail sums")
+    gate(t[2 * NC:], SC.twin_reference(n, "init")[2 * NC:], f"n={n} the twin call's four statistics")
+
+
+def test_statistics_see_the_lone_row_of_the_last_split(wide):
+    """769 rows: row 768 is the one real row of the third split.  With that row alone replaced (sac_cases.changed_last_row: on the
+    fp64 reference every row-dependent sum moves by more than 2 GATE) every such statistic of both calls changes, and is within
+    `gate` of the changed case's fp64 reference; ent_coef, the same alpha / m from every row, keeps its bytes"""
+    n = 769
+    assert SC.SPLIT_LAST_REAL[n] == 1 and SC.SPLIT_TABLE[n][2] == 3
+    c, (changed, b64, u64) = SC.grad_case(n, "init"), SC.changed_last_row(n, "init")
+    a64, t64 = SC.references(n, "init")[0], SC.twin_reference(n, "init")
+    rs = SC.ROW_SUMS
+    assert SC.moved(b64[NA:NA + rs], a64[NA:NA + rs]).min() > 2 * SC.GATE and SC.moved(u64[2 * NC:], t64[2 * NC:]).min() > 2 * SC.GATE   # on the reference, first
+    _poison(wide)
+    a0, t0 = _actor_grad(wide, _full_dev(c)), _twin(wide, _full_dev(c))
+    a1, t1 = _actor_grad(wide, _full_dev(changed)), _twin(wide, _full_dev(changed))
+    print(f"n={n}: the replaced row moves the tail sums by {SC.moved(a1[NA:], a0[NA:])} and the twin statistics by {SC.moved(t1[2 * NC:], t0[2 * NC:])}")
+    assert (a1[NA:NA + rs] != a0[NA:NA + rs]).all() and a1[NA + rs:].tobytes() == a0[NA + rs:].tobytes()
+    assert (t1[2 * NC:] != t0[2 * NC:]).all()
+    gate(a1[NA:], b64[NA:], f"n={n} the tail sums with row {n - 1} replaced")
+    gate(t1[2 * NC:], u64[2 * NC:], f"n={n} the twin statistics with row {n - 1} replaced")
 
 
 def test_no_leftover_scratch_between_sizes(big):

@@ -8,9 +8,20 @@ Largest distances reached on an MI355X, next to each gate (fp32 torch on the sam
   act / target outputs against fp64, gate 1e-5: log_std 8.6e-6 (spread: the output layer's rows are x 60 and cancel), a' 5.0e-6, mu 4.1e-6,
     logp' 3.9e-6, action 3.7e-6, y 3.3e-6, z 2.8e-6; against the host build: log_std 5.7e-6, logp' 4.1e-6, mu 3.1e-6, y 2.5e-6, z 2.2e-7
   actor gradient blocks against fp64, gate 1e-5: init 2.5e-7 [fp32 torch 4.5e-7], x3 3.9e-6 [2.0e-2], spread 3.8e-6 [7.6e-2]; against the
-    host build 3.4e-6; statistics 7.9e-7 (gate 1e-5); the split geometries 1.6e-7 (513 rows) and 9.3e-8 (2,049).  fp32 torch misses the
-    gate on x3 and spread by the way SB3 writes the loss (see tests/test_sac_cpu.py); the kernels meet it on the same cases
-  critic gradient against fp64: 9.5e-7; six chained steps: every block at 1.0x fp32 torch's floored distance (gate 4x)."""
+    host build 3.4e-6; statistics 7.9e-7 (gate 1e-5).  fp32 torch misses the gate on x3 and spread by the way SB3 writes the loss (see
+    tests/test_sac_cpu.py); the kernels meet it on the same cases
+  critic gradient against fp64: 9.5e-7; six chained steps: every block at 1.0x fp32 torch's floored distance (gate 4x).
+
+The sample split (ddpg_learner_cases.SPLIT_TABLE; the allocation's arithmetic is asserted first, launching nothing: 1,544 scratch rows
+and 8.0000 partial rows of 64,206 floats on a SAC handle, exactly a TD3 twin handle's).  Largest block distance from fp64 per row, on
+a fresh handle of max_batch == m and on the NaN-filled one of 8,448 rows (identical bytes), gate 1e-5:
+  actor gradient, init: 385 1.2e-7, 513 1.6e-7, 769 1.4e-7, 1,025 1.1e-7, 2,049 9.3e-8, 8,192 1.1e-7, 8,193 1.3e-7 [fp32 torch up to
+    8.3e-7]; x3: 513 3.9e-7, 2,049 3.3e-7, 8,193 1.5e-7 [1.7e-3]; spread: 769 1.3e-6, 2,049 6.8e-7 [5.6e-2]; against the host build
+    (every row: sac_cases.HOST_ROWS_MAX) 2.1e-6 (769 spread), init and x3 at most 2.6e-7; statistics 1.4e-7
+  critic gradient, 0.5 x the TD3 call byte for byte on the SAC handle, against fp64: init 1.1e-7 (385), 1.5e-7 (513), 1.4e-7 (769),
+    1.1e-7 (1,025), 8.5e-8 (2,049), 1.1e-7 (8,192), 1.3e-7 (8,193); x3 3.4e-7 (513), 1.4e-7 (2,049), 1.4e-7 (8,193)
+  the five tail sums / the twin call's four statistics under `gate`: 769 rows 1.4e-8 / 6.9e-9, 8,193 rows 8.9e-8 / 8.0e-9; with row 768
+    of 769 replaced (the sums move by 1.8e-4 to 1.2e-3, the twin statistics by 1.8e-4 to 1.0e-2) 6.3e-8 / 1.4e-8."""
 import os
 import sys
 
@@ -21,14 +32,14 @@ import ref_offpolicy as R
 import ref_sac as S
 import sac_cases as SC
 import td3_cases as TC
-from ddpg_learner_cases import GRAD_GATE, block_distances
+from ddpg_learner_cases import GRAD_GATE, SPLIT_CASES, block_distances
 from offpolicy_cases import GAMMA, ROOT, SEED, gate
 from test_ddpg_learner_gpu import _poison
 from test_offpolicy_gpu import Guarded, _cuda
 
 pytestmark = pytest.mark.gpu
 NA, NC = SC.NA, SC.NC
-GLEN = NA + 1 + S.NSTAT
+GLEN, TLEN = NA + 1 + S.NSTAT, 2 * NC + 4
 UNTOUCHED = np.float32(-3.25)   # Guarded's float32 sentinel
 
 
@@ -55,6 +66,23 @@ def big():
     lrn = _sac(1024)
     yield lrn
     lrn.close()
+
+
+# --------------------------------------------------------------------------------------- 0. the allocation, launching nothing
+def _assert_partial_rows_fit():
+    rows, _ = SC.assert_partial_rows_fit(_sac, max(NA + SC.SAC_TAIL, TLEN), "SAC handle")
+    assert rows >= 2 * 544 + 4 + 1 + S.NSTAT   # the actor's image (test_existing_calls_return_the_same_bytes_on_a_sac_handle)
+
+
+def test_eight_partial_rows_fit_the_allocation():
+    """first in the file: the arithmetic of the handle's one allocation is known before any launch with eight workgroup rows.  A
+    TD3 twin handle is the control: its sizes are known exactly (tests/test_td3_gpu.py runs it at every split geometry)"""
+    from balance_robot_mujoco_rl_amd import DeviceTD3Learner
+    from ddpg_learner_cases import ADAM
+    assert SC.SPLIT_TABLE[8193][2] == SC.SPLIT_TABLE[8192][2] == SC.MAX_SPLIT
+    twin = SC.assert_partial_rows_fit(lambda mb: DeviceTD3Learner(device=0, max_batch=mb, **ADAM), max(TLEN, R.NACTOR + 2), "TD3 twin handle")
+    assert twin == (2 * 772, SC.MAX_SPLIT * TLEN)
+    _assert_partial_rows_fit()
 
 
 # --------------------------------------------------------------------------------------- 1. act
@@ -122,10 +150,30 @@ def test_target_against_fp64_and_the_host_build(nets, host, m, kind):
 
 
 # --------------------------------------------------------------------------------------- 3. the critic gradient
+@pytest.fixture(scope="module")
+def wide():
+    """max_batch = 8,448: ld != mp at every row of ddpg_learner_cases.SPLIT_ROWS; the allocation's arithmetic is asserted first"""
+    _assert_partial_rows_fit()
+    lrn = _sac(SC.SPLIT_BIG)
+    yield lrn
+    lrn.close()
+
+
 @pytest.mark.parametrize("n", (1, 33, 129, 1000))
 def test_critic_gradient_is_half_the_td3_call_byte_for_byte(big, n):
+    _check_half_the_td3_call(big, n, "x3")
+
+
+@pytest.mark.parametrize("n,kind", SPLIT_CASES)
+def test_critic_gradient_is_half_the_td3_call_at_every_split_geometry(wide, n, kind):
+    """the same identity at the rows of ddpg_learner_cases.SPLIT_ROWS on the NaN-filled SAC handle of 8,448, whose partial rows are
+    sized for the SAC actor's row, not the twin one (the TD3 side is held to fp64 at these rows by tests/test_td3_gpu.py)"""
+    _check_half_the_td3_call(wide, n, kind)
+
+
+def _check_half_the_td3_call(big, n, kind):
     import torch
-    c = TC.twin_case(n, "x3")
+    c = TC.twin_case(n, kind)
     dev = {k: _cuda(c[k]) for k in ("obs", "act", "y", "critics")}
     _poison(big)
     td3, sac = Guarded((2 * NC + 4,)), Guarded((2 * NC + 4,))
@@ -185,17 +233,85 @@ def test_actor_gradient_against_fp64_fp32_torch_and_the_host_build(host, big, n,
     _check_actor_gradient(host, big, n, kind)
 
 
-@pytest.fixture(scope="module")
-def wide():
-    lrn = _sac(2304)
-    yield lrn
-    lrn.close()
+@pytest.mark.parametrize("n,kind", SC.SPLIT_ACTOR_CASES)
+def test_actor_gradient_at_every_split_geometry(host, wide, n, kind):
+    """the assertions of test_actor_gradient_against_fp64_fp32_torch_and_the_host_build at the rows of ddpg_learner_cases.SPLIT_ROWS
+    (`init` at all seven, `x3` at 513, 2,049 and 8,193, `spread` at 769 and 2,049): two to eight partial rows of 63,104 + 5 floats
+    behind the two-launch chain, whose padded rows must add exact zeros; a fresh handle of max_batch == m against the NaN-filled one of
+    8,448, byte for byte; the host build up to sac_cases.HOST_ROWS_MAX"""
+    _check_actor_gradient(host, wide, n, kind, with_host=n <= SC.HOST_ROWS_MAX)
 
 
-@pytest.mark.parametrize("n", SC.SPLIT_ROWS)
-def test_actor_gradient_at_two_split_geometries(host, wide, n):
-    """513 rows: two partial rows, 384 + 256 with 129 real rows in the second; 2,049: six, the last shorter; combined in fp64"""
-    _check_actor_gradient(host, wide, n, "init")
+def _twin(lrn, dev):
+    import torch
+    g = Guarded((TLEN,))
+    lrn.twin_critic_grad(dev["critics"], dev["obs"], dev["act"], dev["y"], out=g.t)
+    torch.cuda.synchronize()
+    assert g.intact(), "a kernel wrote outside the gradient buffer"
+    return g.np()
+
+
+def _full_dev(c):
+    return {k: _cuda(c[k]) for k in ("obs", "act", "y", "actor", "critics")}
+
+
+def _fresh(n, call, dev):
+    own = _sac(n)
+    g = call(own, dev)
+    own.close()
+    return g
+
+
+def test_no_leftover_between_split_geometries_and_calls_on_one_handle(wide):
+    """8,193 -> 513 -> 33 -> 2,049 -> 769 rows on the NaN-filled handle of 8,448 (8 partial rows, then 2, none, 6 and 3), at each m the
+    twin critic gradient and then the actor gradient, whose partial rows lie at different strides in the same storage: every result
+    is what a fresh handle of exactly that size returns, byte for byte; the sequence a second time returns the same bytes; another
+    draw at 2,049 rows changes the actor gradient"""
+    devs = {n: _full_dev(SC.grad_case(n, "init")) for n in SC.SPLIT_SEQUENCE}
+    fresh = {n: (_fresh(n, _twin, devs[n]), _fresh(n, _actor_grad, devs[n])) for n in SC.SPLIT_SEQUENCE}
+    assert all(np.isfinite(t).all() and np.isfinite(a).all() for t, a in fresh.values())
+    _poison(wide)
+    for run in range(2):
+        for n in SC.SPLIT_SEQUENCE:
+            t = _twin(wide, devs[n])
+            a = _actor_grad(wide, devs[n])
+            assert t.tobytes() == fresh[n][0].tobytes(), (run, n, "twin critic gradient")
+            assert a.tobytes() == fresh[n][1].tobytes(), (run, n, "actor gradient")
+    other = _actor_grad(wide, devs[2049], draw=1)
+    assert np.isfinite(other).all() and other[:NA].tobytes() != fresh[2049][1][:NA].tobytes()   # another draw, another sample
+
+
+# --------------------------------------------------------------------------------------- 4b. the statistics at a split
+@pytest.mark.parametrize("n", SC.SPLIT_STAT_ROWS)
+def test_statistics_at_a_split(wide, n):
+    """the five sums behind the actor's parameters and the twin call's four statistics against fp64, each under `gate`, at 769 rows
+    (three splits, the last holds one real row) and 8,193 (eight, the last short)"""
+    c = SC.grad_case(n, "init")
+    dev = _full_dev(c)
+    _poison(wide)
+    a, t = _actor_grad(wide, dev), _twin(wide, dev)
+    gate(a[NA:], SC.references(n, "init")[0][NA:], f"n={n} the actor call's five tail sums")
+    gate(t[2 * NC:], SC.twin_reference(n, "init")[2 * NC:], f"n={n} the twin call's four statistics")
+
+
+def test_statistics_see_the_lone_row_of_the_last_split(wide):
+    """769 rows: row 768 is the one real row of the third split.  With that row alone replaced (sac_cases.changed_last_row: on the
+    fp64 reference every row-dependent sum moves by more than 2 GATE) every such statistic of both calls changes, and is within
+    `gate` of the changed case's fp64 reference; ent_coef, the same alpha / m from every row, keeps its bytes"""
+    n = 769
+    assert SC.SPLIT_LAST_REAL[n] == 1 and SC.SPLIT_TABLE[n][2] == 3
+    c, (changed, b64, u64) = SC.grad_case(n, "init"), SC.changed_last_row(n, "init")
+    a64, t64 = SC.references(n, "init")[0], SC.twin_reference(n, "init")
+    rs = SC.ROW_SUMS
+    assert SC.moved(b64[NA:NA + rs], a64[NA:NA + rs]).min() > 2 * SC.GATE and SC.moved(u64[2 * NC:], t64[2 * NC:]).min() > 2 * SC.GATE   # on the reference, first
+    _poison(wide)
+    a0, t0 = _actor_grad(wide, _full_dev(c)), _twin(wide, _full_dev(c))
+    a1, t1 = _actor_grad(wide, _full_dev(changed)), _twin(wide, _full_dev(changed))
+    print(f"n={n}: the replaced row moves the tail sums by {SC.moved(a1[NA:], a0[NA:])} and the twin statistics by {SC.moved(t1[2 * NC:], t0[2 * NC:])}")
+    assert (a1[NA:NA + rs] != a0[NA:NA + rs]).all() and a1[NA + rs:].tobytes() == a0[NA + rs:].tobytes()
+    assert (t1[2 * NC:] != t0[2 * NC:]).all()
+    gate(a1[NA:], b64[NA:], f"n={n} the tail sums with row {n - 1} replaced")
+    gate(t1[2 * NC:], u64[2 * NC:], f"n={n} the twin statistics with row {n - 1} replaced")
 
 
 def test_no_leftover_scratch_between_sizes(big):
