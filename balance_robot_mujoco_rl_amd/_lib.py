@@ -24,10 +24,11 @@ SIM_FLAGS = ["-Xarch_device", "-ffast-math", "-Xarch_device", "-fgpu-flush-denor
 # keep IEEE math (checked against fp32 torch at rtol 1e-5 / bit for bit against their host builds under tests/), and so does the
 # episode monitor, the PPO learner (fp64 torch autograd at 1e-5 per parameter block), the DDPG data path (fp64 numpy at 1e-5) and
 # the DDPG learner (fp64 torch autograd at 1e-5 per block); the build id names the step and policy kernels that committed profiles
-# were measured on, so the other seven units stay out of it.
+# were measured on, so the other eight units stay out of it.  VecNormalize (fp64 statistics, byte for byte against its host build) is
+# the eighth.
 UNITS = [("brs_kernels.hip", SIM_FLAGS, True), ("brs_policy.hip", [], True), ("brs_render.hip", [], False), ("brs_qpolicy.hip", [], False),
          ("brs_monitor.hip", [], False), ("brs_learner.hip", [], False), ("brs_offpolicy.hip", [], False),
-         ("brs_ddpg_learner.hip", [], False), ("brs_qactor.hip", [], False)]
+         ("brs_ddpg_learner.hip", [], False), ("brs_qactor.hip", [], False), ("brs_vecnorm.hip", [], False)]
 SRC = os.path.join(_CSRC, UNITS[0][0])  # the unit that takes the A/B flags and the build id stamp
 # what the build id hashes next to the sources of its units; brs_host.hpp holds no kernel code and stays out of it.  The policy
 # kernels take their tower tiling from brs_policy_tile.hpp and, through it, the parameter layout from brs_learner.hpp
@@ -93,6 +94,14 @@ class BrsLearnerInfo(C.Structure):
 
 class BrsReplayStorage(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("obs", "next_obs", "action", "reward", "done")]
+
+
+class BrsVecnormConfig(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("gamma", "epsilon", "clip_obs", "clip_reward")] + [(k, C.c_int32) for k in ("norm_obs", "norm_reward")]
+
+
+class BrsVecnormStats(C.Structure):
+    _fields_ = [(k, C.c_double * 6) for k in ("obs_mean", "obs_var", "obs_count")] + [(k, C.c_double) for k in ("ret_mean", "ret_var", "ret_count")]
 
 
 class BrsQLayer(C.Structure):
@@ -231,6 +240,16 @@ SIGNATURES = {
         "brs_sac_actor_grad": (C.c_int, [_vp, _vp, _vp, _i32, _vp, C.c_uint64, C.c_uint32, _i32, _f32, _vp, _vp]),
         "brs_ddpg_create_arch": (C.c_int, [_i32, _i32, C.POINTER(_vp)]),
         "brs_ddpg_learner_create_sac_arch": (C.c_int, [_i32, _i32, _i32, C.POINTER(_vp)]),
+        "brs_vecnorm_create": (C.c_int, [_i32, _i32, C.POINTER(BrsVecnormConfig), C.POINTER(_vp)]),
+        "brs_vecnorm_destroy": (C.c_int, [_vp]),
+        "brs_vecnorm_last_error": (C.c_char_p, [_vp]),
+        "brs_vecnorm_reset": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+        "brs_vecnorm_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+        "brs_vecnorm_normalize_obs": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+        "brs_vecnorm_normalize_reward": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+        "brs_vecnorm_get_stats": (C.c_int, [_vp, C.POINTER(BrsVecnormStats), _vp]),
+        "brs_vecnorm_set_stats": (C.c_int, [_vp, C.POINTER(BrsVecnormStats), _vp]),
+        "brs_vecnorm_get_returns": (C.c_int, [_vp, _dp, _vp]),
     },
     "brs_render.h": {
         "brs_render_default_camera": (None, [C.POINTER(BrsCamera)]),

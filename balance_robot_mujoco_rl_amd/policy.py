@@ -118,11 +118,14 @@ class DeviceRollout:
     """[T][N] rollout buffer resident in HBM (SB3's RolloutBuffer, without the host): collect() alternates
     brs_policy_act -> brs_step -> brs_rollout_bootstrap with no synchronisation and no allocation, finish() runs GAE.
     `monitor`: an EpisodeMonitor (monitor.py) that is fed the env's own reward and done flags of every step (one more kernel
-    per step, still no synchronisation); its statistics are read by the caller, whenever it wants them."""
+    per step, still no synchronisation); its statistics are read by the caller, whenever it wants them.
+    `normalize`: a DeviceVecNormalize (vecnorm.py) between the simulator and the buffer, as SB3 wraps the env in VecNormalize: the
+    buffer holds the normalised observation and reward, the time-limit bootstrap reads the normalised terminal observation, the
+    monitor still sees the env's own reward.  None: collect() enqueues what it enqueued before the argument existed."""
 
-    def __init__(self, sim, policy, n_steps, gamma=0.99, gae_lambda=0.95, monitor=None):
+    def __init__(self, sim, policy, n_steps, gamma=0.99, gae_lambda=0.95, monitor=None, normalize=None):
         self.sim, self.policy, self.T, self.gamma, self.lam = sim, policy, int(n_steps), float(gamma), float(gae_lambda)
-        self.monitor = monitor
+        self.monitor, self.normalize = monitor, normalize
         n, d, T = sim.n, sim.device, self.T
         f = lambda *s: torch.zeros(s, dtype=torch.float32, device=d)
         self.obs, self.action, self.logp, self.value, self.reward = f(T, n, 6), f(T, n, 2), f(T, n), f(T, n), f(T, n)
@@ -135,9 +138,9 @@ class DeviceRollout:
         self._step = 0
 
     def collect(self):
-        sim, pol = self.sim, self.policy
+        sim, pol, norm = self.sim, self.policy, self.normalize
         if self._last_obs is None:
-            self._last_obs = sim.reset().clone()
+            self._last_obs = (sim.reset() if norm is None else norm.reset(sim.reset())).clone()
         for t in range(self.T):
             self.obs[t].copy_(self._last_obs)
             self.episode_start[t].copy_(self._last_start)
@@ -146,6 +149,8 @@ class DeviceRollout:
             obs, rew, term, trunc, tobs = sim.step(self._clipped)
             if self.monitor is not None:
                 self.monitor.update(rew, term, trunc)
+            if norm is not None:
+                obs, rew, tobs = norm.step(obs, rew, term, trunc, tobs)
             self.reward[t].copy_(rew)
             pol.bootstrap(tobs, term, trunc, self.gamma, self.reward[t])
             self._last_obs.copy_(obs)

@@ -396,6 +396,53 @@ int brs_sac_actor_grad(brs_ddpg_learner*, const float* actor_dev, const float* c
 int brs_ddpg_create_arch(int32_t device, int32_t arch, brs_ddpg** out);
 int brs_ddpg_learner_create_sac_arch(int32_t device, int32_t max_batch, int32_t arch, brs_ddpg_learner** out);
 
+/* ---- VecNormalize: SB3's VecNormalize / RunningMeanStd for the n envs of a simulator, on the device.  Per
+ * column -- the six observation columns and the discounted return -- a running mean, variance and count in fp64 (0, 1, 1e-4 at
+ * create), and per env the discounted return (fp64, 0 at create).  A batch enters as its (count, mean, M2) triple, reduced by a
+ * tree of Chan merges whose shape depends on n alone (no atomics): the statistics are the same bytes on every run.
+ *   batch update   delta = bm - mean; tot = count + n; mean += delta n / tot;
+ *                  var = (var count + bv n + delta^2 count n / tot) / tot; count = tot
+ *   normalise      obs_out = clip((obs - mean) / sqrt(var + epsilon), +-clip_obs); reward_out = clip(reward / sqrt(ret_var +
+ *                  epsilon), +-clip_reward); evaluated in fp64, rounded once to fp32; a NaN stays a NaN; norm_obs == 0 /
+ *                  norm_reward == 0 copy the input through */
+typedef struct brs_vecnorm brs_vecnorm;
+
+typedef struct brs_vecnorm_config {
+  double gamma;        /* discount of the return the reward statistics are taken of (0.99) */
+  double epsilon;      /* 1e-8 */
+  double clip_obs;     /* >= 0 (10) */
+  double clip_reward;  /* >= 0 (10) */
+  int32_t norm_obs;
+  int32_t norm_reward;
+} brs_vecnorm_config;
+
+typedef struct brs_vecnorm_stats {
+  double obs_mean[6], obs_var[6], obs_count[6];
+  double ret_mean, ret_var, ret_count;
+} brs_vecnorm_stats;
+
+int brs_vecnorm_create(int32_t device, int32_t n, const brs_vecnorm_config* config, brs_vecnorm** out);
+int brs_vecnorm_destroy(brs_vecnorm*);
+const char* brs_vecnorm_last_error(const brs_vecnorm*);
+/* returns = 0; with training && norm_obs the observation statistics take obs_dev [n][6]; obs_out_dev [n][6] receives the
+ * normalised observations.  Only enqueues. */
+int brs_vecnorm_reset(brs_vecnorm*, const float* obs_dev, int32_t training, float* obs_out_dev, void* stream);
+/* one env step, in this order: with training && norm_obs the observation statistics take obs_dev; with training
+ * returns = returns gamma + reward and the return statistics take returns; the three outputs are written with the updated
+ * statistics (terminal_obs_out_dev: every row of terminal_obs_dev [n][6]); returns[i] = 0 where terminated[i] | truncated[i],
+ * training or not.  Only enqueues, no allocation.  An output may not alias an input. */
+int brs_vecnorm_step(brs_vecnorm*, const float* obs_dev, const float* reward_dev, const uint8_t* terminated_dev,
+                     const uint8_t* truncated_dev, const float* terminal_obs_dev, int32_t training, float* obs_out_dev,
+                     float* reward_out_dev, float* terminal_obs_out_dev, void* stream);
+/* any m >= 1, no state touched: in_dev / out_dev [m][6] and [m].  Only enqueue. */
+int brs_vecnorm_normalize_obs(brs_vecnorm*, int32_t m, const float* in_dev, float* out_dev, void* stream);
+int brs_vecnorm_normalize_reward(brs_vecnorm*, int32_t m, const float* in_dev, float* out_dev, void* stream);
+/* VecNormalize.save / .load: the 21 doubles, and returns [n].  get_* wait for the stream; set_stats only enqueues a copy of
+ * *in_host, which is read before the call returns */
+int brs_vecnorm_get_stats(brs_vecnorm*, brs_vecnorm_stats* out_host, void* stream);
+int brs_vecnorm_set_stats(brs_vecnorm*, const brs_vecnorm_stats* in_host, void* stream);
+int brs_vecnorm_get_returns(brs_vecnorm*, double* returns_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ GAE as HIP kernels); the update is taken in torch, or with --device-learner by D
 
 The value loss is the PPO tool's 0.5 (v - ret / ret_scale)^2, so --vf-coef 1.0 (the default) is SB3's vf_coef = 0.5 on mse_loss."""
 import argparse, json, os, sys, time
+import numpy as np
 import torch
 import torch.distributed as dist
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,8 +55,9 @@ def torch_update(model, opt, obs, act, adv, ret, vf_coef=1.0, ent=0.0, max_grad_
 
 
 def train(sim, model, iters, n_steps=5, lr=7e-4, alpha=0.99, rms_eps=1e-5, ent=0.0, vf_coef=1.0, gamma=0.99, lam=1.0, max_grad_norm=0.5,
-          normalize_advantage=False, device_learner=False, seed=0, env_index_base=0, log=None, tag="", after_iter=None, log_every=100):
-    """`device_learner`: True builds a DeviceA2CLearner from `model`, an instance is used as it is.  -> (env steps taken, the learner
+          normalize_advantage=False, device_learner=False, seed=0, env_index_base=0, log=None, tag="", after_iter=None, log_every=100,
+          vec_normalize=None):
+    """`vec_normalize`: a DeviceVecNormalize that DeviceRollout puts between the simulator and its buffer.  `device_learner`: True builds a DeviceA2CLearner from `model`, an instance is used as it is.  -> (env steps taken, the learner
     or None).  `model` holds the current weights whenever after_iter runs and at the end"""
     from balance_robot_mujoco_rl_amd.learner import DeviceA2CLearner
     from balance_robot_mujoco_rl_amd.policy import DevicePolicy, DeviceRollout
@@ -71,7 +73,7 @@ def train(sim, model, iters, n_steps=5, lr=7e-4, alpha=0.99, rms_eps=1e-5, ent=0
         opt = RMSpropTFLike(model.parameters(), lr=lr, alpha=alpha, eps=rms_eps)
     pol = DevicePolicy(device=dev.index, seed=seed, env_index_base=env_index_base)
     mon = EpisodeMonitor(sim.n, device=dev.index)
-    ro = DeviceRollout(sim, pol, n_steps, gamma=gamma, gae_lambda=lam, monitor=mon)
+    ro = DeviceRollout(sim, pol, n_steps, gamma=gamma, gae_lambda=lam, monitor=mon, normalize=vec_normalize)
     flat = lambda t: t.reshape((-1,) + t.shape[2:])
     seen, total, t_start = (0, 0.0, 0), 0, time.time()
     for it in range(iters):
@@ -134,10 +136,16 @@ def main():
     ap.add_argument("--eval-episodes", type=int, default=1024)
     ap.add_argument("--save-best", default="")
     ap.add_argument("--device-learner", action="store_true", help="take the update with the HIP learner (brs_a2c_*) instead of torch")
+    ap.add_argument("--vec-normalize", action="store_true",
+                    help="SB3's VecNormalize on the device between the simulator and the rollout (one rank): running mean / variance "
+                    "of the observations and of the discounted return, clipped at 10; the evaluations use the frozen statistics, "
+                    "--save also writes them (<path>.vecnormalize.npz)")
     ap.add_argument("--save", default="", help="write the policy/value weights (torch state_dict) here")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if a.vec_normalize and world > 1:
+        ap.error("--vec-normalize runs on one rank only: merging the running statistics across ranks is not implemented")
     rank = int(os.environ.get("RANK", "0")); local = int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("BRS_PPO_ONE_DEVICE") == "1":
         local = 0
@@ -151,13 +159,18 @@ def main():
     dev = torch.device("cuda", local)
     model = ActorCritic(a.log_std_init).to(dev)
     sim = BatchedSim(a.env, a.envs, device=local, seed=2 * a.seed, env_index_base=rank * a.envs, auto_reset=True)
+    vecnorm = None
+    if a.vec_normalize:
+        from balance_robot_mujoco_rl_amd import DeviceVecNormalize
+        vecnorm = DeviceVecNormalize(a.envs, device=local, gamma=a.gamma)
     cb = None
     if a.eval_every > 0 and rank == 0:
-        cb = EvalCallback(a.env, a.eval_every, a.eval_episodes, min(a.eval_envs, a.eval_episodes), a.save_best, local)
+        cb = EvalCallback(a.env, a.eval_every, a.eval_episodes, min(a.eval_envs, a.eval_episodes), a.save_best, local, normalize=vecnorm)
     log = []
     t0 = time.perf_counter()
     total, _ = train(sim, model, a.iters, a.n_steps, a.lr, a.alpha, a.rms_eps, a.ent, a.vf_coef, a.gamma, a.lam, a.max_grad_norm,
-                     a.normalize_advantage, a.device_learner, 1000 * (a.seed + 1), rank * a.envs, log, a.env, cb)
+                     a.normalize_advantage, a.device_learner, 1000 * (a.seed + 1), rank * a.envs, log, a.env, cb,
+                     vec_normalize=vecnorm)
     wall = time.perf_counter() - t0
     sim.close()
     if world > 1:
@@ -168,9 +181,11 @@ def main():
     print(json.dumps(run), flush=True)
     evals = []
     if a.eval_steps > 0:
-        evals.append(evaluate(a.env, model, a.eval_envs, a.eval_steps)); print(json.dumps(evals[-1]), flush=True)
+        evals.append(evaluate(a.env, model, a.eval_envs, a.eval_steps, normalize=vecnorm)); print(json.dumps(evals[-1]), flush=True)
     if a.save:
         torch.save(model.state_dict(), a.save)
+        if vecnorm is not None:
+            np.savez(a.save + ".vecnormalize.npz", **vecnorm.state_dict())
     if a.out:
         json.dump(dict(args=vars(a), world_size=world, run=run, log=log, eval=evals, eval_during_training=cb.rows if cb else []),
                   open(a.out, "w"), indent=1)

@@ -8,6 +8,7 @@ actor / critic towers, state-independent log-std) consuming BatchedSim tensors d
     python tools/train_ppo_torch.py --env Env01-v2 --envs 16384 --iters 60 [--then Env03-v2 --iters2 60] [--out log.json]
 """
 import argparse, json, os, sys, time
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -87,14 +88,18 @@ class MixedSim:
 
 def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, log, tag, ent=0.0, reward_clip=None,
           critic_warmup=0, lr_end=None, norm_returns=False, target_kl=None, device_rollout=False, seed=0, env_index_base=0,
-          after_iter=None, device_learner=False):
-    """device_learner: take the optimiser steps with the HIP learner (balance_robot_mujoco_rl_amd.learner) instead of torch autograd +
+          after_iter=None, device_learner=False, vec_normalize=None):
+    """vec_normalize: a DeviceVecNormalize between the simulator and the rollout (device_rollout only), as SB3 wraps the env in
+    VecNormalize: the policy sees normalised observations, the buffer normalised rewards; the monitor keeps the env's own reward.
+    device_learner: take the optimiser steps with the HIP learner (balance_robot_mujoco_rl_amd.learner) instead of torch autograd +
     `opt`; True builds a DevicePPOLearner from `model` (Adam's moments start at zero), an instance is used as it is (main() keeps
     one over both phases).  `model` receives the learner's weights after every iteration; `opt` only supplies the learning rate."""
     n = sim.n
     dev = sim.device
     pol = None
     lrn = None
+    if vec_normalize is not None and not device_rollout:
+        raise ValueError("vec_normalize needs device_rollout: it runs between the simulator and the HIP rollout kernels")
     if device_learner:
         if not device_rollout:
             raise ValueError("device_learner needs device_rollout: it reads the rollout tensors of the HIP path")
@@ -110,7 +115,7 @@ def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, 
         S = torch.zeros((n_steps, n), dtype=torch.uint8, device=dev); gstep = 0
         mon = EpisodeMonitor(n, device=dev.index)   # episode returns and lengths stay on the device: read once per iteration
         seen = (0, 0.0, 0)
-    obs = sim.reset().clone()
+    obs = (sim.reset() if vec_normalize is None else vec_normalize.reset(sim.reset())).clone()
     ep_len = torch.zeros(n, device=dev); ep_ret = torch.zeros(n, device=dev)
     done_len_sum = done_ret_sum = done_cnt = 0.0
     B = {k: torch.zeros((n_steps, n) + s, device=dev) for k, s in dict(obs=(6,), act=(2,), logp=(), rew=(), val=(), done=(), boot=()).items()}
@@ -130,6 +135,8 @@ def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, 
                     pol.act(B["obs"][t], gstep, out=(B["act"][t], a_buf, B["logp"][t], B["val"][t])); gstep += 1
                     o, r, te, tr, to = sim.step(a_buf)
                     mon.update(r, te, tr)   # the env's own reward, before the clip and the bootstrap
+                    if vec_normalize is not None:
+                        o, r, to = vec_normalize.step(o, r, te, tr, to)
                     done = (te | tr).bool()
                     B["rew"][t] = r if reward_clip is None else r.clamp(max=reward_clip)
                     pol.bootstrap(to, te, tr, gamma, B["rew"][t])   # rew += gamma V(terminal_obs) where truncated only
@@ -246,15 +253,17 @@ def train(sim, model, opt, iters, n_steps, epochs, minibatch, gamma, lam, clip, 
 
 
 @torch.no_grad()
-def evaluate(env_id, model, n, steps, seed=123, device=0):
+def evaluate(env_id, model, n, steps, seed=123, device=0, normalize=None):
     """deterministic policy (mean action) on fresh envs: episode-length statistics and the share of episodes that
     run into the time limit (= balanced for the whole episode).  Every episode that ends within `steps` steps counts (an
-    EpisodeMonitor without targets; evaluate_policy is the SB3 measure with a quota per env)"""
+    EpisodeMonitor without targets; evaluate_policy is the SB3 measure with a quota per env).  `normalize`: the
+    DeviceVecNormalize the policy was trained behind; its statistics are used as they are (normalize_obs), not updated"""
     sim = BatchedSim(env_id, n, device=0, seed=seed, auto_reset=True)
     mon = EpisodeMonitor(n, device=0, max_len=sim.max_episode_steps)
+    see = (lambda o: o) if normalize is None else normalize.normalize_obs
     obs = sim.reset()
     for _ in range(steps):
-        obs, r, te, tr, _to = sim.step(model.pi(obs).clamp(-1, 1).contiguous())
+        obs, r, te, tr, _to = sim.step(model.pi(see(obs)).clamp(-1, 1).contiguous())
         mon.update(r, te, tr)
     s, median = mon.stats(), mon.median_len(lower=True)
     sim.close(); mon.close()
@@ -268,8 +277,9 @@ class EvalCallback:
     episodes (evaluate_policy) on a fresh simulator of fixed seed, so that successive evaluations start from the same states;
     the weights with the best mean return so far are saved to `save_best`"""
 
-    def __init__(self, env_id, every, episodes, envs, save_best="", device=0, seed=123):
+    def __init__(self, env_id, every, episodes, envs, save_best="", device=0, seed=123, normalize=None):
         self.env_id, self.every, self.episodes, self.envs, self.save_best = env_id, every, episodes, envs, save_best
+        self.see = (lambda o: o) if normalize is None else normalize.normalize_obs   # the statistics as they are, frozen
         self.device, self.seed, self.best, self.rows = device, seed, None, []
 
     @torch.no_grad()
@@ -277,7 +287,7 @@ class EvalCallback:
         if self.every <= 0 or (it + 1) % self.every:
             return
         sim = BatchedSim(self.env_id, self.envs, device=self.device, seed=self.seed, auto_reset=True)
-        mean, std = evaluate_policy(lambda obs, t: model.pi(obs).clamp(-1, 1).contiguous(), sim, n_eval_episodes=self.episodes)
+        mean, std = evaluate_policy(lambda obs, t: model.pi(self.see(obs)).clamp(-1, 1).contiguous(), sim, n_eval_episodes=self.episodes)
         sim.close()
         best = self.best is None or mean > self.best
         if best:
@@ -322,6 +332,10 @@ def main():
     ap.add_argument("--obs-init-scale", default="", help="comma-separated factors on the INITIAL first-layer weights per observation "
                     "channel (both towers), e.g. 1,0.1,1,1,1,1: Env01-v2's obs[1] is a finite difference of two noisy pitch samples "
                     "(+-10 rad/s of noise, envs/env01_v2.py:16-20 with RobotBaseEnv.py:142-157) and saturates freshly initialised tanh units")
+    ap.add_argument("--vec-normalize", action="store_true",
+                    help="SB3's VecNormalize on the device between the simulator and the rollout (needs --device-rollout, one rank): "
+                    "running mean / variance of the observations and of the discounted return, clipped at 10; the evaluations use "
+                    "the frozen statistics, --save also writes them (<path>.vecnormalize.npz)")
     ap.add_argument("--save", default="", help="write the policy/value weights (torch state_dict) here")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -330,6 +344,10 @@ def main():
     if a.device_learner and a.fix_log_std2:
         ap.error("--fix-log-std2 is not available with --device-learner (the learner updates every parameter)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if a.vec_normalize and not a.device_rollout:
+        ap.error("--vec-normalize requires --device-rollout (it runs between the simulator and the HIP rollout kernels)")
+    if a.vec_normalize and world > 1:
+        ap.error("--vec-normalize runs on one rank only: merging the running statistics across ranks is not implemented")
     rank = int(os.environ.get("RANK", "0")); local = int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("BRS_PPO_ONE_DEVICE") == "1":   # rehearsal of N ranks on a one-GPU box (with BRS_PPO_BACKEND=gloo)
         local = 0
@@ -351,6 +369,10 @@ def main():
     opt = torch.optim.Adam(model.parameters(), lr=a.lr)
     log, callbacks = [], []
     learner = False
+    vecnorm = None
+    if a.vec_normalize:   # one normaliser for both phases, as one VecNormalize wraps whatever env SB3 is given
+        from balance_robot_mujoco_rl_amd import DeviceVecNormalize
+        vecnorm = DeviceVecNormalize(a.envs, device=local, gamma=a.gamma)
     if a.device_learner:   # one learner for both phases: Adam's moments carry over, as `opt`'s do
         from balance_robot_mujoco_rl_amd.learner import DevicePPOLearner
         learner = DevicePPOLearner(device=local, vf_coef=0.5, max_grad_norm=0.5, separate_clip=True)
@@ -377,12 +399,13 @@ def main():
             sim = BatchedSim(env_id, a.envs, device=local, seed=2 * a.seed, env_index_base=base, auto_reset=True)
         cb = None
         if a.eval_every > 0 and rank == 0:   # the phase's own env id (the second phase of a mix: the new one)
-            cb = EvalCallback((a.env, a.then)[phase], a.eval_every, a.eval_episodes, min(a.eval_envs, a.eval_episodes), a.save_best, local)
+            cb = EvalCallback((a.env, a.then)[phase], a.eval_every, a.eval_episodes, min(a.eval_envs, a.eval_episodes), a.save_best, local,
+                              normalize=vecnorm)
             callbacks.append(cb)
         train(sim, model, opt, iters, a.n_steps, a.epochs, a.minibatch, a.gamma, a.lam, 0.2, log, env_id, a.ent, a.reward_clip,
               warm, a.lr2_end if phase == 1 else None, a.norm_returns or (phase == 1 and a.norm_returns2),
               a.target_kl2 if (phase == 1 and a.target_kl2 is not None) else a.target_kl, a.device_rollout, 1000 * (a.seed + 1) + phase, base,
-              after_iter=cb, device_learner=learner)
+              after_iter=cb, device_learner=learner, vec_normalize=vecnorm)
         sim.close()
     evals = []
     if world > 1:
@@ -391,9 +414,11 @@ def main():
         dist.destroy_process_group(); return
     if a.eval_steps > 0:
         for env_id in dict.fromkeys(e for e in (a.env, a.then) if e):
-            evals.append(evaluate(env_id, model, a.eval_envs, a.eval_steps)); print(json.dumps(evals[-1]), flush=True)
+            evals.append(evaluate(env_id, model, a.eval_envs, a.eval_steps, normalize=vecnorm)); print(json.dumps(evals[-1]), flush=True)
     if a.save:
         torch.save(model.state_dict(), a.save)
+        if vecnorm is not None:
+            np.savez(a.save + ".vecnormalize.npz", **vecnorm.state_dict())
     if a.out:
         json.dump(dict(args=vars(a), world_size=world, log=log, eval=evals, eval_during_training=[r for c in callbacks for r in c.rows]),
                   open(a.out, "w"), indent=1)
