@@ -55,43 +55,8 @@ namespace {
 using namespace brs::ddpg_learner;
 using namespace brs::ddpg_tile;
 using brs::learner::AdamScalars;
-using brs::sac::SacActor, brs::sac::SAC_TAIL, brs::sac::SAC_Z3_ROWS, brs::sac::SAC_ROW_LEN, brs::sac::SAC_NACTOR;
-using brs::sac::ArchReference, brs::sac::ArchSacDefault;
-
-// rows of a scratch image (each `ld` floats, ld = max_batch padded to the workgroup's 128 rows) sized for network N.  The single
-// calls use the actor's, the wider net, for both networks; the twin call keeps two images of the critic's back to back.
-template <class N, int ZR = Z3_ROWS> struct Layout {
-  static constexpr int H1 = 0, H2 = H1 + Tile<N>::H1P, DZ1 = H2 + Tile<N>::H2P, DZ2 = DZ1 + Tile<N>::H1P, Z3 = DZ2 + Tile<N>::H2P, ROWS = Z3 + ZR;
-};
-using Wide = Layout<Actor>;
-using Narrow = Layout<Critic>;
-static_assert(Tile<Critic>::H1P <= Tile<Actor>::H1P && Tile<Critic>::H2P <= Tile<Actor>::H2P, "the critic fits in the actor's scratch");
-constexpr int SCRATCH_ROWS = Wide::ROWS, TWIN_SCRATCH_ROWS = 2 * Narrow::ROWS > Wide::ROWS ? 2 * Narrow::ROWS : Wide::ROWS;
-// a SAC handle: the SAC actor's image with its nine per-sample rows (Z3_ROWS = 4 holds dz3[OUT <= 2] and two statistics only), and
-// whatever the calls above need, so that all of them run on it; its partial rows hold the longest row of any call
-using SacLay = Layout<SacActor, SAC_Z3_ROWS>;
-static_assert(SacActor::OUT + SAC_TAIL <= SAC_Z3_ROWS && Tile<SacActor>::H1P == Tile<Actor>::H1P && Tile<SacActor>::H2P == Tile<Actor>::H2P, "rows");
-constexpr int SAC_SCRATCH_ROWS = SacLay::ROWS > TWIN_SCRATCH_ROWS ? SacLay::ROWS : TWIN_SCRATCH_ROWS;
-constexpr int SAC_PARTIAL_LEN = SAC_ROW_LEN > TWIN_PARTIAL_LEN ? SAC_ROW_LEN : TWIN_PARTIAL_LEN;
-constexpr int SAC_LDS_FLOATS = Tile<SacActor>::L_SIZE > LDS_FLOATS ? Tile<SacActor>::L_SIZE : LDS_FLOATS;
-constexpr int imax(int a, int b) { return a > b ? a : b; }
-// The same for the SAC calls of architecture A: the actor's image with its nine per-sample rows, two images of the
-// critic's back to back, the longer of the actor's and the twin row as a partial row, one LDS image for both networks.
-template <class A> struct ArchDims {
-  using Pi = typename A::Pi;
-  using Qf = typename A::Qf;
-  using PiLay = Layout<Pi, SAC_Z3_ROWS>;
-  using QfLay = Layout<Qf>;
-  static constexpr int ROW_LEN = nparam<Pi>() + SAC_TAIL, TWIN_ROW_LEN = 2 * nparam<Qf>() + BRS_TD3_NSTAT;
-  static constexpr int SCRATCH_ROWS = imax(PiLay::ROWS, 2 * QfLay::ROWS), PARTIAL = imax(ROW_LEN, TWIN_ROW_LEN);
-  static constexpr int LDS = imax(Tile<Pi>::L_SIZE, Tile<Qf>::L_SIZE);
-  static_assert(Pi::OUT + SAC_TAIL <= SAC_Z3_ROWS && Qf::OUT + NSTAT <= Z3_ROWS, "rows");
-  static_assert(2 * LDS * sizeof(float) <= 160 * 1024, "two workgroups per CU");
-};
-// the reference widths keep the sizes they had (a reference handle also serves the DDPG / TD3 calls: Wide fits in SacLay)
-static_assert(ArchDims<ArchReference>::SCRATCH_ROWS == SAC_SCRATCH_ROWS && ArchDims<ArchReference>::PARTIAL == SAC_PARTIAL_LEN &&
-              ArchDims<ArchReference>::LDS == SAC_LDS_FLOATS && ArchDims<ArchReference>::ROW_LEN == SAC_ROW_LEN &&
-              ArchDims<ArchReference>::TWIN_ROW_LEN == TWIN_LEN, "the reference architecture's sizes are unchanged");
+// (the scratch layouts Layout / Wide / Narrow and what a handle allocates of them: brs_ddpg_learner.hpp; brs_sac.hpp: ArchDims, handle_size)
+using brs::sac::SAC_TAIL, brs::sac::ArchDims;
 
 struct Scratch {
   float* base;
@@ -107,6 +72,7 @@ __device__ __forceinline__ float* column(const Scratch& s, int first_row, int i)
 #define UNIFORM_UNIT(mt, r) (32 * (mt) + 8 * ((r) >> 2) + ((r) & 3))
 
 __device__ __forceinline__ bool bit(const uint32_t* g, int mt, int r) { return (g[mt >> 1] >> (16 * (mt & 1) + r)) & 1u; }
+__device__ __forceinline__ void set_gate(uint32_t* g, int mt, int r) { g[mt >> 1] |= 1u << (16 * (mt & 1) + r); }
 
 // what the forward leaves for the backward: the gates as bit masks (tile mt, register r -> bit 16 (mt % 2) + r of word mt / 2), the
 // outputs before the tanh, and, with STORE, the activations in the scratch column of this lane's row
@@ -123,11 +89,11 @@ template <class N, bool STORE, class Lay = Wide> struct Tape {
     for (int k = 0; k < (Tile<N>::MT2 + 1) / 2; k++) g2[k] = 0u;
   }
   __device__ __forceinline__ void h1(int mt, int r, float v) {
-    if (relu_gate(v)) g1[mt >> 1] |= 1u << (16 * (mt & 1) + r);
+    if (relu_gate(v)) set_gate(g1, mt, r);
     if (STORE) h1col[UNIFORM_UNIT(mt, r) * ld] = v;
   }
   __device__ __forceinline__ void h2(int mt, int r, float v) {
-    if (relu_gate(v)) g2[mt >> 1] |= 1u << (16 * (mt & 1) + r);
+    if (relu_gate(v)) set_gate(g2, mt, r);
     if (STORE) h2col[UNIFORM_UNIT(mt, r) * ld] = v;
   }
   __device__ __forceinline__ void pre_out(int k, float s) { pre[k] = s; }
@@ -219,7 +185,7 @@ template <class Q, class Lay> __global__ void __launch_bounds__(THREADS) ddpg_cr
   Tape<Q, true, Lay> tape(S, i);
   forward_tile<Q>(critic, L, xb, v, tape);
   CriticHead hd = {0.0f, 0.0f, 0.0f};
-  if (i < m) hd = brs::sac::scale_head(critic_head(v[0], y[i], 1.0f / (float)m), loss_scale);  // 1 (exact) but for SAC's 0.5
+  if (i < m) hd = scale_head(critic_head(v[0], y[i], 1.0f / (float)m), loss_scale);  // 1 (exact) but for SAC's 0.5
   if (finishes_row()) {
     S.row(Lay::Z3)[i] = hd.dq;
     S.row(Lay::Z3 + 1)[i] = hd.loss;
@@ -231,7 +197,7 @@ template <class Q, class Lay> __global__ void __launch_bounds__(THREADS) ddpg_cr
 
 __global__ void __launch_bounds__(THREADS) ddpg_actor_backward_kernel(const float* __restrict__ actor, const float* __restrict__ critic, const int m,
                                                                       const float* __restrict__ obs, const Scratch S) {
-  __shared__ float L[LDS_FLOATS];
+  __shared__ float L[lds_floats<Actor, Critic>()];
   const int i = tile_row();
   float sb[OBS / 2], mu[ACT], v[1], a[ACT], ga[ACT];
   load_obs_operands(obs, m, i, sb);
@@ -268,7 +234,7 @@ template <class A> __global__ void __launch_bounds__(THREADS) sac_actor_backward
   using Pi = typename A::Pi;
   using Qf = typename A::Qf;
   using PiLay = typename ArchDims<A>::PiLay;
-  __shared__ float L[ArchDims<A>::LDS];
+  __shared__ float L[lds_floats<Pi, Qf>()];
   const int i = tile_row();
   const float* __restrict__ critic1 = critics + nparam<Qf>();
   float sb[OBS / 2], out[Pi::OUT], z[ACT], q0[1], q1[1];
@@ -324,12 +290,12 @@ template <class A> __global__ void __launch_bounds__(THREADS) sac_actor_tail_ker
   for (int mt = 0; mt < T::MT1; mt++)
 #pragma unroll
     for (int r = 0; r < 16; r++)
-      if (relu_gate(h1col[UNIFORM_UNIT(mt, r) * S.ld])) ta.g1[mt >> 1] |= 1u << (16 * (mt & 1) + r);
+      if (relu_gate(h1col[UNIFORM_UNIT(mt, r) * S.ld])) set_gate(ta.g1, mt, r);
 #pragma unroll
   for (int mt = 0; mt < T::MT2; mt++)
 #pragma unroll
     for (int r = 0; r < 16; r++)
-      if (relu_gate(h2col[UNIFORM_UNIT(mt, r) * S.ld])) ta.g2[mt >> 1] |= 1u << (16 * (mt & 1) + r);
+      if (relu_gate(h2col[UNIFORM_UNIT(mt, r) * S.ld])) set_gate(ta.g2, mt, r);
   float dz3[Pi::OUT];
 #pragma unroll
   for (int k = 0; k < Pi::OUT; k++) dz3[k] = S.row(PiLay::Z3 + k)[i];
@@ -479,14 +445,23 @@ struct brs_ddpg_learner {
   std::string err;
 };
 
-using brs::host::DeviceGuard, brs::host::fail;
-
-// the DDPG / TD3 calls exist at the reference widths only
-#define BRS_REFERENCE_ARCH_ONLY(l, who)                                                                                                  \
-  if ((l)->arch != BRS_ARCH_REFERENCE)                                                                                                   \
-    return fail(l, BRS_ERR_ARG, who ": the handle's architecture does not serve this call (DDPG and TD3 run at BRS_ARCH_REFERENCE only)")
+using brs::host::DeviceGuard, brs::host::fail, brs::host::launch_on;
 
 namespace {
+
+// what a gradient call needs of its handle, in the order the ABI checks it: the reference widths, a twin handle, a SAC handle, m rows
+enum : unsigned { REFERENCE_ARCH = 1, TWIN = 2, SAC = 4 };
+struct Needs {
+  int m;
+  unsigned of_handle;
+  const char* operator()(const brs_ddpg_learner* l) const {
+    if (of_handle & REFERENCE_ARCH)
+      if (const char* why = BRS_REFERENCE_ARCH_ONLY(l)) return why;
+    if ((of_handle & TWIN) && !l->twin) return "the handle was not created with brs_ddpg_learner_create_twin";
+    if ((of_handle & SAC) && !l->sac) return "the handle was not created with brs_ddpg_learner_create_sac";
+    return m > l->max_batch ? "m exceeds the handle's max_batch" : nullptr;
+  }
+};
 
 // the scratch view, the split of m rows and the launches after a backward kernel
 template <class N, class Lay = Wide, int NETS = 1, int NS = NSTAT> void launch_weight_kernels(brs_ddpg_learner* l, int m, const float* obs, const float* act, float* grad, hipStream_t s) {
@@ -501,22 +476,12 @@ template <class N, class Lay = Wide, int NETS = 1, int NS = NSTAT> void launch_w
   if (nsplit > 1) hipLaunchKernelGGL(ddpg_combine_kernel, dim3((len + 255) / 256), dim3(256), 0, s, l->partial, nsplit, len, grad);
 }
 
-// the launches of the two SAC gradient calls for architecture A
-template <class A> void sac_twin_critic_launch(brs_ddpg_learner* l, const float* critics, int m, const float* obs, const float* act, const float* y,
-                                               float* grad, hipStream_t s) {
-  using Qf = typename A::Qf;
-  using QfLay = typename ArchDims<A>::QfLay;
-  hipLaunchKernelGGL((ddpg_critic_backward_kernel<Qf, QfLay>), dim3(pad128(m) / WG_ROWS, 2), dim3(THREADS), 0, s, critics, m, obs, act, y,
-                     Scratch{l->block, l->ld}, 0.5f);
-  launch_weight_kernels<Qf, QfLay, 2>(l, m, obs, act, grad, s);
-}
-template <class A> void sac_actor_launch(brs_ddpg_learner* l, const float* actor, const float* critics, int m, const float* obs, uint64_t seed,
-                                         uint32_t draw, int learn_alpha, float target_entropy, float* grad, hipStream_t s) {
-  using PiLay = typename ArchDims<A>::PiLay;
-  hipLaunchKernelGGL(sac_actor_backward_kernel<A>, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, actor, critics, m, obs, seed, draw, learn_alpha,
-                     target_entropy, Scratch{l->block, l->ld});
-  hipLaunchKernelGGL(sac_actor_tail_kernel<A>, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, actor, Scratch{l->block, l->ld});
-  launch_weight_kernels<typename A::Pi, PiLay, 1, SAC_TAIL>(l, m, obs, nullptr, grad, s);
+// the gradient of loss_scale mse(Q(s, a), y) for NETS critics Q laid back to back, each in a scratch image of layout Lay
+template <class Q, class Lay, int NETS> void launch_critic_grad(brs_ddpg_learner* l, const float* critics, int m, const float* obs, const float* act,
+                                                                const float* y, float* grad, hipStream_t s, float loss_scale) {
+  hipLaunchKernelGGL((ddpg_critic_backward_kernel<Q, Lay>), dim3(pad128(m) / WG_ROWS, NETS), dim3(THREADS), 0, s, critics, m, obs, act, y,
+                     Scratch{l->block, l->ld}, loss_scale);
+  launch_weight_kernels<Q, Lay, NETS>(l, m, obs, act, grad, s);
 }
 
 int create(const char* who, bool twin, bool sac, int32_t device, int32_t max_batch, brs_ddpg_learner** out, int32_t arch = BRS_ARCH_REFERENCE) {
@@ -536,10 +501,8 @@ int create(const char* who, bool twin, bool sac, int32_t device, int32_t max_bat
   l->twin = twin;
   l->sac = sac;
   l->arch = arch;
-  const bool wide = arch == BRS_ARCH_SAC_DEFAULT;  // (only with sac)
-  const size_t scratch = (size_t)(wide ? ArchDims<ArchSacDefault>::SCRATCH_ROWS : sac ? SAC_SCRATCH_ROWS : twin ? TWIN_SCRATCH_ROWS : SCRATCH_ROWS) * l->ld,
-               partial = wide ? (size_t)MAX_SPLIT * ArchDims<ArchSacDefault>::PARTIAL : sac ? (size_t)MAX_SPLIT * SAC_PARTIAL_LEN : partial_floats(twin),
-               bytes = (scratch + partial) * sizeof(float);
+  const brs::sac::HandleSize size = brs::sac::handle_size(twin, sac, arch);
+  const size_t scratch = (size_t)size.scratch_rows * l->ld, partial = (size_t)MAX_SPLIT * size.partial_len, bytes = (scratch + partial) * sizeof(float);
   if (hipMalloc((void**)&l->block, bytes) != hipSuccess || hipMemset(l->block, 0, bytes) != hipSuccess) {
     if (l->block) (void)hipFree(l->block);
     delete l;
@@ -596,17 +559,9 @@ int brs_ddpg_learner_critic_grad(brs_ddpg_learner* l, const float* critic_dev, i
   // what needs no handle is checked first (fail() records it in the family's slot when there is none)
   if (!critic_dev || !obs_dev || !act_dev || !y_dev || !grad_dev) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_critic_grad: null argument");
   if (m < 1) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_critic_grad: m must be at least 1");
-  if (!l) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_critic_grad: null handle");
-  BRS_REFERENCE_ARCH_ONLY(l, "brs_ddpg_learner_critic_grad");
-  if (m > l->max_batch) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_critic_grad: m exceeds the handle's max_batch");
-  DeviceGuard g(l->device);
-  if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_ddpg_learner_critic_grad: hipSetDevice failed");
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((ddpg_critic_backward_kernel<Critic, Wide>), dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, critic_dev, m, obs_dev, act_dev, y_dev,
-                     Scratch{l->block, l->ld}, 1.0f);
-  launch_weight_kernels<Critic>(l, m, obs_dev, act_dev, grad_dev, s);
-  BRS_HIP_TRY(l, hipGetLastError());
-  return BRS_OK;
+  return launch_on(l, "brs_ddpg_learner_critic_grad", Needs{m, REFERENCE_ARCH}, [&] {
+    launch_critic_grad<Critic, Wide, 1>(l, critic_dev, m, obs_dev, act_dev, y_dev, grad_dev, (hipStream_t)stream, 1.0f);
+  });
 }
 
 int brs_ddpg_learner_twin_critic_grad(brs_ddpg_learner* l, const float* critics_dev, int32_t m, const float* obs_dev, const float* act_dev,
@@ -614,83 +569,61 @@ int brs_ddpg_learner_twin_critic_grad(brs_ddpg_learner* l, const float* critics_
   if (!critics_dev || !obs_dev || !act_dev || !y_dev || !grad_dev)
     return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: null argument");
   if (m < 1) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: m must be at least 1");
-  if (!l) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: null handle");
-  BRS_REFERENCE_ARCH_ONLY(l, "brs_ddpg_learner_twin_critic_grad");
-  if (!l->twin)
-    return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: the handle was not created with brs_ddpg_learner_create_twin");
-  if (m > l->max_batch) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_twin_critic_grad: m exceeds the handle's max_batch");
-  DeviceGuard g(l->device);
-  if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_ddpg_learner_twin_critic_grad: hipSetDevice failed");
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((ddpg_critic_backward_kernel<Critic, Narrow>), dim3(pad128(m) / WG_ROWS, 2), dim3(THREADS), 0, s, critics_dev, m, obs_dev,
-                     act_dev, y_dev, Scratch{l->block, l->ld}, 1.0f);
-  launch_weight_kernels<Critic, Narrow, 2>(l, m, obs_dev, act_dev, grad_dev, s);
-  BRS_HIP_TRY(l, hipGetLastError());
-  return BRS_OK;
+  return launch_on(l, "brs_ddpg_learner_twin_critic_grad", Needs{m, REFERENCE_ARCH | TWIN}, [&] {
+    launch_critic_grad<Critic, Narrow, 2>(l, critics_dev, m, obs_dev, act_dev, y_dev, grad_dev, (hipStream_t)stream, 1.0f);
+  });
 }
 
 int brs_sac_twin_critic_grad(brs_ddpg_learner* l, const float* critics_dev, int32_t m, const float* obs_dev, const float* act_dev, const float* y_dev,
                              float* grad_dev, void* stream) {
   if (const char* why = brs::sac::sac_critic_grad_argument_error(critics_dev, m, obs_dev, act_dev, y_dev, grad_dev))
     return fail(l, BRS_ERR_ARG, std::string("brs_sac_twin_critic_grad: ") + why);
-  if (!l) return fail(l, BRS_ERR_ARG, "brs_sac_twin_critic_grad: null handle");
-  if (!l->sac) return fail(l, BRS_ERR_ARG, "brs_sac_twin_critic_grad: the handle was not created with brs_ddpg_learner_create_sac");
-  if (m > l->max_batch) return fail(l, BRS_ERR_ARG, "brs_sac_twin_critic_grad: m exceeds the handle's max_batch");
-  DeviceGuard g(l->device);
-  if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_sac_twin_critic_grad: hipSetDevice failed");
-  hipStream_t s = (hipStream_t)stream;
-  if (l->arch == BRS_ARCH_SAC_DEFAULT) sac_twin_critic_launch<ArchSacDefault>(l, critics_dev, m, obs_dev, act_dev, y_dev, grad_dev, s);
-  else sac_twin_critic_launch<ArchReference>(l, critics_dev, m, obs_dev, act_dev, y_dev, grad_dev, s);
-  BRS_HIP_TRY(l, hipGetLastError());
-  return BRS_OK;
+  return launch_on(l, "brs_sac_twin_critic_grad", Needs{m, SAC}, [&] {
+    brs::sac::with_arch(l->arch, [&](auto a) {
+      using A = decltype(a);
+      launch_critic_grad<typename A::Qf, typename ArchDims<A>::QfLay, 2>(l, critics_dev, m, obs_dev, act_dev, y_dev, grad_dev, (hipStream_t)stream, 0.5f);
+    });
+  });
 }
 
 int brs_sac_actor_grad(brs_ddpg_learner* l, const float* actor_dev, const float* critics_dev, int32_t m, const float* obs_dev, uint64_t seed,
                        uint32_t draw, int32_t learn_alpha, float target_entropy, float* grad_dev, void* stream) {
   if (const char* why = brs::sac::sac_actor_grad_argument_error(actor_dev, critics_dev, m, obs_dev, target_entropy, grad_dev))
     return fail(l, BRS_ERR_ARG, std::string("brs_sac_actor_grad: ") + why);
-  if (!l) return fail(l, BRS_ERR_ARG, "brs_sac_actor_grad: null handle");
-  if (!l->sac) return fail(l, BRS_ERR_ARG, "brs_sac_actor_grad: the handle was not created with brs_ddpg_learner_create_sac");
-  if (m > l->max_batch) return fail(l, BRS_ERR_ARG, "brs_sac_actor_grad: m exceeds the handle's max_batch");
-  DeviceGuard g(l->device);
-  if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_sac_actor_grad: hipSetDevice failed");
-  hipStream_t s = (hipStream_t)stream;
-  if (l->arch == BRS_ARCH_SAC_DEFAULT)
-    sac_actor_launch<ArchSacDefault>(l, actor_dev, critics_dev, m, obs_dev, seed, draw, learn_alpha != 0, target_entropy, grad_dev, s);
-  else
-    sac_actor_launch<ArchReference>(l, actor_dev, critics_dev, m, obs_dev, seed, draw, learn_alpha != 0, target_entropy, grad_dev, s);
-  BRS_HIP_TRY(l, hipGetLastError());
-  return BRS_OK;
+  return launch_on(l, "brs_sac_actor_grad", Needs{m, SAC}, [&] {
+    brs::sac::with_arch(l->arch, [&](auto a) {
+      using A = decltype(a);
+      using PiLay = typename ArchDims<A>::PiLay;
+      hipStream_t s = (hipStream_t)stream;
+      const dim3 grid(pad128(m) / WG_ROWS);
+      hipLaunchKernelGGL(sac_actor_backward_kernel<A>, grid, dim3(THREADS), 0, s, actor_dev, critics_dev, m, obs_dev, seed, draw, learn_alpha != 0,
+                         target_entropy, Scratch{l->block, l->ld});
+      hipLaunchKernelGGL(sac_actor_tail_kernel<A>, grid, dim3(THREADS), 0, s, actor_dev, Scratch{l->block, l->ld});
+      launch_weight_kernels<typename A::Pi, PiLay, 1, SAC_TAIL>(l, m, obs_dev, nullptr, grad_dev, s);
+    });
+  });
 }
 
 int brs_ddpg_learner_actor_grad(brs_ddpg_learner* l, const float* actor_dev, const float* critic_dev, int32_t m, const float* obs_dev,
                                 float* grad_dev, void* stream) {
   if (!actor_dev || !critic_dev || !obs_dev || !grad_dev) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_actor_grad: null argument");
   if (m < 1) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_actor_grad: m must be at least 1");
-  if (!l) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_actor_grad: null handle");
-  BRS_REFERENCE_ARCH_ONLY(l, "brs_ddpg_learner_actor_grad");
-  if (m > l->max_batch) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_actor_grad: m exceeds the handle's max_batch");
-  DeviceGuard g(l->device);
-  if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_ddpg_learner_actor_grad: hipSetDevice failed");
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ddpg_actor_backward_kernel, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, actor_dev, critic_dev, m, obs_dev,
-                     Scratch{l->block, l->ld});
-  launch_weight_kernels<Actor>(l, m, obs_dev, nullptr, grad_dev, s);
-  BRS_HIP_TRY(l, hipGetLastError());
-  return BRS_OK;
+  return launch_on(l, "brs_ddpg_learner_actor_grad", Needs{m, REFERENCE_ARCH}, [&] {
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ddpg_actor_backward_kernel, dim3(pad128(m) / WG_ROWS), dim3(THREADS), 0, s, actor_dev, critic_dev, m, obs_dev,
+                       Scratch{l->block, l->ld});
+    launch_weight_kernels<Actor>(l, m, obs_dev, nullptr, grad_dev, s);
+  });
 }
 
 int brs_ddpg_learner_apply(brs_ddpg_learner* l, int32_t n_param, float* params_dev, const float* grad_dev, float* m_dev, float* v_dev,
                            float* target_dev, const brs_adam_config* cfg, int64_t step, float tau, void* stream) {
   if (const char* why = apply_argument_error(n_param, params_dev, grad_dev, m_dev, v_dev, cfg, step, tau))
     return fail(l, BRS_ERR_ARG, std::string("brs_ddpg_learner_apply: ") + why);
-  if (!l) return fail(l, BRS_ERR_ARG, "brs_ddpg_learner_apply: null handle");
-  DeviceGuard g(l->device);
-  if (!g.ok) return fail(l, BRS_ERR_HIP, "brs_ddpg_learner_apply: hipSetDevice failed");
-  hipLaunchKernelGGL(ddpg_apply_kernel, dim3((unsigned)(((int64_t)n_param + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_param, params_dev,
-                     grad_dev, m_dev, v_dev, target_dev, adam_scalars(*cfg, step), tau);
-  BRS_HIP_TRY(l, hipGetLastError());
-  return BRS_OK;
+  return launch_on(l, "brs_ddpg_learner_apply", brs::host::needs_nothing, [&] {
+    hipLaunchKernelGGL(ddpg_apply_kernel, dim3((unsigned)(((int64_t)n_param + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_param, params_dev,
+                       grad_dev, m_dev, v_dev, target_dev, adam_scalars(*cfg, step), tau);
+  });
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "brs_offpolicy.hpp"  // Actor, Critic, Offsets, nparam
@@ -28,11 +29,28 @@ constexpr int MAX_SPLIT = 8, SPLIT_ROWS = 256;
 constexpr int pad128(int x) { return (x + 127) / 128 * 128; }
 constexpr int TWIN_LEN = 2 * nparam<Critic>() + BRS_TD3_NSTAT;  // the twin gradient buffer / a twin partial row
 static_assert(BRS_TD3_NSTAT == 2 * NSTAT, "two statistics per critic");
-// a partial row holds the longest row a call writes: the actor's in the single calls, two critics side by side in the twin call
-constexpr int PARTIAL_LEN = row_len<Actor>(), TWIN_PARTIAL_LEN = TWIN_LEN > row_len<Actor>() ? TWIN_LEN : row_len<Actor>();
-static_assert(row_len<Critic>() <= PARTIAL_LEN, "the critic's row fits a partial row");
-// floats the handle keeps for partial rows, behind its scratch rows
-constexpr size_t partial_floats(bool twin) { return (size_t)MAX_SPLIT * (twin ? TWIN_PARTIAL_LEN : PARTIAL_LEN); }
+static_assert(row_len<Critic>() <= row_len<Actor>(), "the critic's row fits the actor's partial row");
+// rows of a scratch image (each `ld` floats, ld = max_batch padded to the workgroup's 128 rows) sized for network N: the two hidden
+// layers' activations and their gradients in [unit][sample] layout, then ZR per-sample rows.  The single calls use the actor's, the
+// wider net, for both networks; the twin calls keep two images of the critic's back to back.  What a handle allocates of them:
+// handle_size of brs_sac.hpp.
+template <class N, int ZR = Z3_ROWS> struct Layout {
+  static constexpr int H1 = 0, H2 = H1 + Padded<N>::H1P, DZ1 = H2 + Padded<N>::H2P, DZ2 = DZ1 + Padded<N>::H1P, Z3 = DZ2 + Padded<N>::H2P, ROWS = Z3 + ZR;
+};
+using Wide = Layout<Actor>;
+using Narrow = Layout<Critic>;
+static_assert(Padded<Critic>::H1P <= Padded<Actor>::H1P && Padded<Critic>::H2P <= Padded<Actor>::H2P, "the critic fits in the actor's scratch");
+// ---- the sizing table of a learner handle (brs_ddpg_learner.hip: create): scratch rows (each max_batch padded to 128 floats) and the
+// length of each of the MAX_SPLIT partial rows behind them -- the largest image and the longest row of any call the handle serves.
+//   single (brs_ddpg_learner_create)  the actor's image serves both networks; the actor's row
+//   twin   (..._create_twin)          that, or two critic images back to back; that, or two critics side by side in a row
+//   sac    (..._create_sac[_arch])    brs_sac.hpp: handle_size, which is what create() calls
+struct HandleSize { int scratch_rows, partial_len; };
+constexpr HandleSize ddpg_handle_size(bool twin) {
+  return twin ? HandleSize{std::max(Wide::ROWS, 2 * Narrow::ROWS), std::max(row_len<Actor>(), TWIN_LEN)} : HandleSize{Wide::ROWS, row_len<Actor>()};
+}
+// floats such a handle keeps for partial rows (the host build's sweep of the split holds every m against it)
+constexpr size_t partial_floats(bool twin) { return (size_t)MAX_SPLIT * ddpg_handle_size(twin).partial_len; }
 
 struct SampleSplit { int mp, span, nsplit; };  // samples padded to 128; samples per split (a multiple of 128); splits launched
 inline SampleSplit sample_split(int m) {
@@ -177,22 +195,41 @@ template <class N> inline void backward_row(const float* w, const RowTape<N>& t,
     }
 }
 
+// the loss head with a factor in front of the loss (SAC's 0.5, a power of two: exact; the DDPG / TD3 calls pass 1, exact too)
+BRS_HD CriticHead scale_head(CriticHead h, float loss_scale) { return CriticHead{h.dq * loss_scale, h.loss * loss_scale, h.q}; }
+
+// the rows of loss_scale mse(Q(s, a), y) for critic Q, summed into g[nparam<Q>() + NSTAT]: the gradient, then the loss and mean Q
+template <class Q> inline void critic_grad_rows(const float* critic, int m, const float* obs, const float* act, const float* y, float loss_scale,
+                                                double* g) {
+  const float inv_m = 1.0f / (float)m;
+  RowTape<Q> t;
+  for (int i = 0; i < m; i++) {
+    float x[Q::IN];
+    for (int k = 0; k < OBS; k++) x[k] = obs[(size_t)OBS * i + k];
+    for (int k = 0; k < ACT; k++) x[OBS + k] = act[(size_t)ACT * i + k];
+    forward_row_keep<Q>(critic, x, t);
+    const CriticHead hd = scale_head(critic_head(t.pre[0], y[i], inv_m), loss_scale);
+    backward_row<Q>(critic, t, &hd.dq, g, nullptr);
+    g[nparam<Q>()] += (double)hd.loss;
+    g[nparam<Q>() + 1] += (double)hd.q;
+  }
+}
 // grad[NCRITIC + 2]
 inline void critic_grad_host(const float* critic, int m, const float* obs, const float* act, const float* y, float* grad) {
   std::vector<double> g((size_t)row_len<Critic>(), 0.0);
-  const float inv_m = 1.0f / (float)m;
-  RowTape<Critic> t;
-  for (int i = 0; i < m; i++) {
-    float x[Critic::IN];
-    for (int k = 0; k < OBS; k++) x[k] = obs[(size_t)OBS * i + k];
-    for (int k = 0; k < ACT; k++) x[OBS + k] = act[(size_t)ACT * i + k];
-    forward_row_keep<Critic>(critic, x, t);
-    const CriticHead hd = critic_head(t.pre[0], y[i], inv_m);
-    backward_row<Critic>(critic, t, &hd.dq, g.data(), nullptr);
-    g[nparam<Critic>()] += (double)hd.loss;
-    g[nparam<Critic>() + 1] += (double)hd.q;
-  }
+  critic_grad_rows<Critic>(critic, m, obs, act, y, 1.0f, g.data());
   for (int j = 0; j < row_len<Critic>(); j++) grad[j] = (float)g[j];
+}
+// grad[2 nparam<Q>() + 4]: block 0, block 1, then (loss, mean Q) of critic 0 and of critic 1
+template <class Q> inline void twin_critic_grad_host(const float* critics, int m, const float* obs, const float* act, const float* y,
+                                                     float loss_scale, float* grad) {
+  constexpr int NC = nparam<Q>();
+  for (int c = 0; c < 2; c++) {
+    std::vector<double> g((size_t)NC + NSTAT, 0.0);
+    critic_grad_rows<Q>(critics + (size_t)c * NC, m, obs, act, y, loss_scale, g.data());
+    for (int j = 0; j < NC; j++) grad[(size_t)c * NC + j] = (float)g[j];
+    for (int j = 0; j < NSTAT; j++) grad[2 * (size_t)NC + (size_t)c * NSTAT + j] = (float)g[NC + j];
+  }
 }
 
 // grad[NACTOR + 2]

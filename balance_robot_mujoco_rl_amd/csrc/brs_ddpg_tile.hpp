@@ -11,6 +11,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "brs_offpolicy.hpp"
 
 namespace brs {
@@ -21,13 +23,12 @@ using namespace brs::offpolicy;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int THREADS = 256, WAVE_ROWS = 32, WG_ROWS = WAVE_ROWS * (THREADS / 64);
-constexpr int pad32(int x) { return (x + 31) / 32 * 32; }
 
 // unit (inside its M-tile) held by accumulator register r in half h of the wave (a local `h` at the place of use)
 #define BRS_UNIT(r) (8 * ((r) >> 2) + 4 * h + ((r) & 3))
 
 template <class N> struct Tile {
-  static constexpr int H1P = pad32(N::H1), H2P = pad32(N::H2), MT1 = H1P / 32, MT2 = H2P / 32;
+  static constexpr int H1P = Padded<N>::H1P, H2P = Padded<N>::H2P, MT1 = H1P / 32, MT2 = H2P / 32;
   static constexpr int W1_LD = N::IN + 1, CH_LD = 33;  // odd strides: no bank conflict between the 32 units of an M-tile
   static constexpr int KSTEPS1 = N::IN / 2;
   // LDS image (floats): W1 [H1P][W1_LD], b1 [H1P], b2 [H2P], W3 [OUT][H2P], b3 [4], two chunks of W2 [H2P][CH_LD]
@@ -37,7 +38,12 @@ template <class N> struct Tile {
   static_assert(N::IN % 2 == 0 && (H2P * 32) % THREADS == 0, "tiling");
   static_assert(N::OUT >= 1 && N::OUT <= 4, "the image reserves 4 words for b3 (the SAC actor of brs_sac.hpp uses all of them)");
 };
-constexpr int LDS_FLOATS = Tile<Actor>::L_SIZE > Tile<Critic>::L_SIZE ? Tile<Actor>::L_SIZE : Tile<Critic>::L_SIZE;
+// the LDS image of a kernel that walks the networks Nets one after the other: the largest of theirs
+template <class... Nets> constexpr int lds_floats() {
+  constexpr int n = std::max({Tile<Nets>::L_SIZE...});
+  static_assert(2 * n * sizeof(float) <= 160 * 1024, "two workgroups per CU");
+  return n;
+}
 
 // what stays in LDS for the whole forward; padded units and columns are written as zeros
 template <class N> __device__ __forceinline__ void stage_resident(const float* __restrict__ w, float* __restrict__ L) {

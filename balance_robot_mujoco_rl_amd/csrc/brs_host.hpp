@@ -37,6 +37,25 @@ template <class H> const char* last_error(const H* h) { return (h ? h->err : no_
     if (e_ != hipSuccess) return brs::host::fail(h, BRS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
+// The handle-dependent half of an entry point, after the argument checks that need no handle: the null handle, what the call needs
+// of its handle -- `needs(h)` returns nullptr or the text that follows "<who>: " --, the device guard, `launch()`, which enqueues on
+// the caller's stream, and hipGetLastError.  The checks run in this order, which is part of the ABI.
+template <class H, class Needs, class Launch> int launch_on(H* h, const char* who, Needs&& needs, Launch&& launch) {
+  // (a text is put together only where a check fails: a call that succeeds allocates nothing)
+  if (!h) return fail(h, BRS_ERR_ARG, std::string(who) + ": null handle");
+  if (const char* why = needs(h)) return fail(h, BRS_ERR_ARG, std::string(who) + ": " + why);
+  DeviceGuard g(h->device);
+  if (!g.ok) return fail(h, BRS_ERR_HIP, std::string(who) + ": hipSetDevice failed");
+  launch();
+  BRS_HIP_TRY(h, hipGetLastError());
+  return BRS_OK;
+}
+// a call that needs nothing of its handle but its device
+inline const char* needs_nothing(const void*) { return nullptr; }
+// the DDPG / TD3 calls exist at the reference widths only (h->arch: a BRS_ARCH_* of include/brs_policy.h): nullptr, or what launch_on says
+#define BRS_REFERENCE_ARCH_ONLY(h) \
+  ((h)->arch != BRS_ARCH_REFERENCE ? "the handle's architecture does not serve this call (DDPG and TD3 run at BRS_ARCH_REFERENCE only)" : nullptr)
+
 // BRS_OK if `device` is an ordinal of this machine; otherwise the code to return and, in *msg, the text for `who`
 inline int check_device(int device, const char* who, std::string* msg) {
   int ndev = 0;

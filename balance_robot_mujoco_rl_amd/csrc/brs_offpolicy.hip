@@ -32,15 +32,16 @@ namespace {
 
 using namespace brs::offpolicy;
 using namespace brs::ddpg_tile;
-using brs::sac::SacActor, brs::sac::ArchReference, brs::sac::ArchSacDefault;
-constexpr int SAC_LDS_FLOATS = Tile<SacActor>::L_SIZE > LDS_FLOATS ? Tile<SacActor>::L_SIZE : LDS_FLOATS;
-static_assert(Tile<SacActor>::L_SIZE == Tile<Actor>::L_SIZE + 2 * Tile<Actor>::H2P && SAC_LDS_FLOATS * sizeof(float) <= 160 * 1024, "LDS");
-// the LDS image of architecture A's SAC kernels: its actor's and its critic's forwards share it one after the other
-template <class A> constexpr int sac_lds_floats() {
-  return Tile<typename A::Pi>::L_SIZE > Tile<typename A::Qf>::L_SIZE ? Tile<typename A::Pi>::L_SIZE : Tile<typename A::Qf>::L_SIZE;
+using brs::sac::SacActor;
+// (the SAC actor's image is the DDPG actor's with two more rows of the output layer)
+static_assert(Tile<SacActor>::L_SIZE == Tile<Actor>::L_SIZE + 2 * Tile<Actor>::H2P, "LDS");
+
+// row i's ACT words of an output that may be absent
+__device__ __forceinline__ void store_row(float* __restrict__ dst, const int i, const float (&v)[ACT]) {
+  if (!dst) return;
+#pragma unroll
+  for (int k = 0; k < ACT; k++) dst[(size_t)ACT * i + k] = v[k];
 }
-// (two workgroups of the [256, 256] actor's 80,912 bytes still fit a CU's 160 KB)
-static_assert(sac_lds_floats<ArchReference>() == SAC_LDS_FLOATS && 2 * sac_lds_floats<ArchSacDefault>() * sizeof(float) <= 160 * 1024, "LDS");
 
 __global__ void __launch_bounds__(THREADS) ddpg_act_kernel(const float* __restrict__ actor, const int n, const float* __restrict__ obs,
                                                            const uint64_t seed, const int64_t gid_base, const uint32_t step, const float sigma,
@@ -53,12 +54,9 @@ __global__ void __launch_bounds__(THREADS) ddpg_act_kernel(const float* __restri
   if (i >= n || !finishes_row()) return;
   float a[ACT], m[ACT], z[ACT];
   act_tail(seed, gid_base + (int64_t)i, step, sigma, 0, mu, a, m, z);
-#pragma unroll
-  for (int k = 0; k < ACT; k++) {
-    action[(size_t)ACT * i + k] = a[k];
-    if (mean) mean[(size_t)ACT * i + k] = m[k];
-    if (noise) noise[(size_t)ACT * i + k] = z[k];
-  }
+  store_row(action, i, a);
+  store_row(mean, i, m);
+  store_row(noise, i, z);
 }
 
 // the learning_starts phase: no network
@@ -70,12 +68,9 @@ __global__ void __launch_bounds__(256) ddpg_random_kernel(const int n, const uin
   const float none[ACT] = {0.0f, 0.0f};
   float a[ACT], m[ACT], z[ACT];
   act_tail(seed, gid_base + (int64_t)i, step, sigma, 1, none, a, m, z);
-#pragma unroll
-  for (int k = 0; k < ACT; k++) {
-    action[(size_t)ACT * i + k] = a[k];
-    if (mean) mean[(size_t)ACT * i + k] = m[k];
-    if (noise) noise[(size_t)ACT * i + k] = z[k];
-  }
+  store_row(action, i, a);
+  store_row(mean, i, m);
+  store_row(noise, i, z);
 }
 
 template <class Q> __global__ void __launch_bounds__(THREADS) ddpg_q_kernel(const float* __restrict__ critic, const int n, const float* __restrict__ obs,
@@ -89,45 +84,98 @@ template <class Q> __global__ void __launch_bounds__(THREADS) ddpg_q_kernel(cons
   if (i < n && finishes_row()) q[i] = v[0];
 }
 
-// actor' -> concat -> critic' -> combine in one launch; the two forwards share the LDS image one after the other
+// The three targets are one shape: the actor's forward -> the rule's action -> the forwards of the rule's CRITICS target critics, laid
+// back to back -> the rule's combine -> the rule's optional outputs, in one launch; the forwards share the LDS image L one after the
+// other.  A Rule names the networks (Pi, Qf, and PiNet / QfNet as forward_tile is to walk them), and holds the call's scalars and,
+// between action() and store(), what the row's sample left.  Both halves of a wave compute the row's action: it is the B operand of both.
+template <class R> __device__ __forceinline__ void target_body(R rule, float* __restrict__ L, const float* __restrict__ actor,
+                                                               const float* __restrict__ critics, const int m, const float* __restrict__ next_obs,
+                                                               const float* __restrict__ reward, const uint8_t* __restrict__ done, const float gamma,
+                                                               float* __restrict__ y) {
+  const int i = tile_row();
+  float sb[OBS / 2], out[R::Pi::OUT], a[ACT], q[R::CRITICS];
+  load_obs_operands(next_obs, m, i, sb);
+  forward_tile<typename R::PiNet>(actor, L, sb, out);
+  rule.action(i, out, a);
+  const float xb[(OBS + ACT) / 2] = {sb[0], sb[1], sb[2], wave_half() ? a[1] : a[0]};
+#pragma unroll
+  for (int k = 0; k < R::CRITICS; k++) {
+    float v[1];
+    forward_tile<typename R::QfNet>(critics + k * nparam<typename R::Qf>(), L, xb, v);
+    q[k] = v[0];
+  }
+  if (i >= m || !finishes_row()) return;
+  y[i] = rule.combine(reward[i], done[i], gamma, q);
+  rule.store(i, a);
+}
+
+// DDPG: the target actor's action as it is, one critic
+struct DdpgTarget {
+  using Pi = Actor; using Qf = Critic; using PiNet = Actor; using QfNet = Critic;
+  static constexpr int CRITICS = 1;
+  __device__ __forceinline__ void action(int, const float (&mu)[ACT], float (&a)[ACT]) { a[0] = mu[0]; a[1] = mu[1]; }
+  __device__ __forceinline__ float combine(float reward, uint8_t done, float gamma, const float (&q)[1]) const { return td_combine(reward, done, gamma, q[0]); }
+  __device__ __forceinline__ void store(int, const float (&)[ACT]) const {}
+};
+// TD3: smoothing noise and two clamps on the action, the minimum of two critics
+struct Td3Target {
+  using Pi = Actor; using Qf = Critic; using PiNet = Actor; using QfNet = Critic;
+  static constexpr int CRITICS = 2;
+  float policy_noise, noise_clip;
+  uint64_t seed;
+  uint32_t draw;
+  float *next_action, *noise;
+  float z[ACT];
+  __device__ __forceinline__ void action(int i, const float (&mu)[ACT], float (&a)[ACT]) {
+    td3_action_tail(seed, draw, (uint32_t)i, policy_noise, noise_clip, mu, a, z);
+  }
+  __device__ __forceinline__ float combine(float reward, uint8_t done, float gamma, const float (&q)[2]) const {
+    return td3_combine(reward, done, gamma, q[0], q[1]);
+  }
+  __device__ __forceinline__ void store(int i, const float (&a)[ACT]) const { store_row(next_action, i, a); store_row(noise, i, z); }
+};
+// SAC: the CURRENT actor's sample and logp, the minimum of two target critics, the entropy term with alpha =
+// exp(log_ent_coef), the element behind the actor's b3; A: the handle's architecture
+template <class A> struct SacTarget {
+  using Pi = typename A::Pi; using Qf = typename A::Qf; using PiNet = typename SeriesOf<A>::Pi; using QfNet = typename SeriesOf<A>::Qf;
+  static constexpr int CRITICS = 2;
+  const float* actor;
+  uint64_t seed;
+  uint32_t draw;
+  float *next_action, *logp, *noise;
+  float z[ACT];
+  brs::sac::Sample sm;
+  __device__ __forceinline__ void action(int i, const float (&out)[Pi::OUT], float (&a)[ACT]) {
+    uint32_t o[4];
+    brs::sac::sac_row_block(BRS_SAC_TAG_TARGET, seed, draw, (uint32_t)i, o);
+    normal_pair(o[0], o[1], z);
+    brs::sac::sample(out, z, sm);
+    a[0] = sm.a[0]; a[1] = sm.a[1];
+  }
+  __device__ __forceinline__ float combine(float reward, uint8_t done, float gamma, const float (&q)[2]) const {
+    return brs::sac::sac_combine(reward, done, gamma, q[0], q[1], brs::sac::ent_coef_of<Pi>(actor), sm.logp);
+  }
+  __device__ __forceinline__ void store(int i, const float (&a)[ACT]) const {
+    if (logp) logp[i] = sm.logp;
+    store_row(next_action, i, a);
+    store_row(noise, i, z);
+  }
+};
+
 __global__ void __launch_bounds__(THREADS) ddpg_td_target_kernel(const float* __restrict__ actor_t, const float* __restrict__ critic_t, const int m,
                                                                  const float* __restrict__ next_obs, const float* __restrict__ reward,
                                                                  const uint8_t* __restrict__ done, const float gamma, float* __restrict__ y) {
-  __shared__ float L[LDS_FLOATS];
-  const int i = tile_row();
-  float sb[OBS / 2], a[ACT], v[1];
-  load_obs_operands(next_obs, m, i, sb);
-  forward_tile<Actor>(actor_t, L, sb, a);
-  const float a_mine = wave_half() ? a[1] : a[0];
-  const float xb[(OBS + ACT) / 2] = {sb[0], sb[1], sb[2], a_mine};
-  forward_tile<Critic>(critic_t, L, xb, v);
-  if (i < m && finishes_row()) y[i] = td_combine(reward[i], done[i], gamma, v[0]);
+  __shared__ float L[lds_floats<Actor, Critic>()];
+  target_body(DdpgTarget{}, L, actor_t, critic_t, m, next_obs, reward, done, gamma, y);
 }
 
-// TD3's target: actor' -> smoothing noise, two clamps -> critic 0' -> critic 1' -> minimum -> combine in one launch;
-// the three forwards share the LDS image one after the other.  Both halves of a wave compute the row's Philox block: the action
-// is the B operand of both.
 __global__ void __launch_bounds__(THREADS) td3_td_target_kernel(const float* __restrict__ actor_t, const float* __restrict__ critics_t, const int m,
                                                                 const float* __restrict__ next_obs, const float* __restrict__ reward,
                                                                 const uint8_t* __restrict__ done, const float gamma, const float policy_noise,
                                                                 const float noise_clip, const uint64_t seed, const uint32_t draw,
                                                                 float* __restrict__ y, float* __restrict__ next_action, float* __restrict__ noise) {
-  __shared__ float L[LDS_FLOATS];
-  const int i = tile_row();
-  float sb[OBS / 2], mu[ACT], a[ACT], z[ACT], q1[1], q2[1];
-  load_obs_operands(next_obs, m, i, sb);
-  forward_tile<Actor>(actor_t, L, sb, mu);
-  td3_action_tail(seed, draw, (uint32_t)i, policy_noise, noise_clip, mu, a, z);
-  const float xb[(OBS + ACT) / 2] = {sb[0], sb[1], sb[2], wave_half() ? a[1] : a[0]};
-  forward_tile<Critic>(critics_t, L, xb, q1);
-  forward_tile<Critic>(critics_t + nparam<Critic>(), L, xb, q2);
-  if (i >= m || !finishes_row()) return;
-  y[i] = td3_combine(reward[i], done[i], gamma, q1[0], q2[0]);
-#pragma unroll
-  for (int k = 0; k < ACT; k++) {
-    if (next_action) next_action[(size_t)ACT * i + k] = a[k];
-    if (noise) noise[(size_t)ACT * i + k] = z[k];
-  }
+  __shared__ float L[lds_floats<Actor, Critic>()];
+  target_body(Td3Target{policy_noise, noise_clip, seed, draw, next_action, noise}, L, actor_t, critics_t, m, next_obs, reward, done, gamma, y);
 }
 
 // SAC's actor: the forward with four outputs, then the per-row tail of brs_sac.hpp; A: the handle's architecture
@@ -146,13 +194,10 @@ template <class A> __global__ void __launch_bounds__(THREADS) sac_act_kernel(con
   if (i >= n || !finishes_row()) return;
   float a[ACT], m[ACT], ls[ACT], z[ACT];
   brs::sac::sac_act_tail(seed, gid_base + (int64_t)i, step, deterministic, 0, out, a, m, ls, z);
-#pragma unroll
-  for (int k = 0; k < ACT; k++) {
-    action[(size_t)ACT * i + k] = a[k];
-    if (mu) mu[(size_t)ACT * i + k] = m[k];
-    if (log_std) log_std[(size_t)ACT * i + k] = ls[k];
-    if (noise) noise[(size_t)ACT * i + k] = z[k];
-  }
+  store_row(action, i, a);
+  store_row(mu, i, m);
+  store_row(log_std, i, ls);
+  store_row(noise, i, z);
 }
 
 __global__ void __launch_bounds__(256) sac_random_kernel(const int n, const uint64_t seed, const int64_t gid_base, const uint32_t step,
@@ -163,47 +208,20 @@ __global__ void __launch_bounds__(256) sac_random_kernel(const int n, const uint
   const float none[SacActor::OUT] = {0.0f, 0.0f, 0.0f, 0.0f};
   float a[ACT], m[ACT], ls[ACT], z[ACT];
   brs::sac::sac_act_tail(seed, gid_base + (int64_t)i, step, 0, 1, none, a, m, ls, z);
-#pragma unroll
-  for (int k = 0; k < ACT; k++) {
-    action[(size_t)ACT * i + k] = a[k];
-    if (mu) mu[(size_t)ACT * i + k] = m[k];
-    if (log_std) log_std[(size_t)ACT * i + k] = ls[k];
-    if (noise) noise[(size_t)ACT * i + k] = z[k];
-  }
+  store_row(action, i, a);
+  store_row(mu, i, m);
+  store_row(log_std, i, ls);
+  store_row(noise, i, z);
 }
 
-// SAC's target: the CURRENT actor -> sample and logp -> target critic 0 -> target critic 1 -> minimum, entropy term, combine in one
-// launch; the three forwards share the LDS image one after the other.  alpha = exp(log_ent_coef), the element behind the actor's b3,
-// is read here.
 template <class A> __global__ void __launch_bounds__(THREADS) sac_td_target_kernel(const float* __restrict__ actor, const float* __restrict__ critics_t,
                                                                                   const int m, const float* __restrict__ next_obs,
                                                                                   const float* __restrict__ reward, const uint8_t* __restrict__ done,
                                                                                   const float gamma, const uint64_t seed, const uint32_t draw,
                                                                                   float* __restrict__ y, float* __restrict__ next_action,
                                                                                   float* __restrict__ logp, float* __restrict__ noise) {
-  using Pi = typename A::Pi;
-  using Qf = typename A::Qf;
-  __shared__ float L[sac_lds_floats<A>()];
-  const int i = tile_row();
-  float sb[OBS / 2], out[Pi::OUT], z[ACT], q1[1], q2[1];
-  load_obs_operands(next_obs, m, i, sb);
-  forward_tile<typename SeriesOf<A>::Pi>(actor, L, sb, out);
-  uint32_t o[4];
-  brs::sac::sac_row_block(BRS_SAC_TAG_TARGET, seed, draw, (uint32_t)i, o);
-  normal_pair(o[0], o[1], z);
-  brs::sac::Sample sm;
-  brs::sac::sample(out, z, sm);
-  const float xb[(OBS + ACT) / 2] = {sb[0], sb[1], sb[2], wave_half() ? sm.a[1] : sm.a[0]};
-  forward_tile<typename SeriesOf<A>::Qf>(critics_t, L, xb, q1);
-  forward_tile<typename SeriesOf<A>::Qf>(critics_t + nparam<Qf>(), L, xb, q2);
-  if (i >= m || !finishes_row()) return;
-  y[i] = brs::sac::sac_combine(reward[i], done[i], gamma, q1[0], q2[0], brs::sac::ent_coef_of<Pi>(actor), sm.logp);
-  if (logp) logp[i] = sm.logp;
-#pragma unroll
-  for (int k = 0; k < ACT; k++) {
-    if (next_action) next_action[(size_t)ACT * i + k] = sm.a[k];
-    if (noise) noise[(size_t)ACT * i + k] = z[k];
-  }
+  __shared__ float L[lds_floats<typename A::Pi, typename A::Qf>()];
+  target_body(SacTarget<A>{actor, seed, draw, next_action, logp, noise}, L, actor, critics_t, m, next_obs, reward, done, gamma, y);
 }
 
 // ------------------------------------------------------------------------------------------------ replay buffer
@@ -286,12 +304,11 @@ struct brs_ddpg {
   std::string err;
 };
 
-using brs::host::DeviceGuard, brs::host::fail;
+using brs::host::DeviceGuard, brs::host::fail, brs::host::launch_on, brs::host::needs_nothing;
+using brs::sac::with_arch;
 
-// the DDPG / TD3 calls exist at the reference widths only
-#define BRS_REFERENCE_ARCH_ONLY(d, who)                                                                                                  \
-  if ((d)->arch != BRS_ARCH_REFERENCE)                                                                                                   \
-    return fail(d, BRS_ERR_ARG, who ": the handle's architecture does not serve this call (DDPG and TD3 run at BRS_ARCH_REFERENCE only)")
+static const char* reference_arch(const brs_ddpg* d) { return BRS_REFERENCE_ARCH_ONLY(d); }
+static dim3 row_grid(int32_t n) { return dim3((n + WG_ROWS - 1) / WG_ROWS); }  // workgroups of 4 waves x 32 rows
 
 extern "C" {
 
@@ -327,33 +344,25 @@ int brs_ddpg_act(brs_ddpg* d, const float* actor_dev, int32_t n, const float* ob
   if (n < 1) return fail(d, BRS_ERR_ARG, "brs_ddpg_act: n must be at least 1");
   if (!(sigma >= 0.0f)) return fail(d, BRS_ERR_ARG, "brs_ddpg_act: sigma must be >= 0");
   if (!action_dev || (!random && (!actor_dev || !obs_dev))) return fail(d, BRS_ERR_ARG, "brs_ddpg_act: null argument");
-  if (!d) return fail(d, BRS_ERR_ARG, "brs_ddpg_act: null handle");
-  BRS_REFERENCE_ARCH_ONLY(d, "brs_ddpg_act");
-  DeviceGuard g(d->device);
-  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_ddpg_act: hipSetDevice failed");
-  if (random)
-    hipLaunchKernelGGL(ddpg_random_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, env_index_base, step, sigma,
-                       action_dev, mean_dev, noise_dev);
-  else
-    hipLaunchKernelGGL(ddpg_act_kernel, dim3((n + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_dev, n, obs_dev, seed,
-                       env_index_base, step, sigma, action_dev, mean_dev, noise_dev);
-  BRS_HIP_TRY(d, hipGetLastError());
-  return BRS_OK;
+  return launch_on(d, "brs_ddpg_act", reference_arch, [&] {
+    if (random)
+      hipLaunchKernelGGL(ddpg_random_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, env_index_base, step, sigma,
+                         action_dev, mean_dev, noise_dev);
+    else
+      hipLaunchKernelGGL(ddpg_act_kernel, row_grid(n), dim3(THREADS), 0, (hipStream_t)stream, actor_dev, n, obs_dev, seed, env_index_base, step,
+                         sigma, action_dev, mean_dev, noise_dev);
+  });
 }
 
 int brs_ddpg_q(brs_ddpg* d, const float* critic_dev, int32_t n, const float* obs_dev, const float* act_dev, float* q_dev, void* stream) {
   if (n < 1) return fail(d, BRS_ERR_ARG, "brs_ddpg_q: n must be at least 1");
   if (!critic_dev || !obs_dev || !act_dev || !q_dev) return fail(d, BRS_ERR_ARG, "brs_ddpg_q: null argument");
-  if (!d) return fail(d, BRS_ERR_ARG, "brs_ddpg_q: null handle");
-  DeviceGuard g(d->device);
-  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_ddpg_q: hipSetDevice failed");
-  const dim3 grid((n + WG_ROWS - 1) / WG_ROWS);
-  if (d->arch == BRS_ARCH_SAC_DEFAULT)
-    hipLaunchKernelGGL(ddpg_q_kernel<Critic256>, grid, dim3(THREADS), 0, (hipStream_t)stream, critic_dev, n, obs_dev, act_dev, q_dev);
-  else
-    hipLaunchKernelGGL(ddpg_q_kernel<Critic>, grid, dim3(THREADS), 0, (hipStream_t)stream, critic_dev, n, obs_dev, act_dev, q_dev);
-  BRS_HIP_TRY(d, hipGetLastError());
-  return BRS_OK;
+  return launch_on(d, "brs_ddpg_q", needs_nothing, [&] {
+    with_arch(d->arch, [&](auto a) {
+      hipLaunchKernelGGL(ddpg_q_kernel<typename decltype(a)::Qf>, row_grid(n), dim3(THREADS), 0, (hipStream_t)stream, critic_dev, n, obs_dev, act_dev,
+                         q_dev);
+    });
+  });
 }
 
 int brs_ddpg_td_target(brs_ddpg* d, const float* actor_target_dev, const float* critic_target_dev, int32_t m, const float* next_obs_dev,
@@ -361,14 +370,10 @@ int brs_ddpg_td_target(brs_ddpg* d, const float* actor_target_dev, const float* 
   if (m < 1) return fail(d, BRS_ERR_ARG, "brs_ddpg_td_target: m must be at least 1");
   if (!actor_target_dev || !critic_target_dev || !next_obs_dev || !reward_dev || !done_dev || !y_dev)
     return fail(d, BRS_ERR_ARG, "brs_ddpg_td_target: null argument");
-  if (!d) return fail(d, BRS_ERR_ARG, "brs_ddpg_td_target: null handle");
-  BRS_REFERENCE_ARCH_ONLY(d, "brs_ddpg_td_target");
-  DeviceGuard g(d->device);
-  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_ddpg_td_target: hipSetDevice failed");
-  hipLaunchKernelGGL(ddpg_td_target_kernel, dim3((m + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_target_dev,
-                     critic_target_dev, m, next_obs_dev, reward_dev, done_dev, gamma, y_dev);
-  BRS_HIP_TRY(d, hipGetLastError());
-  return BRS_OK;
+  return launch_on(d, "brs_ddpg_td_target", reference_arch, [&] {
+    hipLaunchKernelGGL(ddpg_td_target_kernel, row_grid(m), dim3(THREADS), 0, (hipStream_t)stream, actor_target_dev, critic_target_dev, m,
+                       next_obs_dev, reward_dev, done_dev, gamma, y_dev);
+  });
 }
 
 int brs_td3_td_target(brs_ddpg* d, const float* actor_target_dev, const float* critics_target_dev, int32_t m, const float* next_obs_dev,
@@ -377,35 +382,26 @@ int brs_td3_td_target(brs_ddpg* d, const float* actor_target_dev, const float* c
   if (const char* why = td3_target_argument_error(actor_target_dev, critics_target_dev, m, next_obs_dev, reward_dev, done_dev, policy_noise,
                                                   noise_clip, y_dev))
     return fail(d, BRS_ERR_ARG, std::string("brs_td3_td_target: ") + why);
-  if (!d) return fail(d, BRS_ERR_ARG, "brs_td3_td_target: null handle");
-  BRS_REFERENCE_ARCH_ONLY(d, "brs_td3_td_target");
-  DeviceGuard g(d->device);
-  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_td3_td_target: hipSetDevice failed");
-  hipLaunchKernelGGL(td3_td_target_kernel, dim3((m + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_target_dev,
-                     critics_target_dev, m, next_obs_dev, reward_dev, done_dev, gamma, policy_noise, noise_clip, seed, draw, y_dev,
-                     next_action_dev, noise_dev);
-  BRS_HIP_TRY(d, hipGetLastError());
-  return BRS_OK;
+  return launch_on(d, "brs_td3_td_target", reference_arch, [&] {
+    hipLaunchKernelGGL(td3_td_target_kernel, row_grid(m), dim3(THREADS), 0, (hipStream_t)stream, actor_target_dev, critics_target_dev, m,
+                       next_obs_dev, reward_dev, done_dev, gamma, policy_noise, noise_clip, seed, draw, y_dev, next_action_dev, noise_dev);
+  });
 }
 
 int brs_sac_act(brs_ddpg* d, const float* actor_dev, int32_t n, const float* obs_dev, uint64_t seed, int64_t env_index_base, uint32_t step,
                 int32_t deterministic, int32_t random, float* action_dev, float* mu_dev, float* log_std_dev, float* z_dev, void* stream) {
   if (const char* why = brs::sac::sac_act_argument_error(actor_dev, n, obs_dev, random, action_dev))
     return fail(d, BRS_ERR_ARG, std::string("brs_sac_act: ") + why);
-  if (!d) return fail(d, BRS_ERR_ARG, "brs_sac_act: null handle");
-  DeviceGuard g(d->device);
-  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_sac_act: hipSetDevice failed");
-  if (random)
-    hipLaunchKernelGGL(sac_random_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, env_index_base, step, action_dev,
-                       mu_dev, log_std_dev, z_dev);
-  else if (d->arch == BRS_ARCH_SAC_DEFAULT)
-    hipLaunchKernelGGL(sac_act_kernel<ArchSacDefault>, dim3((n + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_dev, n,
-                       obs_dev, seed, env_index_base, step, deterministic != 0, action_dev, mu_dev, log_std_dev, z_dev);
-  else
-    hipLaunchKernelGGL(sac_act_kernel<ArchReference>, dim3((n + WG_ROWS - 1) / WG_ROWS), dim3(THREADS), 0, (hipStream_t)stream, actor_dev, n,
-                       obs_dev, seed, env_index_base, step, deterministic != 0, action_dev, mu_dev, log_std_dev, z_dev);
-  BRS_HIP_TRY(d, hipGetLastError());
-  return BRS_OK;
+  return launch_on(d, "brs_sac_act", needs_nothing, [&] {
+    if (random)
+      hipLaunchKernelGGL(sac_random_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, env_index_base, step, action_dev,
+                         mu_dev, log_std_dev, z_dev);
+    else
+      with_arch(d->arch, [&](auto a) {
+        hipLaunchKernelGGL(sac_act_kernel<decltype(a)>, row_grid(n), dim3(THREADS), 0, (hipStream_t)stream, actor_dev, n, obs_dev, seed,
+                           env_index_base, step, deterministic != 0, action_dev, mu_dev, log_std_dev, z_dev);
+      });
+  });
 }
 
 int brs_sac_td_target(brs_ddpg* d, const float* actor_dev, const float* critics_target_dev, int32_t m, const float* next_obs_dev,
@@ -413,18 +409,12 @@ int brs_sac_td_target(brs_ddpg* d, const float* actor_dev, const float* critics_
                       float* next_action_dev, float* logp_dev, float* z_dev, void* stream) {
   if (const char* why = brs::sac::sac_target_argument_error(actor_dev, critics_target_dev, m, next_obs_dev, reward_dev, done_dev, gamma, y_dev))
     return fail(d, BRS_ERR_ARG, std::string("brs_sac_td_target: ") + why);
-  if (!d) return fail(d, BRS_ERR_ARG, "brs_sac_td_target: null handle");
-  DeviceGuard g(d->device);
-  if (!g.ok) return fail(d, BRS_ERR_HIP, "brs_sac_td_target: hipSetDevice failed");
-  const dim3 grid((m + WG_ROWS - 1) / WG_ROWS);
-  if (d->arch == BRS_ARCH_SAC_DEFAULT)
-    hipLaunchKernelGGL(sac_td_target_kernel<ArchSacDefault>, grid, dim3(THREADS), 0, (hipStream_t)stream, actor_dev, critics_target_dev, m,
-                       next_obs_dev, reward_dev, done_dev, gamma, seed, draw, y_dev, next_action_dev, logp_dev, z_dev);
-  else
-    hipLaunchKernelGGL(sac_td_target_kernel<ArchReference>, grid, dim3(THREADS), 0, (hipStream_t)stream, actor_dev, critics_target_dev, m,
-                       next_obs_dev, reward_dev, done_dev, gamma, seed, draw, y_dev, next_action_dev, logp_dev, z_dev);
-  BRS_HIP_TRY(d, hipGetLastError());
-  return BRS_OK;
+  return launch_on(d, "brs_sac_td_target", needs_nothing, [&] {
+    with_arch(d->arch, [&](auto a) {
+      hipLaunchKernelGGL(sac_td_target_kernel<decltype(a)>, row_grid(m), dim3(THREADS), 0, (hipStream_t)stream, actor_dev, critics_target_dev, m,
+                         next_obs_dev, reward_dev, done_dev, gamma, seed, draw, y_dev, next_action_dev, logp_dev, z_dev);
+    });
+  });
 }
 
 const char* brs_replay_last_error(void) { return brs::host::last_error<brs_replay>(nullptr); }

@@ -27,6 +27,10 @@ static_assert(nparam<Critic256>() == BRS_SAC256_NCRITIC, "include/brs_policy.h")
 template <class N> struct Offsets {
   static constexpr int W1 = 0, B1 = W1 + N::H1 * N::IN, W2 = B1 + N::H1, B2 = W2 + N::H2 * N::H1, W3 = B2 + N::H2, B3 = W3 + N::OUT * N::H2;
 };
+// the hidden widths as the matrix-core kernels hold them, padded to the 32-unit tile (brs_ddpg_tile.hpp); here, without device code,
+// so that the sizing table of a learner handle (brs_ddpg_learner.hpp, brs_sac.hpp) compiles with g++
+constexpr int pad32(int x) { return (x + 31) / 32 * 32; }
+template <class N> struct Padded { static constexpr int H1P = pad32(N::H1), H2P = pad32(N::H2); };
 
 constexpr uint32_t TAG_ACT = BRS_DDPG_TAG_ACT, TAG_SAMPLE = BRS_DDPG_TAG_SAMPLE, TAG_TD3_NOISE = BRS_TD3_TAG_NOISE;
 

@@ -28,9 +28,37 @@ static_assert(nparam<SacActor256>() == BRS_SAC256_NACTOR && SacActor256::OUT == 
 struct ArchReference { static constexpr int ID = BRS_ARCH_REFERENCE; using Pi = SacActor; using Qf = Critic; };
 struct ArchSacDefault { static constexpr int ID = BRS_ARCH_SAC_DEFAULT; using Pi = SacActor256; using Qf = Critic256; };
 inline bool known_arch(int32_t arch) { return arch == BRS_ARCH_REFERENCE || arch == BRS_ARCH_SAC_DEFAULT; }
+// f(A{}) for the architecture `arch` names (known_arch): how a call dispatches on its handle's
+template <class F> auto with_arch(int32_t arch, F&& f) { return arch == BRS_ARCH_SAC_DEFAULT ? f(ArchSacDefault{}) : f(ArchReference{}); }
 // the per-sample rows next to the hidden ones: dz3[4], the temperature's gradient share, then the SAC_NSTAT statistics; in the
 // gradient buffer the last five follow b3 directly (b3 is the last parameter block)
 constexpr int SAC_TAIL = 1 + SAC_NSTAT, SAC_Z3_ROWS = SacActor::OUT + SAC_TAIL, SAC_ROW_LEN = SAC_NACTOR + SAC_TAIL;
+
+// ---- the sizing table of a learner handle (brs_ddpg_learner.hip: create).  What the SAC calls of architecture A keep in the scratch:
+// the actor's image with its nine per-sample rows (Z3_ROWS = 4 holds dz3[OUT <= 2] and two statistics only), two images of the
+// critic's back to back; and the two rows they write
+template <class A> struct ArchDims {
+  using Pi = typename A::Pi;
+  using Qf = typename A::Qf;
+  using PiLay = Layout<Pi, SAC_Z3_ROWS>;
+  using QfLay = Layout<Qf>;
+  static constexpr int ROW_LEN = nparam<Pi>() + SAC_TAIL, TWIN_ROW_LEN = 2 * nparam<Qf>() + BRS_TD3_NSTAT;
+  static_assert(Pi::OUT + SAC_TAIL <= SAC_Z3_ROWS && Qf::OUT + NSTAT <= Z3_ROWS, "rows");
+};
+// the `sac` row of brs_ddpg_learner.hpp's table, and the table as create() reads it.  At the reference widths a SAC handle also serves
+// the DDPG / TD3 calls: their images and rows fit (asserted); at other widths those calls are refused
+template <class A> constexpr HandleSize sac_handle_size() {
+  using D = ArchDims<A>;
+  return HandleSize{std::max(D::PiLay::ROWS, 2 * D::QfLay::ROWS), std::max(D::ROW_LEN, D::TWIN_ROW_LEN)};
+}
+constexpr HandleSize handle_size(bool twin, bool sac, int32_t arch) {
+  if (sac) return arch == BRS_ARCH_SAC_DEFAULT ? sac_handle_size<ArchSacDefault>() : sac_handle_size<ArchReference>();
+  return ddpg_handle_size(twin);
+}
+static_assert(handle_size(true, true, BRS_ARCH_REFERENCE).scratch_rows >= handle_size(true, false, BRS_ARCH_REFERENCE).scratch_rows &&
+              handle_size(true, true, BRS_ARCH_REFERENCE).partial_len >= handle_size(true, false, BRS_ARCH_REFERENCE).partial_len,
+              "a SAC handle of the reference widths serves the DDPG and TD3 calls");
+
 constexpr float LOG_STD_MIN = -20.0f, LOG_STD_MAX = 2.0f, SQUASH_EPS = 1e-6f, HALF_LOG_2PI = 0.9189385332046727f;
 
 BRS_HD void sac_act_block(uint64_t seed, int64_t gid, uint32_t step, uint32_t* o) {
@@ -45,8 +73,9 @@ BRS_HD void sac_row_block(uint32_t tag, uint64_t seed, uint32_t draw, uint32_t j
 // torch.clamp(log_std, -20, 2) and where its backward lets the gradient through (both ends included, as torch)
 BRS_HD float clamp_log_std(float raw) { return clip_keep_nan(raw, LOG_STD_MIN, LOG_STD_MAX); }  // a NaN stays, as torch.clamp
 BRS_HD bool log_std_gate(float raw) { return raw >= LOG_STD_MIN && raw <= LOG_STD_MAX; }
-BRS_HD float ent_coef(const float* actor) { return expf(actor[SAC_NACTOR]); }
 template <class P> BRS_HD float ent_coef_of(const float* actor) { return expf(actor[nparam<P>()]); }  // log_ent_coef follows actor P's b3
+// (the name of it in the header as host mirrors were first written against it; nothing of this tree calls it any more)
+BRS_HD float ent_coef(const float* actor) { return ent_coef_of<SacActor>(actor); }
 
 // u = mu + sigma z: a product and a sum, on the device as on the host
 BRS_HD float pre_squash(float mu, float sigma, float z) {
@@ -124,9 +153,6 @@ BRS_HD void sac_shares(int learn_alpha, float target_entropy, float alpha, float
   share[3] = qmin * inv_m;
   share[4] = alpha * inv_m;
 }
-
-// brs_sac_twin_critic_grad: the loss head with SB3's 0.5 (a power of two: exact)
-BRS_HD CriticHead scale_head(CriticHead h, float loss_scale) { return CriticHead{h.dq * loss_scale, h.loss * loss_scale, h.q}; }
 
 // ---- the argument rules that need no device: 0 or the text after the function's name and ": "
 inline const char* sac_act_argument_error(const void* actor, int32_t n, const void* obs, int32_t random, const void* action) {

@@ -9,7 +9,6 @@ Two conditions on top of offpolicy_cases.conditioned, both checked on the fp64 y
     t = 2 (q - y) / m and for the two components of d La / d (actor output before the tanh)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import torch
@@ -17,7 +16,8 @@ import torch
 import ref_ddpg_learner as RL
 import ref_offpolicy as R
 from balance_robot_mujoco_rl_amd import _lib
-from offpolicy_cases import GXX, ROOT, _active_ok, conditioned
+from hostbuild import ROOT, _ptr, compile_host
+from offpolicy_cases import _active_ok, conditioned
 
 HOST_DIR = os.path.join(ROOT, "tests", "ddpglearnerhost")
 MARGIN = {"init": 1e-5, "x3": 1e-4}
@@ -214,15 +214,9 @@ def check_trajectory(what, flats, case):
 
 
 # ------------------------------------------------------------------------------------------------ the host build
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def build_host(directory):
     """g++ -> libddpglearnerhost.so in `directory`, with its signatures applied"""
-    so = os.path.join(str(directory), "libddpglearnerhost.so")
-    subprocess.check_call(GXX + ["-fPIC", "-shared", "-o", so, os.path.join(HOST_DIR, "ddpglearnerhost.cpp")])
-    L = C.CDLL(so)
+    L = compile_host(directory, "libddpglearnerhost.so", os.path.join(HOST_DIR, "ddpglearnerhost.cpp"))
     vp, i = C.c_void_p, C.c_int
     L.dh_critic_grad.restype, L.dh_critic_grad.argtypes = i, [vp, i, vp, vp, vp, vp]
     L.dh_actor_grad.restype, L.dh_actor_grad.argtypes = i, [vp, vp, i, vp, vp]

@@ -4,16 +4,14 @@ combination of the two end flags, the gate, and the host build of the kernel sou
 import ctypes as C
 import itertools
 import os
-import subprocess
 
 import numpy as np
 
 import ref_offpolicy as R
 from balance_robot_mujoco_rl_amd import _lib
+from hostbuild import GXX, ROOT, _ptr, compile_host  # noqa: F401 (the tests take GXX and ROOT from here)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST_DIR = os.path.join(ROOT, "tests", "offpolicyhost")
-GXX = ["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off", "-I", os.path.join(ROOT, "balance_robot_mujoco_rl_amd", "csrc")]
 
 FORWARD_ROWS = (1, 31, 32, 33, 63, 64, 65, 255, 256, 257)
 KERNEL_ROWS = (127, 128, 129)              # the kernel's workgroup edge (4 waves x 32 rows); 31 / 32 / 33 are its wave edge
@@ -105,15 +103,9 @@ def reference_buffer(n, cap, steps):
 
 
 # ------------------------------------------------------------------------------------------------ the host build
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def build_host(directory):
     """g++ -> liboffpolicyhost.so in `directory`, with its signatures applied"""
-    so = os.path.join(str(directory), "liboffpolicyhost.so")
-    subprocess.check_call(GXX + ["-fPIC", "-shared", "-o", so, os.path.join(HOST_DIR, "offpolicyhost.cpp")])
-    L = C.CDLL(so)
+    L = compile_host(directory, "liboffpolicyhost.so", os.path.join(HOST_DIR, "offpolicyhost.cpp"))
     vp, i, st = C.c_void_p, C.c_int, C.POINTER(_lib.BrsReplayStorage)
     L.oh_act.restype, L.oh_act.argtypes = i, [vp, i, vp, C.c_uint64, C.c_int64, C.c_uint32, C.c_float, i, vp, vp, vp]
     L.oh_q.restype, L.oh_q.argtypes = i, [vp, i, vp, vp, vp]

@@ -18,7 +18,6 @@ instance are its own, and the originals are not touched."""
 import ctypes as C_
 import importlib.util
 import os
-import subprocess
 import sys
 import types
 
@@ -27,7 +26,7 @@ import numpy as np
 import ref_ddpg_learner as _RL
 import ref_offpolicy as _R
 from balance_robot_mujoco_rl_amd import _lib
-from offpolicy_cases import GXX, ROOT
+from hostbuild import ROOT, compile_host
 
 ARCH_ID, NET_ARCH = _lib.ARCH_SAC_DEFAULT, "sb3"
 ACTOR_SIZES, CRITIC_SIZES = (_R.OBS, 256, 256, 2 * _R.ACT), (_R.OBS + _R.ACT, 256, 256, 1)
@@ -134,9 +133,7 @@ C.HOST_ROWS_MAX = 2049
 def build_host(directory, arch="ArchSacDefault"):
     """g++ -> libsacarchhost.so of tests/sacarchhost for `arch` in `directory`, with sac_cases.build_host's signatures: the Host*
     wrappers of C drive it"""
-    so = os.path.join(str(directory), f"libsacarchhost_{arch}.so")
-    subprocess.check_call(GXX + [f"-DSACARCH={arch}", "-fPIC", "-shared", "-o", so, os.path.join(HOST_DIR, "sacarchhost.cpp")])
-    L = C_.CDLL(so)
+    L = compile_host(directory, f"libsacarchhost_{arch}.so", os.path.join(HOST_DIR, "sacarchhost.cpp"), [f"SACARCH={arch}"])
     vp, i, f, u64, u32 = C_.c_void_p, C_.c_int, C_.c_float, C_.c_uint64, C_.c_uint32
     L.sh_act.restype, L.sh_act.argtypes = i, [vp, i, vp, u64, C_.c_int64, u32, i, i, vp, vp, vp, vp]
     L.sh_target.restype, L.sh_target.argtypes = i, [vp, vp, i, vp, vp, vp, f, u64, u32, vp, vp, vp, vp]

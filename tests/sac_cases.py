@@ -20,7 +20,6 @@ the bound of the comparison with the host build, the allocation's arithmetic (pa
 replaced (changed_last_row) are here, for both widths (tests/sac_arch_cases.py executes this source a second time)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import torch
@@ -32,7 +31,8 @@ import td3_cases as TC
 from balance_robot_mujoco_rl_amd import _lib
 from ddpg_learner_cases import (GRAD_GATE, SPLIT_BIG, SPLIT_LAST_REAL, SPLIT_ROWS, SPLIT_SEQUENCE, SPLIT_TABLE, SPLIT_X3_ROWS, _draw, _no_cancellation,
                                 block_distances)
-from offpolicy_cases import GAMMA, GATE, GXX, ROOT, SEED, _active_ok, conditioned
+from hostbuild import ROOT, _ptr, compile_host
+from offpolicy_cases import GAMMA, GATE, SEED, _active_ok, conditioned
 
 HOST_DIR = os.path.join(ROOT, "tests", "sachost")
 NA, NC = S.NACTOR, S.NCRITIC
@@ -423,15 +423,9 @@ def check_chain(what, flats, case):
 
 
 # ------------------------------------------------------------------------------------------------ the host build
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def build_host(directory):
     """g++ -> libsachost.so in `directory`, with its signatures applied"""
-    so = os.path.join(str(directory), "libsachost.so")
-    subprocess.check_call(GXX + ["-fPIC", "-shared", "-o", so, os.path.join(HOST_DIR, "sachost.cpp")])
-    L = C.CDLL(so)
+    L = compile_host(directory, "libsachost.so", os.path.join(HOST_DIR, "sachost.cpp"))
     vp, i, f, u64, u32 = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint32
     L.sh_act.restype, L.sh_act.argtypes = i, [vp, i, vp, u64, C.c_int64, u32, i, i, vp, vp, vp, vp]
     L.sh_target.restype, L.sh_target.argtypes = i, [vp, vp, i, vp, vp, vp, f, u64, u32, vp, vp, vp, vp]

@@ -1,7 +1,8 @@
 // Host build of SAC's kernel source for an ARCHITECTURE (balance_robot_mujoco_rl_amd/csrc/brs_sac.hpp: ArchReference,
-// ArchSacDefault): tests/sachost/sachost.hpp's row loops as templates over the actor and the critic of the architecture, around the same
-// per-row functions the kernels call -- clamp and gate, sample, logp, the two dz3 formulas, min-select, combine, shares -- behind the
-// argument rules of the C ABI.  Shared by sacarchhost.cpp (a library for tests/test_sac_arch_cpu.py) and sacarchhost_main.cpp (a
+// ArchSacDefault): the act, the target and the actor's chain as plain row loops (forward_row_keep / backward_row of brs_ddpg_learner.hpp),
+// templates over the actor and the critic of the architecture, around the per-row functions the kernels call -- clamp and gate, sample,
+// logp, the two dz3 formulas, min-select, combine, shares -- and the critic gradient with the 0.5 at the loss head, behind the argument
+// rules of the C ABI (include/brs_policy.h: brs_sac_*).  tests/sachost is Host<ArchReference> of this file.  Shared by sacarchhost.cpp (a library for tests/test_sac_arch_cpu.py) and sacarchhost_main.cpp (a
 // program of its own, for the sanitizers).  SACARCH names the architecture of a build: -DSACARCH=ArchSacDefault (the default) or
 // ArchReference.
 #pragma once
@@ -81,27 +82,10 @@ template <class A> struct Host {
     return BRS_OK;
   }
 
-  // grad[2 NC + 4]: the twin gradient with loss_scale at the head (0.5: SAC's)
+  // grad[2 NC + 4]: the twin gradient with loss_scale at the head (1: TD3's; 0.5: SAC's)
   static int twin_critic_grad(const float* critics, int m, const float* obs, const float* act_, const float* y, float loss_scale, float* grad) {
     if (sac_critic_grad_argument_error(critics, m, obs, act_, y, grad)) return BRS_ERR_ARG;
-    const float inv_m = 1.0f / (float)m;
-    for (int c = 0; c < 2; c++) {
-      const float* critic = critics + (size_t)c * NC;
-      std::vector<double> g((size_t)NC + NSTAT, 0.0);
-      RowTape<Qf> t;
-      for (int i = 0; i < m; i++) {
-        float x[Qf::IN];
-        for (int k = 0; k < OBS; k++) x[k] = obs[(size_t)OBS * i + k];
-        for (int k = 0; k < ACT; k++) x[OBS + k] = act_[(size_t)ACT * i + k];
-        forward_row_keep<Qf>(critic, x, t);
-        const CriticHead hd = scale_head(critic_head(t.pre[0], y[i], inv_m), loss_scale);
-        backward_row<Qf>(critic, t, &hd.dq, g.data(), nullptr);
-        g[NC] += (double)hd.loss;
-        g[NC + 1] += (double)hd.q;
-      }
-      for (int j = 0; j < NC; j++) grad[(size_t)c * NC + j] = (float)g[j];
-      for (int j = 0; j < NSTAT; j++) grad[2 * (size_t)NC + (size_t)c * NSTAT + j] = (float)g[NC + j];
-    }
+    twin_critic_grad_host<Qf>(critics, m, obs, act_, y, loss_scale, grad);
     return BRS_OK;
   }
 
@@ -143,7 +127,8 @@ template <class A> struct Host {
     return BRS_OK;
   }
 
-  // one update of SAC.train on host arrays, in sachost::step's order
+  // one update of SAC.train on host arrays: the critic gradient with its 0.5 (for a y from the critics' targets and the CURRENT actor),
+  // one Adam with Polyak over both critics, the actor's gradient through the UPDATED critics, one Adam over the actor and the temperature
   struct State {
     std::vector<float> actor, critics, critics_t, ma, va, mc, vc, ga, gc;
     int64_t steps = 0;

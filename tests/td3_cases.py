@@ -9,7 +9,6 @@ within a tenth of that, and no cancellation behind its b3 gradient (|sum t| >= 1
 no margin: every hard decision in it (both clamps, the minimum) is continuous in its inputs."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import torch
@@ -19,7 +18,8 @@ import ref_offpolicy as R
 import ref_td3 as T3
 from balance_robot_mujoco_rl_amd import _lib
 from ddpg_learner_cases import ADAM, MARGIN, _bad_rows, _draw, _no_cancellation, block_distances, learner_case
-from offpolicy_cases import GAMMA, GXX, ROOT, SEED, _active_ok, conditioned, weights as _ddpg_weights
+from hostbuild import ROOT, _ptr, compile_host
+from offpolicy_cases import GAMMA, SEED, _active_ok, conditioned, weights as _ddpg_weights
 
 HOST_DIR = os.path.join(ROOT, "tests", "td3host")
 NC, NA = R.NCRITIC, R.NACTOR
@@ -231,15 +231,9 @@ def check_chain(what, flats, case):
 
 
 # ------------------------------------------------------------------------------------------------ the host build
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def build_host(directory):
     """g++ -> libtd3host.so in `directory`, with its signatures applied"""
-    so = os.path.join(str(directory), "libtd3host.so")
-    subprocess.check_call(GXX + ["-fPIC", "-shared", "-o", so, os.path.join(HOST_DIR, "td3host.cpp")])
-    L = C.CDLL(so)
+    L = compile_host(directory, "libtd3host.so", os.path.join(HOST_DIR, "td3host.cpp"))
     vp, i, f = C.c_void_p, C.c_int, C.c_float
     L.th_td3_target.restype, L.th_td3_target.argtypes = i, [vp, vp, i, vp, vp, vp, f, f, f, C.c_uint64, C.c_uint32, vp, vp, vp]
     L.th_twin_critic_grad.restype, L.th_twin_critic_grad.argtypes = i, [vp, i, vp, vp, vp, vp]

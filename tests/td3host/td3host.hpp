@@ -1,5 +1,5 @@
 // Host build of TD3's kernel source: the target through forward_row plus the per-row tail of brs_offpolicy.hpp
-// (td3_action_tail, td3_combine), and the twin critic gradient as two runs of the host's row loops (brs_ddpg_learner.hpp), behind
+// (td3_action_tail, td3_combine), and the twin critic gradient as the host's row loop over both critics (brs_ddpg_learner.hpp), behind
 // the argument rules of the C ABI (include/brs_policy.h: brs_td3_td_target, brs_ddpg_learner_twin_critic_grad).  Shared by
 // td3host.cpp (a library for tests/test_td3_cpu.py) and td3host_main.cpp (a program of its own, for the sanitizers).
 #pragma once
@@ -38,12 +38,7 @@ inline int td3_target(const float* actor_t, const float* critics_t, int m, const
 // grad[2 NC + 4]: block 0, block 1, then (Lc, mean Q) of critic 0 and of critic 1
 inline int twin_critic_grad(const float* critics, int m, const float* obs, const float* act, const float* y, float* grad) {
   if (!critics || !obs || !act || !y || !grad || m < 1) return BRS_ERR_ARG;
-  std::vector<float> one((size_t)row_len<Critic>());
-  for (int k = 0; k < 2; k++) {
-    critic_grad_host(critics + (size_t)k * NC, m, obs, act, y, one.data());
-    memcpy(grad + (size_t)k * NC, one.data(), NC * sizeof(float));
-    memcpy(grad + 2 * (size_t)NC + (size_t)k * NSTAT, one.data() + NC, NSTAT * sizeof(float));
-  }
+  twin_critic_grad_host<Critic>(critics, m, obs, act, y, 1.0f, grad);
   return BRS_OK;
 }
 
