@@ -33,7 +33,10 @@ include/brs.h (libbrs_hip.so).  This package is the host-side mirror of the refe
                                            net_arch="sb3" on SB3's default [256, 256], what `-a SAC` itself builds
     vecnorm.DeviceVecNormalize             SB3's VecNormalize -- running mean and variance of the observations and of the discounted
                                            return in fp64, clipping -- as HIP kernels between the simulator and the algorithm
-                                           (include/brs_policy.h: brs_vecnorm_*)
+                                           (include/brs_policy.h: brs_vecnorm_*); for DDPG, TD3 and SAC the collector
+                                           takes it as `normalize=`, DeviceReplayBuffer.sample(..., normalize=) normalises the minibatch
+                                           in the sampling kernel, and vecnorm.fold_vecnormalize folds the statistics into an actor's
+                                           first layer for deployment on raw observations
     quant.quantize_policy / QuantPolicy    int8 post-training quantisation of the actor and the int8 network as a HIP kernel
                                            (include/brs_qpolicy.h): quantize_tflite.py and sb_rl.py:285-364 on the GPU
     quant.quantize_actor / QuantActor      the same deployment check for the actor DDPG, TD3 and SAC train, 6-300-200-2 with ReLU and
@@ -51,9 +54,9 @@ from .quant import (REFERENCE_CALIBRATION, QuantActor, QuantActorModel, QuantMod
                     quantize_policy)
 from .sim import BatchedSim, BrsError  # noqa: F401
 from .vec_env import BalanceVecEnv  # noqa: F401
-from .vecnorm import DeviceVecNormalize  # noqa: F401
+from .vecnorm import DeviceVecNormalize, fold_vecnormalize  # noqa: F401
 
 __all__ = ["BatchedSim", "BalanceVecEnv", "BrsError", "DeviceA2CLearner", "DeviceDDPGLearner", "DeviceDDPGNets", "DeviceOffPolicyCollector", "DevicePPOLearner", "DeviceReplayBuffer", "DeviceSACLearner", "DeviceSACNets", "DeviceTD3Learner", "DeviceVecNormalize", "ENV_SPECS", "EpisodeMonitor", "EpisodeStats", "LearnerStats",
            "QuantActor", "QuantActorModel", "QuantModel", "QuantPolicy",
-           "REFERENCE_CALIBRATION", "episode_count_targets", "evaluate_policy", "flatten_ddpg_state_dict", "flatten_sac_actor", "flatten_td3_critics", "make_vec", "quantize_actor", "quantize_policy", "spec",
+           "REFERENCE_CALIBRATION", "episode_count_targets", "evaluate_policy", "flatten_ddpg_state_dict", "flatten_sac_actor", "flatten_td3_critics", "fold_vecnormalize", "make_vec", "quantize_actor", "quantize_policy", "spec",
            "unflatten_ddpg_state_dict", "unflatten_sac_actor", "unflatten_td3_critics"]

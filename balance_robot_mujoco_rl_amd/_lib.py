@@ -250,6 +250,8 @@ SIGNATURES = {
         "brs_vecnorm_get_stats": (C.c_int, [_vp, C.POINTER(BrsVecnormStats), _vp]),
         "brs_vecnorm_set_stats": (C.c_int, [_vp, C.POINTER(BrsVecnormStats), _vp]),
         "brs_vecnorm_get_returns": (C.c_int, [_vp, _dp, _vp]),
+        "brs_replay_sample_vecnorm": (C.c_int, [_vp, C.POINTER(BrsReplayStorage), _i32, _i32, _i32, _i32, C.c_uint64, C.c_uint32,
+                                                C.POINTER(BrsReplayStorage), _vp, _vp]),
     },
     "brs_render.h": {
         "brs_render_default_camera": (None, [C.POINTER(BrsCamera)]),

@@ -12,6 +12,9 @@
 //
 // The shape of the tree is a function of n alone (brs_vecnorm.hpp), so the statistics come out the same bytes on every run and
 // in the host build.  When not training only the apply kernel is launched.
+//
+//   vecnorm_replay_sample_kernel  brs_replay_sample's index and gather with the minibatch normalised on the way out:
+//                           eight lanes per sample, one launch, the statistics read and nothing of the handle written.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -117,6 +120,32 @@ __global__ void __launch_bounds__(APPLY_THREADS) vecnorm_reward_kernel(const int
   if (k >= m) return;
   const float r = in[k];
   out[k] = cfg.norm_reward ? normalize_reward(r, stats[var_at(RET)], cfg.epsilon, cfg.clip_reward) : r;
+}
+
+// ReplayBuffer.sample(batch_size, env=vec_normalize) in one launch: replay_sample_kernel's geometry (brs_offpolicy.hip), 256
+// threads, eight lanes per sample, each lane one 8-byte piece or the tail, every lane of a sample computing the same Philox block.
+// The elements pass through normalize_obs / normalize_reward of the handle's statistics as they stand when the kernel runs.  V2:
+// every pointer of the 8-byte pieces is 8-byte aligned (the host side decides).
+template <bool V2> __global__ void __launch_bounds__(SAMPLE_THREADS) vecnorm_replay_sample_kernel(
+    const brs_replay_storage s, const int n, const int size, const int m, const uint64_t seed, const uint32_t draw, const SampleNorm cfg,
+    const double* __restrict__ stats, const brs_replay_storage out, int32_t* __restrict__ idx) {
+  const int64_t t = (int64_t)blockIdx.x * SAMPLE_THREADS + threadIdx.x;
+  const int64_t j = t / SAMPLE_PARTS;
+  const int part = (int)(t % SAMPLE_PARTS);
+  if (j >= m) return;
+  int32_t row, env;
+  const int64_t cell = sample_cell_of(seed, draw, j, size, n, &row, &env);
+  if (part == SAMPLE_PARTS - 1) {
+    sample_tail(s, out, idx, cell, j, row, env, cfg, stats);
+    return;
+  }
+  const SamplePiece p = sample_piece(s, out, cell, j, part);
+  float v[2];
+  if (V2) { const float2 x = *reinterpret_cast<const float2*>(p.src); v[0] = x.x; v[1] = x.y; }
+  else { v[0] = p.src[0]; v[1] = p.src[1]; }
+  normalize_piece(v, p.col, cfg, stats);
+  if (V2) *reinterpret_cast<float2*>(p.dst) = make_float2(v[0], v[1]);
+  else { p.dst[0] = v[0]; p.dst[1] = v[1]; }
 }
 
 struct StatsArg {
@@ -270,6 +299,29 @@ int brs_vecnorm_normalize_reward(brs_vecnorm* v, int32_t m, const float* in_dev,
   hipLaunchKernelGGL(vecnorm_reward_kernel, dim3(blocks_for(m)), dim3(APPLY_THREADS), 0, (hipStream_t)stream, m, v->cfg, v->stats, in_dev,
                      out_dev);
   if (hipGetLastError() != hipSuccess) return fail(v, BRS_ERR_HIP, "brs_vecnorm_normalize_reward: kernel launch failed");
+  return BRS_OK;
+}
+
+int brs_replay_sample_vecnorm(brs_vecnorm* v, const brs_replay_storage* storage, int32_t n, int32_t cap, int32_t size, int32_t m,
+                              uint64_t seed, uint32_t draw, const brs_replay_storage* out, int32_t* idx_dev, void* stream) {
+  if (!v) return BRS_ERR_STATE;
+  if (const char* why = replay_sample_argument_error(storage, n, cap, size, m, out))
+    return fail(v, BRS_ERR_ARG, std::string("brs_replay_sample_vecnorm: ") + why);
+  DeviceGuard g(v->device);
+  if (!g.ok) return fail(v, BRS_ERR_HIP, "brs_replay_sample_vecnorm: hipSetDevice failed");
+  bool v2 = true;
+  for (const void* p : {(const void*)storage->obs, (const void*)storage->next_obs, (const void*)storage->action, (const void*)out->obs,
+                        (const void*)out->next_obs, (const void*)out->action})
+    v2 = v2 && ((uintptr_t)p & 7) == 0;
+  const SampleNorm cfg{v->cfg.epsilon, v->cfg.clip_obs, v->cfg.clip_reward, v->cfg.norm_obs, v->cfg.norm_reward};
+  const dim3 grid((unsigned)(((int64_t)m * SAMPLE_PARTS + SAMPLE_THREADS - 1) / SAMPLE_THREADS));
+  if (v2)
+    hipLaunchKernelGGL(vecnorm_replay_sample_kernel<true>, grid, dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, *storage, n, size, m, seed, draw,
+                       cfg, v->stats, *out, idx_dev);
+  else
+    hipLaunchKernelGGL(vecnorm_replay_sample_kernel<false>, grid, dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, *storage, n, size, m, seed, draw,
+                       cfg, v->stats, *out, idx_dev);
+  if (hipGetLastError() != hipSuccess) return fail(v, BRS_ERR_HIP, "brs_replay_sample_vecnorm: kernel launch failed");
   return BRS_OK;
 }
 

@@ -1,13 +1,15 @@
 // brs_vecnorm.hpp -- VecNormalize of include/brs_policy.h, the part shared by the HIP kernels (brs_vecnorm.hip)
 // and the host build the CPU tests compare with the numpy restatement (tests/vecnormhost): the (count, mean, M2) triple and its
 // merge, the thread <-> env map and the pairing of the reduction tree, the update of the running statistics, and the normalise
-// and clip of one element.  All of it is fp64 `+ - * /` with contraction off, so host and device give the same bytes.
+// and clip of one element, and the lane map of the normalising replay sample (tests/vecnormreplayhost).  All of
+// it is fp64 `+ - * /` with contraction off, so host and device give the same bytes.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/brs.h"
 #include "../../include/brs_policy.h"
+#include "brs_offpolicy.hpp"  // sample_block, sample_cell: the cells of brs_replay_sample
 
 #ifndef BRS_HD
 #if defined(__HIPCC__)
@@ -132,6 +134,66 @@ BRS_HD Triple fold_partials(const Triple* partials, int num, int c, int l) {
   Triple a = empty();
   for (int p = l; p < num; p += WAVE) a = merge(a, partials[(int64_t)p * NCOL + c]);
   return a;
+}
+
+// ---- brs_replay_sample_vecnorm: ReplayBuffer.sample(batch_size, env=vec_normalize).  The geometry is
+// brs_replay_sample's: eight lanes per sample, lane `part` of sample j.  Parts 0-2 carry columns 2p, 2p + 1 of obs, parts 3-5 the
+// same columns of next_obs, part 6 the action, part 7 reward, done and idx.
+constexpr int SAMPLE_PARTS = 8, SAMPLE_THREADS = 256, SAMPLES_PER_GROUP = SAMPLE_THREADS / SAMPLE_PARTS;
+
+// what the normalisation of a sample reads of the handle's configuration
+struct SampleNorm {
+  double epsilon, clip_obs, clip_reward;
+  int norm_obs, norm_reward;
+};
+
+// the cell sample j of `draw` reads: brs_replay_sample's Philox block and row/env map
+BRS_HD int64_t sample_cell_of(uint64_t seed, uint32_t draw, int64_t j, int32_t size, int32_t n, int32_t* row, int32_t* env) {
+  uint32_t w[4];
+  brs::offpolicy::sample_block(seed, draw, (uint32_t)j, w);
+  brs::offpolicy::sample_cell(w[0], w[1], size, n, row, env);
+  return (int64_t)*row * n + *env;
+}
+
+// parts 0-6: where the lane's two floats come from and go to; `col`: their first observation column, -1 for the action
+struct SamplePiece {
+  const float* src;
+  float* dst;
+  int col;
+};
+BRS_HD SamplePiece sample_piece(const brs_replay_storage& s, const brs_replay_storage& out, int64_t cell, int64_t j, int part) {
+  constexpr int OBS = brs::offpolicy::OBS, ACT = brs::offpolicy::ACT;
+  if (part < 3) return SamplePiece{s.obs + cell * OBS + 2 * part, out.obs + j * OBS + 2 * part, 2 * part};
+  if (part < 6) return SamplePiece{s.next_obs + cell * OBS + 2 * (part - 3), out.next_obs + j * OBS + 2 * (part - 3), 2 * (part - 3)};
+  return SamplePiece{s.action + cell * ACT, out.action + j * ACT, -1};
+}
+
+// the two floats of a piece through normalize_obs of their columns; the action and a switched-off half stay as they are
+BRS_HD void normalize_piece(float* v, int col, const SampleNorm& c, const double* stats) {
+  if (col < 0 || !c.norm_obs) return;
+  for (int k = 0; k < 2; k++) v[k] = normalize_obs(v[k], stats[mean_at(col + k)], stats[var_at(col + k)], c.epsilon, c.clip_obs);
+}
+
+// part 7
+BRS_HD void sample_tail(const brs_replay_storage& s, const brs_replay_storage& out, int32_t* idx, int64_t cell, int64_t j, int32_t row,
+                        int32_t env, const SampleNorm& c, const double* stats) {
+  const float r = s.reward[cell];
+  out.reward[j] = c.norm_reward ? normalize_reward(r, stats[var_at(RET)], c.epsilon, c.clip_reward) : r;
+  out.done[j] = s.done[cell];
+  if (idx) { idx[2 * j] = row; idx[2 * j + 1] = env; }
+}
+
+// the argument rules of brs_replay_sample_vecnorm that need no device, brs_replay_sample's: 0 or the text after the call's name
+inline const char* replay_sample_argument_error(const brs_replay_storage* s, int32_t n, int32_t cap, int32_t size, int32_t m,
+                                                const brs_replay_storage* out) {
+  if (!s || !s->obs || !s->next_obs || !s->action || !s->reward || !s->done) return "null storage pointer";
+  if (n < 1 || cap < 1) return "n and cap must be at least 1";
+  if (n > 0x7fffffff / brs::offpolicy::OBS) return "n * 6 exceeds 2^31 - 1";
+  if ((int64_t)cap * (int64_t)n > 0x7fffffffLL) return "cap * n exceeds 2^31 - 1";
+  if (size < 1 || size > cap) return "size must be in [1, cap]";
+  if (m < 1 || m > (1 << 27)) return "m must be in [1, 2^27]";
+  if (!out || !out->obs || !out->next_obs || !out->action || !out->reward || !out->done) return "null output pointer";
+  return nullptr;
 }
 
 }  // namespace vecnorm

@@ -261,12 +261,17 @@ class DeviceReplayBuffer(DeviceObject):
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=d)
         return f(m, 6), f(m, 6), f(m, 2), f(m), torch.empty(m, dtype=torch.uint8, device=d)
 
-    def sample(self, m, out=None, idx=None):
+    def sample(self, m, out=None, idx=None, normalize=None):
         """m uniform transitions -> (obs [m,6], next_obs [m,6], action [m,2], reward [m], done [m] uint8); `out`: the same five
-        preallocated; idx: optional int32 [m,2] that receives (row, env).  Every call uses the next value of the draw counter."""
+        preallocated; idx: optional int32 [m,2] that receives (row, env).  Every call uses the next value of the draw counter.
+        `normalize`: a DeviceVecNormalize on this device -- SB3's sample(batch_size, env=vec_normalize): the same cells, obs and
+        next_obs through normalize_obs and reward through normalize_reward of its statistics as they stand, in the same single
+        launch (brs_replay_sample_vecnorm)"""
         m = int(m)
         if self.rows < 1:
             raise ValueError("sample() from an empty buffer")
+        if normalize is not None and getattr(normalize, "device", None) != self.device:
+            raise ValueError(f"normalize: the normaliser lives on {getattr(normalize, 'device', None)}, the replay buffer on {self.device}")
         if out is None:
             out = self.new_batch(m)
         d, f32 = self.device, torch.float32
@@ -276,8 +281,13 @@ class DeviceReplayBuffer(DeviceObject):
         if idx is not None:
             _need(idx, "idx", torch.int32, (m, 2), d)
         dst = _storage(o, no, a, r, dn)
-        self._check(self.L.brs_replay_sample(d.index, C.byref(self._store), self.n, self.cap, self.rows, m, self.seed, self.draw & 0xffffffff,
-                                             C.byref(dst), _p(idx), self._stream()), "brs_replay_sample")
+        if normalize is None:
+            self._check(self.L.brs_replay_sample(d.index, C.byref(self._store), self.n, self.cap, self.rows, m, self.seed, self.draw & 0xffffffff,
+                                                 C.byref(dst), _p(idx), self._stream()), "brs_replay_sample")
+        else:   # the normaliser's handle: its statistics, its error slot
+            normalize._check(self.L.brs_replay_sample_vecnorm(normalize.h, C.byref(self._store), self.n, self.cap, self.rows, m, self.seed,
+                                                              self.draw & 0xffffffff, C.byref(dst), _p(idx), self._stream()),
+                             "brs_replay_sample_vecnorm")
         self.draw += 1
         return out
 
@@ -285,27 +295,39 @@ class DeviceReplayBuffer(DeviceObject):
 class DeviceOffPolicyCollector:
     """SB3's OffPolicyAlgorithm.collect_rollouts on the device: collect() alternates brs_ddpg_act -> brs_step -> (monitor) ->
     brs_replay_add with no synchronisation and no allocation.  `actor_params`: the flat device tensor the learner updates in place.
-    `monitor`: an EpisodeMonitor that is fed every step."""
+    `monitor`: an EpisodeMonitor that is fed every step.  `normalize`: a DeviceVecNormalize for the simulator's envs (DESIGN.md
+    7.14) -- SB3's off-policy rule: the actor acts on the normalised observation, the buffer stores the raw last observation and
+    the simulator's raw outputs (sample(..., normalize=) normalises the minibatch), the monitor sees the env's own reward, and the
+    statistics train on every step, the uniform warm-up included."""
 
-    def __init__(self, sim, nets, actor_params, replay, sigma=0.1, monitor=None):
+    def __init__(self, sim, nets, actor_params, replay, sigma=0.1, monitor=None, normalize=None):
         self.sim, self.nets, self.actor_params, self.replay, self.sigma, self.monitor = sim, nets, actor_params, replay, float(sigma), monitor
+        self.normalize = normalize
         if replay.n != sim.n:
             raise ValueError(f"the replay buffer holds {replay.n} envs, the simulator {sim.n}")
+        if normalize is not None and normalize.n != sim.n:
+            raise ValueError(f"the normaliser holds {normalize.n} envs, the simulator {sim.n}")
         self._action = torch.zeros((sim.n, 2), dtype=torch.float32, device=sim.device)
         self._last_obs = None   # a private copy: sim.step returns views that the next step overwrites
+        self._last_norm_obs = None   # with a normaliser: what the actor sees (the normaliser's own tensor)
         self.step = 0
 
     def collect(self, steps, random=False):
-        sim, nets, replay = self.sim, self.nets, self.replay
+        sim, nets, replay, normalize = self.sim, self.nets, self.replay, self.normalize
         if self._last_obs is None:
             self._last_obs = sim.reset().clone()
+            if normalize is not None:
+                self._last_norm_obs = normalize.reset(self._last_obs)
         for _ in range(int(steps)):
-            nets.act(self.actor_params, self._last_obs, self.step, self.sigma, random=random, out=self._action)
+            nets.act(self.actor_params, self._last_obs if normalize is None else self._last_norm_obs, self.step, self.sigma, random=random,
+                     out=self._action)
             self.step += 1
             obs, rew, term, trunc, tobs = sim.step(self._action)
             if self.monitor is not None:
                 self.monitor.update(rew, term, trunc)
-            replay.add(self._last_obs, self._action, obs, tobs, rew, term, trunc)
+            if normalize is not None:
+                self._last_norm_obs = normalize.step(obs, rew, term, trunc, tobs)[0]
+            replay.add(self._last_obs, self._action, obs, tobs, rew, term, trunc)   # raw, with or without a normaliser
             self._last_obs.copy_(obs)
         return self
 

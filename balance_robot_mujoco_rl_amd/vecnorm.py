@@ -3,7 +3,11 @@
 Running mean and variance of the six observation columns and of the discounted return, kept in fp64 in HBM and updated by HIP
 kernels that read the simulator's outputs in place: `step` enqueues three kernels (two when the statistics are frozen: one) and
 neither synchronises nor allocates, so it fits between `BatchedSim.step` and the algorithm inside `DeviceRollout.collect`.  The
-reduction is a tree of fixed shape without atomics: the same inputs give the same statistics, byte for byte."""
+reduction is a tree of fixed shape without atomics: the same inputs give the same statistics, byte for byte.
+
+For DDPG, TD3 and SAC the object is handed to DeviceOffPolicyCollector(normalize=) and to
+DeviceReplayBuffer.sample(normalize=), which normalises the minibatch inside the sampling kernel; `fold_vecnormalize` folds the
+observation statistics into an actor's first layer, for deployment on raw observations."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +17,42 @@ from . import _lib
 from ._handle import Handle, _need, _p
 
 _KEYS = ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count", "returns")
+
+
+def fold_first_layer(w1, b1, mean, var, epsilon=1e-8):
+    """the fold itself, in float64 and not yet rounded: (W1 [h][6], b1 [h]) -> (W1 / sqrt(var + epsilon) per column, b1 - W1' . mean)"""
+    w = np.asarray(w1, np.float64) / np.sqrt(np.asarray(var, np.float64) + float(epsilon))
+    return w, np.asarray(b1, np.float64) - w @ np.asarray(mean, np.float64)
+
+
+def fold_vecnormalize(actor_flat, state_dict, net_arch="reference", epsilon=1e-8):
+    """An actor trained behind a normaliser, for callers that hand it RAW observations (the int8 quantiser, a microcontroller): the
+    flat float32 vector with the observation statistics of `state_dict` (DeviceVecNormalize.state_dict(), or SB3's obs_rms as
+    obs_mean / obs_var) folded into the first layer,
+
+        W1' = W1 / sqrt(var + epsilon) per column,   b1' = b1 - W1' . mean,
+
+    computed in float64 and rounded once.  The first layer leads the flat layout of the DDPG / TD3 actor and of the SAC actor (with
+    or without the trailing log_ent_coef) at both width sets; the rest of the vector is copied.  The folded actor on a raw
+    observation is the original actor on the normalised one wherever no column is clipped: the clip to +-clip_obs is not linear
+    and cannot be folded."""
+    from . import nets
+    arch = nets.arch(net_arch)
+    flat = nets.flat_array(actor_flat)
+    lengths = (arch.actor.count, arch.nactor, arch.nactor + 1)
+    if flat.ndim != 1 or flat.shape[0] not in lengths:
+        raise ValueError(f"actor_flat: expected {' or '.join(map(str, lengths))} parameters for net_arch={arch.name!r}, got shape {flat.shape}")
+    for k in ("obs_mean", "obs_var"):
+        if k not in state_dict:
+            raise ValueError(f"state_dict: missing {k}")
+    mean, var = (np.asarray(state_dict[k], np.float64).reshape(-1) for k in ("obs_mean", "obs_var"))
+    if mean.shape != (6,) or var.shape != (6,):
+        raise ValueError(f"state_dict: obs_mean and obs_var must hold 6 elements, got {mean.shape} and {var.shape}")
+    h0 = arch.pi[0]
+    w, b = fold_first_layer(flat[:6 * h0].reshape(h0, 6), flat[6 * h0:7 * h0], mean, var, epsilon)
+    out = flat.copy()
+    out[:6 * h0], out[6 * h0:7 * h0] = w.astype(np.float32).ravel(), b.astype(np.float32)
+    return out
 
 
 class DeviceVecNormalize(Handle):

@@ -443,6 +443,19 @@ int brs_vecnorm_get_stats(brs_vecnorm*, brs_vecnorm_stats* out_host, void* strea
 int brs_vecnorm_set_stats(brs_vecnorm*, const brs_vecnorm_stats* in_host, void* stream);
 int brs_vecnorm_get_returns(brs_vecnorm*, double* returns_host, void* stream);
 
+/* ---- VecNormalize for the off-policy family.  SB3's rule: the actor acts on the normalised observation, the
+ * replay buffer stores the RAW observation, next observation and reward, and ReplayBuffer.sample(batch_size, env=vec_normalize)
+ * normalises the minibatch with the statistics of the moment of sampling.
+ * brs_replay_sample_vecnorm: brs_replay_sample's cells (the same Philox block, the same row/env map, the same idx), with obs and
+ * next_obs through normalize_obs and reward through normalize_reward of the handle's CURRENT statistics; action and done copied.
+ * One launch: every output byte is what brs_replay_sample followed by brs_vecnorm_normalize_obs (twice) and
+ * brs_vecnorm_normalize_reward writes.  Reads the statistics, writes neither them nor the returns nor the storage.  norm_obs == 0 /
+ * norm_reward == 0 copy that half through.  `n` is the buffer's env count and need not be the handle's.  The argument conditions
+ * are brs_replay_sample's (idx_dev may be null).  Only enqueues.  Errors go to the handle's slot (brs_vecnorm_last_error); a null
+ * handle returns BRS_ERR_STATE. */
+int brs_replay_sample_vecnorm(brs_vecnorm*, const brs_replay_storage* storage, int32_t n, int32_t cap, int32_t size, int32_t m,
+                              uint64_t seed, uint32_t draw, const brs_replay_storage* out, int32_t* idx_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,12 @@ def evaluate_actor(a):
     from balance_robot_mujoco_rl_amd import DeviceDDPGNets, DeviceSACNets, QuantActor, quantize_actor
     sac = a.algo == "sac"
     params, flat, net_arch = read_sac_actor(a.actor) if sac else (read_actor(a.actor), None, "reference")
+    if a.vec_normalize:
+        # an actor trained behind a normaliser (--vec-normalize of the train tools): its statistics folded into the first layer, so
+        # that the quantiser, the int8 kernel and both runs below take the simulator's raw observations
+        from balance_robot_mujoco_rl_amd import fold_vecnormalize
+        with np.load(a.vec_normalize) as z:
+            params = flat = fold_vecnormalize(flat if sac else ddpg_flat(params), dict(z), net_arch=net_arch)
     qm = quantize_actor(params, head="sac" if sac else "ddpg", net_arch=net_arch)
     if a.save:
         qm.save(a.save)
@@ -103,7 +109,7 @@ def ddpg_flat(params):
     return np.ascontiguousarray(flatten_ddpg_state_dict(params) if isinstance(params, dict) else params, np.float32)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--env", default="Env01-v3"); ap.add_argument("--envs", type=int, default=4096); ap.add_argument("--steps", type=int, default=1500)
     src = ap.add_mutually_exclusive_group()
@@ -111,7 +117,11 @@ def main():
     ap.add_argument("--algo", choices=("ddpg", "td3", "sac"), default="ddpg", help="how --actor is read")
     ap.add_argument("--head", choices=("mean", "actions"), default="mean")
     ap.add_argument("--save", help="write the int8 model that was evaluated to this .npz")
-    a = ap.parse_args()
+    ap.add_argument("--vec-normalize", metavar="NPZ", help="with --actor: the .vecnormalize.npz a train tool wrote next to the actor; its "
+                                                          "observation statistics are folded into the actor's first layer before quantising")
+    a = ap.parse_args(argv)
+    if a.vec_normalize and not a.actor:
+        ap.error("--vec-normalize goes with --actor")
     if a.actor:
         return evaluate_actor(a)
     if a.params:

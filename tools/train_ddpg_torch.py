@@ -150,12 +150,15 @@ class TorchData:
 class DeviceData:
     """the --device-data path: the same four operations by the HIP kernels"""
 
-    def __init__(self, sim, model, cap, sigma, seed, monitor=None):
+    normalize = None   # a DeviceVecNormalize (--vec-normalize): the collector trains it, sample() normalises the minibatch with it
+
+    def __init__(self, sim, model, cap, sigma, seed, monitor=None, normalize=None):
         from balance_robot_mujoco_rl_amd.offpolicy import DeviceDDPGNets, DeviceOffPolicyCollector, DeviceReplayBuffer
-        self.sim, self.model = sim, model
+        self.sim, self.model, self.normalize = sim, model, normalize
         self.nets = DeviceDDPGNets(device=sim.device, seed=seed)
         self.replay = DeviceReplayBuffer(sim.n, cap, device=sim.device, seed=seed)
-        self.collector = DeviceOffPolicyCollector(sim, self.nets, model.flat["actor"], self.replay, sigma=sigma, monitor=monitor)
+        self.collector = DeviceOffPolicyCollector(sim, self.nets, model.flat["actor"], self.replay, sigma=sigma, monitor=monitor,
+                                                  normalize=normalize)
         self._y = None
 
     def collect(self, steps, random, monitor=None):
@@ -167,7 +170,7 @@ class DeviceData:
         return self.replay.rows
 
     def sample(self, m):
-        return self.replay.sample(m)
+        return self.replay.sample(m, normalize=self.normalize)
 
     def td_target(self, next_obs, reward, done, gamma):
         return self.nets.td_target(self.model.flat["actor_target"], self.model.flat["critic_target"], next_obs, reward, done, gamma)
@@ -200,15 +203,48 @@ def train(sim, model, data, steps, batch=256, learning_starts=100, gamma=0.99, g
     return updates
 
 
-def evaluate(env_id, model, episodes, envs, device_data, device=0, seed=123):
-    """evaluate_policy with sigma = 0 -> (mean return, std, mean length)"""
+def add_vec_normalize_argument(ap):
+    ap.add_argument("--vec-normalize", action="store_true",
+                    help="SB3's VecNormalize on the device (needs --device-data): the actor acts on normalised observations, the buffer "
+                         "stores raw ones, every minibatch is normalised in the sampling kernel with the statistics of that moment; "
+                         "evaluation runs on the frozen statistics; --save-actor P also writes P.vecnormalize.npz")
+
+
+def check_vec_normalize(ap, a):
+    """the two refusals of --vec-normalize, the PPO tool's"""
+    if a.vec_normalize and not a.device_data:
+        ap.error("--vec-normalize requires --device-data (it runs between the simulator and the HIP kernels of the data path)")
+    if a.vec_normalize and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--vec-normalize runs on one rank only: merging the running statistics across ranks is not implemented")
+
+
+def make_vec_normalize(a, sim):
+    if not a.vec_normalize:
+        return None
+    from balance_robot_mujoco_rl_amd import DeviceVecNormalize
+    return DeviceVecNormalize(a.envs, device=sim.device, gamma=a.gamma)
+
+
+def save_vec_normalize(path, vecnorm):
+    """next to the saved actor: the normaliser's state_dict (what vecnorm.fold_vecnormalize and eval_quant_policy.py --vec-normalize read)"""
+    if vecnorm is not None:
+        np.savez(path + ".vecnormalize.npz", **vecnorm.state_dict())
+
+
+def normalized_act(act, normalize):
+    """evaluation on frozen statistics: the stateless normalize_obs in front of `act`"""
+    return act if normalize is None else (lambda obs, t: act(normalize.normalize_obs(obs), t))
+
+
+def evaluate(env_id, model, episodes, envs, device_data, device=0, seed=123, normalize=None):
+    """evaluate_policy with sigma = 0 -> (mean return, std, mean length); `normalize`: its statistics, frozen, in front of the actor"""
     from balance_robot_mujoco_rl_amd import BatchedSim, EpisodeMonitor, evaluate_policy
     sim = BatchedSim(env_id, envs, device=device, seed=seed, auto_reset=True)
     mon = EpisodeMonitor(envs, device=sim.device, max_len=max(1, int(sim.max_episode_steps)), log_capacity=episodes)
     if device_data:
         from balance_robot_mujoco_rl_amd.offpolicy import DeviceDDPGNets
         nets = DeviceDDPGNets(device=sim.device, seed=seed)
-        act = lambda obs, t: nets.act(model.flat["actor"], obs, t, 0.0)
+        act = normalized_act(lambda obs, t: nets.act(model.flat["actor"], obs, t, 0.0), normalize)
     else:
         def act(obs, t):
             with torch.no_grad():
@@ -218,7 +254,7 @@ def evaluate(env_id, model, episodes, envs, device_data, device=0, seed=123):
     return float(np.mean(ret)), float(np.std(ret)), float(np.mean(length))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="Env01-v1"); ap.add_argument("--envs", type=int, default=256)
     ap.add_argument("--steps", type=int, default=1000, help="env steps of every env")
@@ -235,16 +271,19 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--save-actor", default="", help="write the trained actor on exit: the flat vector as .npy, or a state_dict as .pt "
                                                      "(either is what tools/eval_quant_policy.py --actor PATH --algo ddpg reads)")
-    a = ap.parse_args()
+    add_vec_normalize_argument(ap)
+    a = ap.parse_args(argv)
     if a.device_learner and not a.device_data:
         ap.error("--device-learner requires --device-data")
+    check_vec_normalize(ap, a)
     from balance_robot_mujoco_rl_amd import BatchedSim, EpisodeMonitor, _lib
     sim = BatchedSim(a.env, a.envs, device=0, seed=a.seed, auto_reset=True)
     cap = a.capacity_steps or max(1, 1_000_000 // a.envs)
     model = DDPG(sim.device, lr=a.lr, tau=a.tau, seed=a.seed)
     start = {k: v.clone() for k, v in model.flat.items()}
     monitor = EpisodeMonitor(a.envs, device=sim.device, max_len=max(1, int(sim.max_episode_steps)))
-    data = DeviceData(sim, model, cap, a.sigma, a.seed) if a.device_data else TorchData(sim, model, cap, a.sigma, a.seed)
+    vecnorm = make_vec_normalize(a, sim)
+    data = DeviceData(sim, model, cap, a.sigma, a.seed, normalize=vecnorm) if a.device_data else TorchData(sim, model, cap, a.sigma, a.seed)
     log = {"args": vars(a), "build_id": _lib.build_id(), "data_path": "device" if a.device_data else "torch"}
     learner = None
     if a.device_learner:
@@ -261,7 +300,8 @@ def main():
                moved={k: float((model.flat[k] - start[k]).abs().max()) for k in start},
                finite=bool(all(torch.isfinite(v).all() for v in model.flat.values())))
     if a.eval_episodes:
-        log["eval_mean_return"], log["eval_std_return"], log["eval_mean_len"] = evaluate(a.env, model, a.eval_episodes, a.eval_envs, a.device_data)
+        log["eval_mean_return"], log["eval_std_return"], log["eval_mean_len"] = evaluate(a.env, model, a.eval_episodes, a.eval_envs, a.device_data,
+                                                                                         normalize=vecnorm)
     print(json.dumps(log))
     if a.save_actor:
         from balance_robot_mujoco_rl_amd import unflatten_ddpg_state_dict
@@ -270,12 +310,16 @@ def main():
             torch.save(unflatten_ddpg_state_dict(flat, "actor", "tool"), a.save_actor)
         else:
             np.save(a.save_actor, flat)
+        save_vec_normalize(a.save_actor, vecnorm)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(log, f, indent=1)
     if learner is not None:
         learner.close()
+    if vecnorm is not None:
+        vecnorm.close()
     monitor.close(); sim.close()
+    return log
 
 
 if __name__ == "__main__":

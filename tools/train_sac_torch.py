@@ -28,7 +28,8 @@ from torch import nn
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from train_ddpg_torch import CRITIC_SIZES, DeviceData, TorchData, flatten_module_, mlp  # noqa: E402
+from train_ddpg_torch import (CRITIC_SIZES, DeviceData, TorchData, add_vec_normalize_argument, check_vec_normalize, flatten_module_,  # noqa: E402
+                              make_vec_normalize, mlp, normalized_act, save_vec_normalize)
 
 LOG_STD_MIN, LOG_STD_MAX, EPS = -20.0, 2.0, 1e-6
 # --net-arch: the hidden widths of the actor and of the critics
@@ -143,12 +144,13 @@ class SACTorchData(TorchData):
 class SACDeviceData(DeviceData):
     """the --device-data path: brs_sac_act in the collector, one brs_sac_td_target per minibatch, its draw counted here"""
 
-    def __init__(self, sim, model, cap, seed, monitor=None):
+    def __init__(self, sim, model, cap, seed, monitor=None, normalize=None):
         from balance_robot_mujoco_rl_amd.offpolicy import DeviceOffPolicyCollector, DeviceReplayBuffer, DeviceSACNets
-        self.sim, self.model = sim, model
+        self.sim, self.model, self.normalize = sim, model, normalize
         self.nets = DeviceSACNets(device=sim.device, seed=seed, net_arch=model.net_arch)
         self.replay = DeviceReplayBuffer(sim.n, cap, device=sim.device, seed=seed)
-        self.collector = DeviceOffPolicyCollector(sim, self.nets, model.flat["actor"], self.replay, sigma=0.0, monitor=monitor)
+        self.collector = DeviceOffPolicyCollector(sim, self.nets, model.flat["actor"], self.replay, sigma=0.0, monitor=monitor,
+                                                  normalize=normalize)
         self.target_draw = 0
 
     def td_target(self, next_obs, reward, done, gamma):
@@ -187,15 +189,16 @@ def train(sim, model, data, steps, batch=256, learning_starts=100, gamma=0.99, g
     return updates
 
 
-def evaluate(env_id, model, episodes, envs, device_data, device=0, seed=123):
-    """evaluate_policy with deterministic=True -> (mean return, std, mean length)"""
+def evaluate(env_id, model, episodes, envs, device_data, device=0, seed=123, normalize=None):
+    """evaluate_policy with deterministic=True -> (mean return, std, mean length); `normalize`: its statistics, frozen, in front of
+    the actor"""
     from balance_robot_mujoco_rl_amd import BatchedSim, EpisodeMonitor, evaluate_policy
     sim = BatchedSim(env_id, envs, device=device, seed=seed, auto_reset=True)
     mon = EpisodeMonitor(envs, device=sim.device, max_len=max(1, int(sim.max_episode_steps)), log_capacity=episodes)
     if device_data:
         from balance_robot_mujoco_rl_amd.offpolicy import DeviceSACNets
         nets = DeviceSACNets(device=sim.device, seed=seed, net_arch=model.net_arch)
-        act = lambda obs, t: nets.act(model.flat["actor"], obs, t, deterministic=True)
+        act = normalized_act(lambda obs, t: nets.act(model.flat["actor"], obs, t, deterministic=True), normalize)
     else:
         def act(obs, t):
             with torch.no_grad():
@@ -226,9 +229,11 @@ def main(argv=None):
     ap.add_argument("--out", default="")
     ap.add_argument("--save-actor", default="", help="write the trained actor on exit: the flat vector as .npy, or a state_dict as .pt "
                                                      "(either is what tools/eval_quant_policy.py --actor PATH --algo sac reads)")
+    add_vec_normalize_argument(ap)
     a = ap.parse_args(argv)
     if a.device_learner and not a.device_data:
         ap.error("--device-learner requires --device-data")
+    check_vec_normalize(ap, a)
     if a.ent_coef != "auto":
         try:
             ok = float(a.ent_coef) > 0 and math.isfinite(float(a.ent_coef))
@@ -244,7 +249,8 @@ def main(argv=None):
     model = SAC(sim.device, lr=a.lr, tau=a.tau, seed=a.seed, ent_coef=a.ent_coef, target_entropy=a.target_entropy, net_arch=a.net_arch)
     start = {k: v.clone() for k, v in model.flat.items()}
     monitor = EpisodeMonitor(a.envs, device=sim.device, max_len=max(1, int(sim.max_episode_steps)))
-    data = SACDeviceData(sim, model, cap, a.seed) if a.device_data else SACTorchData(sim, model, cap, 0.0, a.seed)
+    vecnorm = make_vec_normalize(a, sim)
+    data = SACDeviceData(sim, model, cap, a.seed, normalize=vecnorm) if a.device_data else SACTorchData(sim, model, cap, 0.0, a.seed)
     log = {"args": vars(a), "build_id": _lib.build_id(), "data_path": "device" if a.device_data else "torch"}
     learner = None
     if a.device_learner:
@@ -262,7 +268,8 @@ def main(argv=None):
                       "log_ent_coef": float((model.flat["actor"][-1] - start["actor"][-1]).abs())},
                finite=bool(all(torch.isfinite(v).all() for v in model.flat.values())))
     if a.eval_episodes:
-        log["eval_mean_return"], log["eval_std_return"], log["eval_mean_len"] = evaluate(a.env, model, a.eval_episodes, a.eval_envs, a.device_data)
+        log["eval_mean_return"], log["eval_std_return"], log["eval_mean_len"] = evaluate(a.env, model, a.eval_episodes, a.eval_envs, a.device_data,
+                                                                                         normalize=vecnorm)
     print(json.dumps(log))
     if a.save_actor:
         from balance_robot_mujoco_rl_amd import unflatten_sac_actor
@@ -271,11 +278,14 @@ def main(argv=None):
             torch.save(unflatten_sac_actor(flat, "tool"), a.save_actor)
         else:
             np.save(a.save_actor, flat)
+        save_vec_normalize(a.save_actor, vecnorm)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(log, f, indent=1)
     if learner is not None:
         learner.close()
+    if vecnorm is not None:
+        vecnorm.close()
     monitor.close(); sim.close()
     return log
 

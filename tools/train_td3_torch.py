@@ -25,7 +25,8 @@ from torch import nn
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from train_ddpg_torch import ACTOR_SIZES, CRITIC_SIZES, DeviceData, TorchData, evaluate, flatten_module_, mlp  # noqa: E402
+from train_ddpg_torch import (ACTOR_SIZES, CRITIC_SIZES, DeviceData, TorchData, add_vec_normalize_argument, check_vec_normalize,  # noqa: E402
+                              evaluate, flatten_module_, make_vec_normalize, mlp, save_vec_normalize)
 
 
 class TD3:
@@ -82,8 +83,8 @@ class TD3:
 class TD3DeviceData(DeviceData):
     """the DDPG tool's device data path with the TD3 target: one brs_td3_td_target per minibatch, its draw counted here"""
 
-    def __init__(self, sim, model, cap, sigma, seed, monitor=None):
-        super().__init__(sim, model, cap, sigma, seed, monitor)
+    def __init__(self, sim, model, cap, sigma, seed, monitor=None, normalize=None):
+        super().__init__(sim, model, cap, sigma, seed, monitor, normalize=normalize)
         self.target_draw = 0
 
     def td_target(self, next_obs, reward, done, gamma):
@@ -151,9 +152,11 @@ def main(argv=None):
     ap.add_argument("--out", default="")
     ap.add_argument("--save-actor", default="", help="write the trained actor on exit: the flat vector as .npy, or a state_dict as .pt "
                                                      "(either is what tools/eval_quant_policy.py --actor PATH --algo td3 reads)")
+    add_vec_normalize_argument(ap)
     a = ap.parse_args(argv)
     if a.device_learner and not a.device_data:
         ap.error("--device-learner requires --device-data")
+    check_vec_normalize(ap, a)
     if a.policy_delay < 1:
         ap.error("--policy-delay must be at least 1")
     if not (a.target_policy_noise >= 0 and a.target_noise_clip >= 0):
@@ -165,7 +168,8 @@ def main(argv=None):
                 target_noise_clip=a.target_noise_clip)
     start = {k: v.clone() for k, v in model.flat.items()}
     monitor = EpisodeMonitor(a.envs, device=sim.device, max_len=max(1, int(sim.max_episode_steps)))
-    data = TD3DeviceData(sim, model, cap, a.sigma, a.seed) if a.device_data else TorchData(sim, model, cap, a.sigma, a.seed)
+    vecnorm = make_vec_normalize(a, sim)
+    data = TD3DeviceData(sim, model, cap, a.sigma, a.seed, normalize=vecnorm) if a.device_data else TorchData(sim, model, cap, a.sigma, a.seed)
     log = {"args": vars(a), "build_id": _lib.build_id(), "data_path": "device" if a.device_data else "torch"}
     learner = None
     if a.device_learner:
@@ -182,7 +186,8 @@ def main(argv=None):
                moved={k: float((model.flat[k] - start[k]).abs().max()) for k in start},
                finite=bool(all(torch.isfinite(v).all() for v in model.flat.values())))
     if a.eval_episodes:
-        log["eval_mean_return"], log["eval_std_return"], log["eval_mean_len"] = evaluate(a.env, model, a.eval_episodes, a.eval_envs, a.device_data)
+        log["eval_mean_return"], log["eval_std_return"], log["eval_mean_len"] = evaluate(a.env, model, a.eval_episodes, a.eval_envs, a.device_data,
+                                                                                         normalize=vecnorm)
     print(json.dumps(log))
     if a.save_actor:
         from balance_robot_mujoco_rl_amd import unflatten_ddpg_state_dict
@@ -191,11 +196,14 @@ def main(argv=None):
             torch.save(unflatten_ddpg_state_dict(flat, "actor", "tool"), a.save_actor)
         else:
             np.save(a.save_actor, flat)
+        save_vec_normalize(a.save_actor, vecnorm)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(log, f, indent=1)
     if learner is not None:
         learner.close()
+    if vecnorm is not None:
+        vecnorm.close()
     monitor.close(); sim.close()
     return log
 

@@ -10,6 +10,12 @@
   collect()     wall time of DeviceRollout.collect() with and without a normaliser (Env01-v2, 16,384 envs, five steps: the A2C
                 configuration of DESIGN.md 7.9), alternating, three repeats
       python3 tools/vecnorm_kernel_time.py --collect
+  replay sample the normalising replay sample of DESIGN.md 7.14 -> profiles/vecnorm_replay_kernel_time.json: microseconds per
+                minibatch of 256 and of 4,096 from a buffer of 16,384 envs, three variants in one process, alternating, with the
+                step time's warm-up, calls and repeats: the plain sample (one launch), the plain sample followed by normalize_obs
+                twice and normalize_reward (four launches, what the parent can do), and sample(normalize=) (one launch).  The
+                required relation: the slowest repeat of the fused call is not slower than the fastest of the four composed calls.
+      python3 tools/vecnorm_kernel_time.py --replay [--out FILE]
 """
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -128,14 +134,70 @@ def collect_times(envs, T, rounds, repeats):
                 added_share=round(min(ms[True]) / min(ms[False]) - 1, 4))
 
 
+def replay_times(envs, cap, warmup, calls, repeats, batches=(256, 4096)):
+    import torch
+    from balance_robot_mujoco_rl_amd import DeviceReplayBuffer, DeviceVecNormalize, _lib
+    dev = torch.device("cuda", 0)
+    rb, norm = DeviceReplayBuffer(envs, cap, device=0, seed=3), DeviceVecNormalize(envs, device=0)
+    norm.reset(_inputs(envs, dev)[0])
+    last = _inputs(envs, dev)[0]
+    for t in range(cap):   # a full buffer of raw transitions, the statistics trained on them
+        obs, rew, te, tr, tobs = _inputs(envs + t + 1, dev)
+        obs, tobs = obs[:envs].contiguous(), tobs[:envs].contiguous()
+        rew, te, tr = rew[:envs].contiguous(), te[:envs].contiguous(), tr[:envs].contiguous()
+        norm.step(obs, rew, te, tr, tobs)
+        rb.add(last, torch.zeros((envs, 2), device=dev), obs, tobs, rew, te, tr)
+        last = obs
+    res = dict(command="python3 tools/vecnorm_kernel_time.py --replay", build_id=_lib.build_id(), units="microseconds per minibatch",
+               envs=envs, capacity_steps=cap, warmup=warmup, calls=calls, repeats=repeats, batches={})
+    for m in batches:
+        out, tmp = rb.new_batch(m), rb.new_batch(m)
+
+        def plain():
+            rb.sample(m, out=out)
+
+        def composed():
+            rb.sample(m, out=tmp)
+            norm.normalize_obs(tmp[0], out=out[0]); norm.normalize_obs(tmp[1], out=out[1]); norm.normalize_reward(tmp[3], out=out[3])
+
+        def fused():
+            rb.sample(m, out=out, normalize=norm)
+        variants = {"plain": plain, "composed": composed, "fused": fused}
+        for fn in variants.values():
+            for _ in range(warmup):
+                fn()
+        torch.cuda.synchronize()
+        us = {k: [] for k in variants}
+        for _ in range(repeats):
+            for k, fn in variants.items():   # alternating, so that all see the same clocks
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    fn()
+                torch.cuda.synchronize()
+                us[k].append(round((time.perf_counter() - t0) / calls * 1e6, 2))
+        # the same draw through the composed and the fused path: the same bytes
+        rb.draw = 7; composed(); a = [t.clone() for t in (out[0], out[1], out[3])]
+        rb.draw = 7; fused(); same = all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, (out[0], out[1], out[3])))
+        res["batches"][str(m)] = dict(plain_us=us["plain"], composed_four_calls_us=us["composed"], fused_us=us["fused"],
+                                      slowest_fused_over_fastest_composed=round(max(us["fused"]) / min(us["composed"]), 3),
+                                      fused_over_plain=round(min(us["fused"]) / min(us["plain"]), 3), fused_equals_composed_bytes=same,
+                                      requirement_met=max(us["fused"]) <= min(us["composed"]))
+    norm.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--replay", action="store_true"); ap.add_argument("--capacity-steps", type=int, default=8)
     ap.add_argument("--collect", action="store_true"); ap.add_argument("--envs", type=int, default=16384); ap.add_argument("--T", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10); ap.add_argument("--calls", type=int, default=200); ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    res = collect_times(a.envs, a.T, a.rounds, a.repeats) if a.collect else step_times(a.warmup, a.calls, a.repeats)
+    if a.replay:
+        res = replay_times(a.envs, a.capacity_steps, a.warmup, a.calls, a.repeats)
+    else:
+        res = collect_times(a.envs, a.T, a.rounds, a.repeats) if a.collect else step_times(a.warmup, a.calls, a.repeats)
     text = json.dumps(res, indent=1)
     print(text)
     if a.out:
